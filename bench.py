@@ -208,9 +208,9 @@ def host_info():
 
 def reference_cg():
     """(fn, kind, where): the reference's OWN cg (betty/hypergradient/cg.py:8-70) when its package is importable — the staged,
-    git-ignored copy oracle/_ref/betty that `make -C oracle ref` takes from the checkout, or /root/reference itself — else the
-    line-for-line restatement oracle/hypergrad_oracle.py (pinned bit-for-bit against it, tests/test_oracle.py)."""
-    for where in (os.path.join(ROOT, "oracle", "_ref"), "/root/reference"):
+    git-ignored copy oracle/_ref/betty that `make -C oracle ref` takes from the checkout — else the line-for-line restatement
+    oracle/hypergrad_oracle.py (pinned bit-for-bit against it, tests/test_oracle.py)."""
+    for where in (os.path.join(ROOT, "oracle", "_ref"),):
         if os.path.isdir(os.path.join(where, "betty", "hypergradient")):
             try:
                 if where not in sys.path:
@@ -586,7 +586,14 @@ def main():
     ap.add_argument("--debug", action="append", default=[], metavar="KEY=INT",
                     help="select a measurement arm of libbhg through bhg_debug_set (the library reads no environment variable); "
                          "repeatable, e.g. --debug packed_chain=0 --debug mlp_proj=0.  Echoed in config.debug_arms")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last full-K step — the upper problem's "
+                         "hypergradient, i.e. the .grad of every meta-weight-net parameter that cg(vector, curr, prev, sync=True) "
+                         "accumulates — as DIR/hypergrad.<parameter>.npy (float32, rank 0).  The inputs are seeded: with the same "
+                         "arguments two builds can be compared output for output")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(args)
 
@@ -713,6 +720,12 @@ def main():
         torch.cuda.synchronize()
         return time.perf_counter() - t0
 
+    def snapshot():
+        """--dump-outputs: the hypergradient the last step left in the upper parameters' .grad, copied to the host (outside every
+        timed region)."""
+        return {f"hypergrad.{name}": p.grad.detach().float().cpu().numpy() for name, p in prev.module.named_parameters()}
+
+    dumped = None
     for _ in range(args.warmup):
         step()
     # Settle (untimed, reported as `settle_steps`): W = 5 warm-up steps are 7 ms of GPU work — the first timed region of a 20-step run
@@ -758,6 +771,8 @@ def main():
     for rep in range(reps):
         c0, c1 = int(be.lib.bhg_mlp_hoist_launches()), int(be.lib.bhg_mlp_proj_iterations())
         t_full.append(timed_region(args.steps))
+        if args.dump_outputs and rep == reps - 1:
+            dumped = snapshot()
         if rep == 0:
             n_hoist, n_proj = int(be.lib.bhg_mlp_hoist_launches()) - c0, int(be.lib.bhg_mlp_proj_iterations()) - c1
         if slope:
@@ -813,6 +828,8 @@ def main():
 
         be.lib.bhg_timing_enable(1)
         elapsed_timed = timed_region(args.steps)
+        if args.dump_outputs:
+            dumped = snapshot()
         for name, kind in (("cg_step", 0), ("neumann_step", 1), ("hvp", 2), ("cg_iter", 3)):
             tot, cnt = ctypes.c_double(0.0), ctypes.c_int(0)
             _native.check(be.lib.bhg_timing_read(kind, ctypes.byref(tot), ctypes.byref(cnt)), "bhg_timing_read")
@@ -829,6 +846,14 @@ def main():
     finite = all(bool(torch.isfinite(p.grad).all()) for p in prev.parameters())
     if not finite:
         raise SystemExit("bench.py: non-finite hypergradient — refusing to report a throughput for a wrong result")
+    if dumped is not None and rank == 0:
+        import numpy as np
+
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, arr in dumped.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), arr)
+        print(f"bench.py: wrote {len(dumped)} arrays ({sum(a.nbytes for a in dumped.values())} bytes) of the last timed step to "
+              f"{args.dump_outputs}", file=sys.stderr)
     parity = parity_check(args, device, jvp_fn, curr, prev, vector, K) if (world == 1 and not args.no_parity) else None
     census = device_census(dist, world, rank, device, M)
     secondary = None

@@ -13,7 +13,8 @@ Round 6 adds SHORT-HORIZON goldens of the same named network (K = 3): the fp32-v
 number of Neumann terms (9.9e-4 at K = 20: below what fp32 resolves across devices) — at K = 3 it is far below north_star's rtol 1e-4,
 so the GPU test can hold the product to 1e-4 against the reference's own CPU output there.
 
-Usage:  python tests/golden/make_cfg5_golden.py            (build container only: needs /root/reference; 8 threads; K = 20: ~35 min)
+Usage:  python tests/golden/make_cfg5_golden.py            (build container only: needs /root/reference and the model files
+                                                           staged by `make -C oracle ref`; 8 threads; K = 20: ~35 min)
         python tests/golden/make_cfg5_golden.py 3 [5 ...]  (adds / refreshes neumann<K> entries, keeps the others of the file as they are)
 """
 import os

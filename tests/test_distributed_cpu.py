@@ -347,7 +347,7 @@ def _fsdp_darts_worker(rank, world, port, q):
         import hypergrad_oracle as horc
         import zoo
         from _cpu_checker_backend import CpuCheckerBackend
-        from conftest import load_golden
+        from conftest import golden_list, load_golden
 
         from betty_amd import Config
         from betty_amd import hypergradient as hg
@@ -377,16 +377,10 @@ def _fsdp_darts_worker(rank, world, port, q):
             got = hg.darts(vector, curr, prev, False)
             drift = max(float((p.data - w).abs().max()) for p, w in zip(curr.trainable_parameters(), w0))
         err = max(float((a - b).abs().max() / b.abs().max().clamp_min(1e-30)) for a, b in zip(got, want))
-        ref_err = -1.0
-        if os.path.isdir("/root/reference/betty"):              # the live reference, same two ranks
-            sys.path.insert(0, "/root/reference")
-            import betty.hypergradient  # noqa: F401
-            from betty.configs import Config as RefConfig
-
-            ref_darts = sys.modules["betty.hypergradient.darts"].darts
-            curr, prev, vector = build(RefConfig)
-            ref = ref_darts(vector, curr, prev, False)
-            ref_err = max(float((a - b).abs().max()) for a, b in zip(want, ref))   # oracle == reference, bitwise
+        # the reference's own output on the same two ranks (tests/golden/make_live_golden.py): oracle == reference, bitwise
+        ref = golden_list(load_golden("live_reference")[1], "fsdp_darts", f"rank{rank}")
+        assert len(ref) == len(want)
+        ref_err = max(float(np.abs(a.detach().numpy() - b).max()) for a, b in zip(want, ref))
         q.put((rank, err, drift, ref_err, local_sq, float(all_sq)))
     finally:
         dist.destroy_process_group()
@@ -395,7 +389,7 @@ def _fsdp_darts_worker(rank, world, port, q):
 def test_darts_fsdp_branch_uses_the_norm_of_the_whole_sharded_vector():
     """darts.py:31-34: under FSDP every rank holds a shard of the direction, eps = R / ||whole vector||.
     Two gloo ranks with different shards: the product (checker backend) matches the oracle's restatement, the
-    oracle matches the live reference bit for bit (when the checkout is present), weights are restored."""
+    oracle matches the reference's own output on the same ranks bit for bit, weights are restored."""
     world = 2
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
@@ -412,7 +406,7 @@ def test_darts_fsdp_branch_uses_the_norm_of_the_whole_sharded_vector():
         assert all_sq > local_sq
         assert err < 2e-3, (rank, err)          # finite differences: the darts tolerance of the golden cases
         assert drift < 2e-7, (rank, drift)
-        assert ref_err in (-1.0, 0.0), (rank, ref_err)
+        assert ref_err == 0.0, (rank, ref_err)
 
 
 # ------------------------------------------------------------------------------------------------

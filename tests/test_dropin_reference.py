@@ -1,7 +1,7 @@
 """Drop-in under the REAL reference: `betty_amd.install()` replaces the registry entries of a live
 `betty.hypergradient` and the reference's own Engine/Problem (unmodified, imported from the checkout named by
 $BETTY_REF; default: oracle/_ref — the git-ignored staging copy `make -C oracle ref` / `__graft_entry__.build()` takes
-in the build container and gpurun ships to the GPU box — else /root/reference) drives our cg/neumann/darts through
+where a reference checkout exists, and which travels with the built tree to the GPU machine) drives our cg/neumann/darts through
 `Problem.backward -> get_grads`.
   * in the build container (no GPU) the kernels are the C oracle via the test-only checker backend;
   * `-m gpu`: the SAME scenario with the reference's Engine over the HIP kernels (`HipBackend`) — the two halves of the
@@ -16,7 +16,7 @@ import torch
 import torch.nn.functional as F
 
 _STAGED = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref")
-REF = os.environ.get("BETTY_REF") or (_STAGED if os.path.isdir(os.path.join(_STAGED, "betty")) else "/root/reference")
+REF = os.environ.get("BETTY_REF") or _STAGED
 pytestmark = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "betty")), reason="reference checkout not present")
 
 

@@ -255,6 +255,23 @@ def test_pointwise_conv_matches_conv2d_value_gradient_and_hessian_vector_product
 
 @pytest.mark.gpu
 def test_pointwise_conv_on_the_gpu_matches_conv2d_gradient_and_hvp():
+    """The yardstick convolutions run on ATen's own kernels, not MIOpen's: which MIOpen solver takes these 1 x 1 shapes (and the kernels
+    it compiles for them at first use) differs from machine to machine, and on a freshly provisioned one this test aborted the process
+    inside that double backward.  What is compared — the matrix-product layer against nn.Conv2d's gradient and Hessian-vector product —
+    does not depend on which library computes nn.Conv2d."""
+    was = torch.backends.cudnn.enabled
+    torch.backends.cudnn.enabled = False
+    try:
+        res = _pointwise_conv_gradient_and_hvp_on_the_gpu()
+    finally:
+        torch.backends.cudnn.enabled = was
+    e_g, _ = rel_err(res[True][0], res[False][0])
+    e_h, _ = rel_err(res[True][1], res[False][1])
+    print(f"PointwiseConv2d vs nn.Conv2d on the GPU: gradient {e_g:.2e}, Hessian-vector product {e_h:.2e}")
+    assert e_g <= 1e-5 and e_h <= 1e-4, (e_g, e_h)
+
+
+def _pointwise_conv_gradient_and_hvp_on_the_gpu():
     res = {}
     for declared in (False, True):
         torch.manual_seed(4)
@@ -269,7 +286,4 @@ def test_pointwise_conv_on_the_gpu_matches_conv2d_gradient_and_hvp():
         grads = torch.autograd.grad(F.cross_entropy(net(x), y), params, create_graph=True)
         hv = torch.autograd.grad(grads, params, grad_outputs=vec)
         res[declared] = ([t.detach().cpu().numpy() for t in grads], [t.cpu().numpy() for t in hv])
-    e_g, _ = rel_err(res[True][0], res[False][0])
-    e_h, _ = rel_err(res[True][1], res[False][1])
-    print(f"PointwiseConv2d vs nn.Conv2d on the GPU: gradient {e_g:.2e}, Hessian-vector product {e_h:.2e}")
-    assert e_g <= 1e-5 and e_h <= 1e-4, (e_g, e_h)
+    return res

@@ -528,11 +528,10 @@ def attach_prox_structure(curr):
 # ------------------------------------------------------------------------------------------------------------------------------------
 # BASELINE.json cfg 5 AS NAMED: the reference's own DARTS supernet `Network(16, 10, 8)` (1,930,618 parameters in 1,399 tensors) and
 # `Architecture(4)` (2 x 14 x 8 = 224) — examples/neural_architecture_search/model_search.py:129-234,302-317 — on the example's batch
-# 64 x 3 x 32 x 32 (train_search.py:24), Neumann K = 20.  The model files are the reference's own: read from the checkout in the build
-# container (tests/golden/make_cfg5_golden.py) or from the staged, git-ignored, test-only copy oracle/_ref/examples_nas on the GPU box.
+# 64 x 3 x 32 x 32 (train_search.py:24), Neumann K = 20.  The model files are the reference's own: read from the staged, git-ignored,
+# test-only copy oracle/_ref/examples_nas that `make -C oracle ref` takes from a reference checkout (tests/golden/make_cfg5_golden.py reads the checkout).
 # ------------------------------------------------------------------------------------------------------------------------------------
-NAS_DIRS = (os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref", "examples_nas"),
-            "/root/reference/examples/neural_architecture_search")
+NAS_DIRS = (os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref", "examples_nas"),)
 CFG5_SEED, CFG5_K, CFG5_ALPHA, CFG5_BATCH = 5, 20, 0.01, 64
 
 
