@@ -167,6 +167,16 @@ SYMBOLS = {
     "bhg_mlp_forward_packed": (c_int, [POINTER(Mlp), _PP, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "bhg_mlp_backward_packed": (c_int, [POINTER(Mlp), c_void_p, c_void_p, c_size_t, c_void_p]),
     "bhg_mwn_max_hidden": (c_int, []),
+    "bhg_mlp_fd_ws_bytes": (c_size_t, [POINTER(c_int), c_int, c_int]),
+    "bhg_mlp_fd_forward": (
+        c_int,
+        [c_void_p, c_void_p, c_int, POINTER(c_int), c_int, _PP, _PP, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p],
+    ),
+    "bhg_mwn_fd_vjp": (
+        c_int,
+        [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+         c_void_p],
+    ),
     "bhg_mwn_forward": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "bhg_mwn_backward": (
         c_int,

@@ -627,3 +627,62 @@ def make_state(spec, x, y):
     if (PAD_WIDTHS_TO_32 and getattr(spec, "pad_widths", True) and len(Ws) >= 3 and dims[-1] <= 256 and padded_dims(dims) != dims and x.is_cuda):
         return PaddedHipMLPState(spec, x, y)
     return HipMLPState(spec, x, y)
+
+
+# ---- finite-difference hop (darts / sama; csrc/bhg_fd.hip) ---------------------------------------------------------------------------
+_FD_WS = weakref.WeakKeyDictionary()   # first nn.Linear of a network -> {(dims, B, device): workspace}
+
+
+def fd_hop(spec, vector, eps32, two_eps, x, y, upper, sync: bool, restore: bool):
+    """WeightedCEMLP.finite_difference on the HIP kernels: CE at w+ and w- in one launch chain that also leaves the inner weights where
+    the reference's three axpys leave them (any widths: no padded twin needed), then the upper half — the closed-form meta-weight-net
+    (one launch for both points) or autograd over weight_fn."""
+    lib = _native.load()
+    params = [t for lin in spec.layers for t in (lin.weight, lin.bias)]
+    L, B = len(spec.layers), int(x.shape[0])
+    dims = [spec.layers[0].weight.shape[1]] + [lin.weight.shape[0] for lin in spec.layers]
+    dims_c = (ctypes.c_int * len(dims))(*dims)
+    dev = params[0].device
+    xs = x.detach().reshape(B, -1)
+    xs = xs if (xs.dtype == torch.float32 and xs.is_contiguous()) else xs.to(torch.float32).contiguous()
+    ys = y.detach().reshape(-1).to(device=dev, dtype=torch.int64).contiguous()
+    dirs = [v if (v.dtype == torch.float32 and v.is_contiguous()) else v.detach().to(torch.float32).contiguous() for v in vector]
+    owner = _FD_WS.setdefault(spec.layers[0], {})
+    key = (tuple(dims), B, str(dev))
+    ws = owner.get(key)
+    if ws is None:
+        n = int(lib.bhg_mlp_fd_ws_bytes(dims_c, L, B))
+        if n <= 0:
+            raise _native.NativeLibraryError(f"bhg_mlp_fd_ws_bytes refused widths {dims} at batch {B}")
+        ws = owner[key] = torch.empty(n, dtype=torch.uint8, device=dev)
+    ce = torch.empty(2, B, dtype=torch.float32, device=dev)
+    eps = eps32 if (eps32.dtype == torch.float32 and eps32.device == dev) else eps32.to(device=dev, dtype=torch.float32)
+    ptab, _pk = _native.ptr_array([p.data.data_ptr() for p in params])
+    dtab, _dk = _native.ptr_array([d.data_ptr() for d in dirs])
+    _native.check(lib.bhg_mlp_fd_forward(xs.data_ptr(), ys.data_ptr(), B, dims_c, L, ptab, dtab, eps.data_ptr(), int(restore),
+                                         ce[0].data_ptr(), ce[1].data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "bhg_mlp_fd_forward")
+    wn = spec.weight_net
+    ts = [t.detach() for t in wn.tensors()] if wn is not None else None
+    slots = wn.slots(upper) if wn is not None else None
+    native_upper = (ts is not None and slots is not None and ts[0].shape[0] <= int(lib.bhg_mwn_max_hidden())
+                    and all(t.is_cuda and t.device == dev and t.dtype == torch.float32 and t.is_contiguous() for t in ts))
+    if not native_upper:
+        return spec.fd_upper_autograd(ce[0], ce[1], two_eps, upper, sync)
+    if sync:
+        for p in upper:   # darts.py:44-53 accumulate into .grad (in place, as autograd's accumulation does)
+            if p.grad is None:
+                p.grad = torch.zeros_like(p, memory_format=torch.contiguous_format)
+            elif not (p.grad.dtype == torch.float32 and p.grad.is_contiguous()):
+                p.grad = p.grad.to(torch.float32).contiguous()
+        outs = [p.grad for p in upper]
+    else:
+        flat = torch.empty(sum(p.numel() for p in upper), dtype=torch.float32, device=dev)
+        outs, off = [], 0
+        for p in upper:
+            outs.append(flat[off: off + p.numel()].view(p.shape))
+            off += p.numel()
+    g = [outs[i] for i in slots]   # (w1, b1, w2, b2) -> their slots in `upper`
+    _native.check(lib.bhg_mwn_fd_vjp(ce[0].data_ptr(), ce[1].data_ptr(), B, ts[0].data_ptr(), ts[1].data_ptr(), ts[2].data_ptr(),
+                                     ts[3].data_ptr(), ts[0].shape[0], two_eps.data_ptr(), int(sync), g[0].data_ptr(), g[1].data_ptr(),
+                                     g[2].data_ptr(), g[3].data_ptr(), _stream()), "bhg_mwn_fd_vjp")
+    return None if sync else outs

@@ -4,12 +4,17 @@ Behavioural twin of /root/reference betty/hypergradient/darts.py:8-69.  The vect
 ``||v||``, the three in-place perturbations of the live inner weights — is four multi-tensor
 launches (40*N bytes) instead of ``cat`` + ``norm`` + 3*T ``add_`` calls, and ``eps`` stays on
 the device (the reference synchronises the host with ``.item()``, darts.py:35).
+
+An inner problem with a structure (``hypergradient_structure``, structured.py) whose provider offers ``finite_difference`` takes
+the whole hop from it — for WeightedCEMLP two native forward passes instead of two ``training_step`` calls through autograd — and
+everything else (no structure, FSDP, a collective, upper parameters the structure does not describe) runs the opaque path below.
 """
 from __future__ import annotations
 
 import torch
 
 from ..backend import get_backend
+from .structured import structured_hvp_for
 from .utils import grad, replace_none_with_zero
 
 
@@ -34,6 +39,13 @@ def darts(vector, curr, prev, sync):
         norm = sq.sqrt().add_(1e-15)
         eps64 = float(config.darts_alpha) / norm.to(torch.float64)
         eps32 = eps64.to(torch.float32)
+    if not is_fsdp:
+        provider = structured_hvp_for(curr, prev)
+        fd = getattr(provider, "finite_difference", None)
+        if fd is not None:
+            out = fd(layout, vector, eps32, eps64, sync, restore=not config.darts_multitask)
+            if out is not NotImplemented:
+                return out
     two_eps = (2.0 * eps64).to(torch.float32)  # the reference divides fp32 tensors by the Python float 2*eps
 
     # w <- w + eps*v   (darts.py:37-38)

@@ -6,13 +6,15 @@ derivative of the inner optimizer's update w.r.t. the gradient (identity for SGD
 of utils.py:37-63 for Adam, built from ``exp_avg``, ``exp_avg_sq`` and the ``last_grad`` the problem
 records in ``optimizer_step``), then the same central finite difference as ``darts`` is applied with
 radius ``sama_adam_alpha``.  The preconditioner is ONE fused kernel over the four tensor lists
-(20*N bytes) writing a flat vector; norm and weight perturbations reuse the darts kernels.
+(20*N bytes) writing a flat vector; norm and weight perturbations reuse the darts kernels.  A structured inner problem whose
+provider offers ``finite_difference`` takes the hop from it on the preconditioned direction, as darts does.
 """
 from __future__ import annotations
 
 import torch
 
 from ..backend import get_backend
+from .structured import structured_hvp_for
 from .utils import grad, replace_none_with_zero
 
 
@@ -87,6 +89,14 @@ def sama(vector, curr, prev, sync):
 
     layout, pv = precondition(vector, curr, be)  # sama.py:25
     eps32, eps64, _ = be.darts_eps(layout, pv, float(config.sama_adam_alpha))  # sama.py:26-27
+    provider = structured_hvp_for(curr, prev)
+    fd = getattr(provider, "finite_difference", None)
+    if fd is not None:
+        out = fd(layout, pv, eps32, eps64, sync, restore=not config.sama_multitask)
+        if out is not NotImplemented:
+            if config.sama_multitask:   # sama.py:54-55
+                curr.synchronize_params(curr.meta_trainable_parameters(), all_reduce=True)
+            return out
     two_eps = (2.0 * eps64).to(torch.float32)
 
     be.axpy_multi(layout, weights, pv, eps32, 1.0)  # sama.py:29-30

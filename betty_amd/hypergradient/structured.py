@@ -21,6 +21,13 @@ Optional "one pass" extension: ``token = provider.fused_cg(layout, x, r, p, K, a
 whole K loop natively and returns a truthy value — ``True``, or a token object that cg/neumann hand back as
 ``provider.mixed_vjp(views, sync, solve=token)`` so the provider knows the views are the solution of exactly that run
 (a provider that never materialises the solution must be told; it cannot read the views).
+
+Optional finite-difference extension (darts, sama): ``out = provider.finite_difference(layout, vector, eps32, eps64, sync, restore)``
+runs the whole hop of betty/hypergradient/darts.py:37-67 (sama.py:29-59 with ``vector`` preconditioned) — perturb the live inner weights
+by ``+eps v``, evaluate, by ``-2 eps v``, evaluate, restore by ``+eps v`` unless ``restore`` is False (``*_multitask``) — from the
+structure instead of two opaque ``training_step`` calls, and returns the list (``sync=False``) or accumulates into ``.grad`` in the
+reference's order and returns None (``sync=True``).  It returns ``NotImplemented``, having touched nothing, when the structure does not
+cover the hop; darts / sama then take the opaque path.
 """
 from __future__ import annotations
 
@@ -469,6 +476,124 @@ class WeightedCEMLP:
         # second direction buffer: the R-backward GEMMs of an HVP still read v while its epilogues write v'
         v_alt = next(t for t in layout.state(3) if t is not v and t is not p)
         return self._state.neumann_solve(layout, v, v_alt, p, K, alpha, self.hvp_shift, keep_p=self.keep_solution)
+
+    # ---------------------------------------------------------------------------------------------
+    # Finite-difference hop (darts / sama): for L_in = (1/B) sum_i s_lam(CE_i.detach()) CE_i(w) + ridge ||w||^2 the derivative of the
+    # inner loss w.r.t. the upper parameters is g(w) = d/d(lam) sum_i (CE_i(w) / B) s_lam(CE_i(w)) — the VJP of the sample weights with
+    # cotangent CE / B.  The inner network only contributes per-sample CE at w+ and w-: two forward passes (csrc/bhg_fd.hip), no
+    # backward through it, no training_step.  Single-rank only: a collective (a DDP wrapper, average_over, more than one rank) and FSDP
+    # keep the opaque path.
+    def _fd_applies(self, layout, vector):
+        """Why not: a short reason string, or None when the native hop covers this call."""
+        curr, prev = self.curr, self.prev
+        if getattr(curr, "_strategy", "default") == "fsdp":
+            return "fsdp"
+        if str(getattr(getattr(curr, "config", None), "precision", "fp32")) != "fp32":
+            return "autocast"
+        params = list(curr.parameters())
+        meta = list(curr.meta_trainable_parameters()) if hasattr(curr, "meta_trainable_parameters") else params
+        if len(meta) != len(params) or any(a is not b for a, b in zip(meta, params)) or len(vector) != len(params):
+            return "parameters"
+        if tuple(layout.numels) != tuple(p.numel() for p in params) or any(v.shape != p.shape for v, p in zip(vector, params)):
+            return "layout"
+        from torch.nn.parallel import DistributedDataParallel as DDP  # noqa: PLC0415
+
+        if isinstance(getattr(prev, "fwd", None), DDP) or isinstance(getattr(prev, "module", None), DDP):
+            return "ddp"
+        import torch.distributed as dist  # noqa: PLC0415
+
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            return "multi-rank"
+        wn = self.weight_net
+        if wn is not None and (wn.average_over is not None or wn.slots(list(prev.trainable_parameters())) is None):
+            return "upper parameters"
+        x, y = self.batch if self.batch is not None else curr.cur_batch
+        if not (torch.is_tensor(x) and torch.is_tensor(y)):
+            return "batch"
+        tensors = params + list(vector) + [x]
+        if (self.impl or "hip") == "hip":
+            if not all(t.is_cuda and t.dtype == torch.float32 and t.device == params[0].device for t in tensors):
+                return "not fp32 cuda"
+            if not all(p.is_contiguous() for p in params) or not (1 <= x.shape[0] <= 512):
+                return "shape"
+        elif not all(t.dtype == torch.float32 for t in tensors):
+            return "not fp32"
+        return None
+
+    def _fd_guard(self, x):
+        """The structure's first-use check (see VERIFY_STRUCTURE), shared with prepare(): a problem verified for cg / neumann is verified
+        for darts / sama, and vice versa."""
+        if not (self.verify and VERIFY_STRUCTURE):
+            return
+        params = list(self.curr.parameters())
+        head = (tuple(tuple(p.shape) for p in params), int(x.shape[0]), self.ridge)
+        done = self.curr.__dict__.get("_bhg_structure_verified", set()) if hasattr(self.curr, "__dict__") else set()
+        if any(k[:3] == head for k in done):
+            return
+        self.prepare()   # raises StructureMismatchError when the closed form does not describe the training_step
+
+    def finite_difference(self, layout, vector, eps32, eps64, sync: bool, restore: bool = True):
+        """darts.py:37-67 / sama.py:29-59 for this structure (see the module docstring).  ``eps32`` / ``eps64``: the 0-dim device tensors
+        of ``be.darts_eps``.  NotImplemented (nothing touched) when the structure does not cover the call."""
+        vector = list(vector)
+        if self._fd_applies(layout, vector) is not None:
+            return NotImplemented
+        x, y = self.batch if self.batch is not None else self.curr.cur_batch
+        self._fd_guard(x)
+        two_eps = (2.0 * eps64).to(torch.float32)   # the reference divides fp32 tensors by the Python float 2*eps
+        upper = list(self.prev.trainable_parameters())
+        if (self.impl or "hip") == "hip":
+            from ._mlp_hip import fd_hop  # noqa: PLC0415
+
+            return fd_hop(self, vector, eps32, two_eps, x, y, upper, bool(sync), bool(restore))
+        # ATen twin: the three perturbations are the backend's own axpys (what the opaque path runs), CE by an ATen forward
+        from ..backend import get_backend  # noqa: PLC0415
+
+        be = get_backend()
+        weights = [p.data for p in self.curr.parameters()]
+        with torch.no_grad():
+            be.axpy_multi(layout, weights, vector, eps32, 1.0)
+            ce_p = self._torch_ce(x, y)
+            be.axpy_multi(layout, weights, vector, eps32, -2.0)
+            ce_m = self._torch_ce(x, y)
+            if restore:
+                be.axpy_multi(layout, weights, vector, eps32, 1.0)
+        return self.fd_upper_autograd(ce_p, ce_m, two_eps, upper, bool(sync))
+
+    def _torch_ce(self, x, y):
+        h = x.detach().reshape(x.shape[0], -1)
+        for l, lin in enumerate(self.layers):
+            h = F.linear(h, lin.weight.detach(), lin.bias.detach())
+            if l + 1 < len(self.layers):
+                h = torch.relu(h)
+        return F.cross_entropy(h, y.reshape(-1), reduction="none")
+
+    def fd_upper_autograd(self, ce_p, ce_m, two_eps, upper, sync: bool):
+        """The upper half of the hop through autograd over ``weight_fn`` on the two CE leaves (any weight function).  Same steps as
+        darts.py:40-67: g+ first; sync=True puts -g+/(2 eps) into .grad, then accumulates the backward of (loss- / 2 eps)."""
+        B = ce_p.shape[0]
+
+        def point(ce, scale=None):
+            ce = ce.detach().clone()
+            with torch.enable_grad():
+                s = self.weight_fn(ce)
+            # d mean(s * ce) / ds = ce / B (autograd: the mean's 1/B times ce); backward(loss / 2 eps) scales that seed first
+            seed = torch.full((), 1.0, dtype=ce.dtype, device=ce.device) if scale is None else 1.0 / scale
+            return s, ((seed / B) * ce).reshape(s.shape)
+
+        def zero_fill(gs):
+            return [torch.zeros_like(p) if g is None else g for g, p in zip(gs, upper)]
+
+        s_p, c_p = point(ce_p)
+        g_p = zero_fill(torch.autograd.grad(s_p, upper, grad_outputs=c_p, allow_unused=True))
+        if sync:
+            self.prev.set_grads(upper, [-(g / two_eps) for g in g_p])
+            s_m, c_m = point(ce_m, two_eps)
+            torch.autograd.backward(s_m, grad_tensors=c_m, inputs=upper)
+            return None
+        s_m, c_m = point(ce_m)
+        g_m = zero_fill(torch.autograd.grad(s_m, upper, grad_outputs=c_m, allow_unused=True))
+        return [(gn - gp) / two_eps for gn, gp in zip(g_m, g_p)]
 
     def mixed_vjp(self, neg_x_views, sync: bool, solve=None):
         """``solve``: token of the fused solve whose solution ``neg_x_views`` name (required when that solution was never

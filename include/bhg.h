@@ -477,6 +477,26 @@ int bhg_bn_backward_vjp(const float* x, const float* gy, const float* a, const f
                         const float* b, const float* c, int N, int C, int HW, float* dx, float* dgy, float* dgamma, void* ws,
                         size_t ws_bytes, void* stream);
 
+/* ---- finite-difference hypergradient of a ReLU-MLP inner problem (darts, SAMA; csrc/bhg_fd.hip) ------------------------------------
+ * betty/hypergradient/darts.py:29-67 (sama.py:25-59 alike) for L_in = (1/B) sum_i s_lam(CE_i.detach()) * CE_i(w) (+ a ridge without lam):
+ *   bhg_mlp_fd_forward  evaluates the network y = (... relu(x W_1^T + b_1) ...) W_L^T + b_L at w+ = w + eps v and w- = w+ - 2 eps v and
+ *                       writes per-sample ce_plus[B], ce_minus[B] (cross-entropy against labels).  params / dir: host tables of 2 L device
+ *                       pointers [W_1, b_1, W_2, b_2, ...] (W_l: [dims[l+1]][dims[l]] row-major fp32, contiguous).  The perturbed
+ *                       weights are formed in registers with the roundings of bhg_axpy_multi (a = mul * eps), never stored; the same
+ *                       pass overwrites params with the weights the reference leaves behind: (w+ - 2 eps v) + eps v when restore != 0,
+ *                       w- otherwise (darts_multitask / sama_multitask).  eps_dev: fp32 device scalar (bhg_darts_eps).  x: [B][dims[0]]
+ *                       fp32 contiguous; labels: int64 [B].  1 <= B <= 512, any widths >= 1.  ws: bhg_mlp_fd_ws_bytes bytes (0 = bad
+ *                       shape).  N-sized traffic: 12 N bytes (read W and V, write W).
+ *   bhg_mwn_fd_vjp      the closed-form meta-weight-net (see bhg_mwn_backward) at both points: g(ce) = d( sum_i (ce_i / B) s(ce_i) ) / d(w1,
+ *                       b1, w2, b2); accumulate = 0: out = (g(ce_minus) - g(ce_plus)) / two_eps (overwritten); accumulate = 1: out =
+ *                       (out + -(g(ce_plus) / two_eps)) + g(ce_minus) / two_eps — the two accumulations of darts.py:44-53 in their order.
+ *                       two_eps_dev: fp32 device scalar.  Deterministic (one workgroup, fixed summation order).                           */
+size_t bhg_mlp_fd_ws_bytes(const int* dims, int L, int B);
+int bhg_mlp_fd_forward(const float* x, const int64_t* labels, int B, const int* dims, int L, void* const* params, const void* const* dir,
+                       const float* eps_dev, int restore, float* ce_plus, float* ce_minus, void* ws, size_t ws_bytes, void* stream);
+int bhg_mwn_fd_vjp(const float* ce_plus, const float* ce_minus, int B, const float* w1, const float* b1, const float* w2, const float* b2,
+                   int H, const float* two_eps_dev, int accumulate, float* gw1, float* gb1, float* gw2, float* gb2, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
