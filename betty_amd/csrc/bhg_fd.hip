@@ -206,7 +206,7 @@ __global__ __launch_bounds__(kThreads) void k_fd_ce(const float* __restrict__ zp
   }
 }
 
-// ---- the meta-weight-net VJP at both points (k_mwn_backward's summation order, once per point) ----------------------------------
+// ---- the meta-weight-net VJP at both points (k_mwn_backward's closed form, once per point; the sums over samples in double)
 constexpr int kMwnMaxH = 2048;
 constexpr int kMwnChunk = 1024;
 
@@ -220,7 +220,7 @@ __global__ __launch_bounds__(kThreads) void k_mwn_fd(const float* __restrict__ c
                                                      const float* __restrict__ two_eps_dev, int accumulate, float* __restrict__ gw1,
                                                      float* __restrict__ gb1, float* __restrict__ gw2, float* __restrict__ gb2) {
   extern __shared__ float sp[];   // [3][H] parameters, then [2][kMwnChunk]
-  __shared__ float red[kWaves];
+  __shared__ double red[kWaves];
   float* sdz = sp + 3 * H;
   float* sce = sdz + kMwnChunk;
   for (int j = threadIdx.x; j < H; j += kThreads) { sp[j] = w1[j]; sp[H + j] = b1[j]; sp[2 * H + j] = w2[j]; }
@@ -233,10 +233,12 @@ __global__ __launch_bounds__(kThreads) void k_mwn_fd(const float* __restrict__ c
   __syncthreads();
   for (int pt = 0; pt < 2; ++pt) {
     const float* ce = pt ? cem : cep;
-    float a_w1[kPer], a_b1[kPer], a_w2[kPer];
+    // the sums over samples in double (the products of two floats are exact there), rounded to float once: g+ and g- differ by about
+    // |CE+ - CE-| / |CE| of themselves, so an fp32 running sum's rounding (growing with sqrt(B)) would reach the difference itself
+    double a_w1[kPer], a_b1[kPer], a_w2[kPer];
 #pragma unroll
-    for (int u = 0; u < kPer; ++u) a_w1[u] = a_b1[u] = a_w2[u] = 0.f;
-    float a_b2 = 0.f;
+    for (int u = 0; u < kPer; ++u) a_w1[u] = a_b1[u] = a_w2[u] = 0.0;
+    double a_b2 = 0.0;
     for (int i0 = 0; i0 < B; i0 += kMwnChunk) {
       const int n = B - i0 < kMwnChunk ? B - i0 : kMwnChunk;
 #pragma unroll
@@ -254,34 +256,39 @@ __global__ __launch_bounds__(kThreads) void k_mwn_fd(const float* __restrict__ c
         const float dz = kc * (v * (1.f - v));
         sdz[t] = dz;
         sce[t] = c;
-        a_b2 += dz;
+        a_b2 += (double)dz;
       }
       __syncthreads();
 #pragma unroll
       for (int u = 0; u < kPer; ++u) {
         const int j = threadIdx.x + kThreads * u;
         if (j < H) {
-          const float wj = sp[j], bj = sp[H + j], vj = sp[2 * H + j];
+          const float wj = sp[j], bj = sp[H + j];
           for (int t = 0; t < n; ++t) {
             const float c = sce[t], dz = sdz[t];
             const float a = fmaf(wj, c, bj);
-            const bool on = a > 0.f;
-            a_w2[u] = fmaf(dz, on ? a : 0.f, a_w2[u]);
-            const float g1 = on ? dz * vj : 0.f;
-            a_b1[u] += g1;
-            a_w1[u] = fmaf(g1, c, a_w1[u]);
+            const double d = a > 0.f ? (double)dz : 0.0;   // the sums of dz and dz c over the active samples; times w2_j below
+            a_w2[u] = fma(d, (double)a, a_w2[u]);
+            a_b1[u] += d;
+            a_w1[u] = fma(d, (double)c, a_w1[u]);
           }
         }
       }
       __syncthreads();
     }
 #pragma unroll
-    for (int u = 0; u < kPer; ++u) { g[pt][0][u] = a_w1[u]; g[pt][1][u] = a_b1[u]; g[pt][2][u] = a_w2[u]; }
+    for (int u = 0; u < kPer; ++u) {
+      const int j = threadIdx.x + kThreads * u;
+      const double vj = j < H ? (double)sp[2 * H + j] : 0.0;
+      g[pt][0][u] = (float)(vj * a_w1[u]);
+      g[pt][1][u] = (float)(vj * a_b1[u]);
+      g[pt][2][u] = (float)a_w2[u];
+    }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) a_b2 += __shfl_down(a_b2, off, 64);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = a_b2;
     __syncthreads();
-    gb[pt] = (red[0] + red[1]) + (red[2] + red[3]);
+    gb[pt] = (float)((red[0] + red[1]) + (red[2] + red[3]));
     __syncthreads();
   }
   const float te = *two_eps_dev;
