@@ -43,7 +43,7 @@ import torch
 import torch.distributed as dist
 
 from .backend import get_backend
-from .hypergradient._common import AutogradHVP, inner_gradient, mixed_vjp
+from .hypergradient._common import InnerOperator
 from .hypergradient.structured import structured_hvp_for
 
 SHARD_ALIGN = 4096   # = BHG_CHUNK_ELEMS: equal chunk counts on all ranks
@@ -108,10 +108,11 @@ _ONE_PASS = weakref.WeakKeyDictionary()
 ONE_PASS_STATS = {"solves": 0, "scalar_all_reduces": 0, "residual_all_reduces": 0}   # test / measurement hook
 
 
-def _cg_global_one_pass(vector, prev, sync, provider, be, full, K: int, alpha: float, G: int, group):
+def _cg_global_one_pass(vector, sync, op, be, full, K: int, alpha: float, G: int, group):
     """The replicated-state form described in the module docstring; returns what cg_global returns."""
     from . import _native  # noqa: PLC0415
 
+    provider = op.provider
     st = _ONE_PASS.get(full)   # (weak-keyed by the layout object: dies with it; round 3 keyed a plain dict by id())
     if st is None:
         st = _ONE_PASS[full] = _OnePassState(full)
@@ -135,12 +136,13 @@ def _cg_global_one_pass(vector, prev, sync, provider, be, full, K: int, alpha: f
                 ONE_PASS_STATS["residual_all_reduces"] += 1
             provider.cg_global_phase(full, x, r, p, k, K, _native.BHG_CG_GLOBAL_DOTS, G, st.php, alpha)
     solve = provider.cg_global_finish(full, K, alpha)
-    neg_x = full.views(x, vector)
     provider.expects_data_parallel_mean = G > 1   # a closed-form upper hop refuses to accumulate a rank-local share
-    if solve is not True:
-        out = provider.mixed_vjp(neg_x, sync, solve=solve)
-    else:
-        out = provider.mixed_vjp(neg_x, sync)
+    return _global_result(op.mixed(full.views(x, vector), sync, solve), sync, group)
+
+
+def _global_result(out, sync: bool, group):
+    """What every form returns: None under ``sync`` (the hop accumulated into ``.grad``, averaged by the DDP reducer or the declared
+    weight net), else the mean of the ranks' hops, identical on all ranks."""
     if sync:
         return None
     from .distributed import exchange_async  # noqa: PLC0415
@@ -148,7 +150,7 @@ def _cg_global_one_pass(vector, prev, sync, provider, be, full, K: int, alpha: f
     return [t.clone() for t in exchange_async(out, group).wait()]
 
 
-# ---- factor-exchange form (round 6): the fully projected solver on sample-partitioned data ------------------------------------------------
+# ---- factor-exchange form (round 6): the fully projected solver on sample-partitioned data (_fx_solve: cg_global and neumann_global) ---------
 # GLOBAL_FORM: "auto" = factor exchange whenever the structure takes it and the caller does not ask for x (else one-pass, else sharded);
 # "one_pass" / "sharded" pin the older forms (tests, bench.py --global-form).
 GLOBAL_FORM = "auto"
@@ -175,10 +177,11 @@ class _FxState:
 _FX = weakref.WeakKeyDictionary()
 
 
-def _cg_global_factor_exchange(vector, prev, sync, provider, be, full, K: int, alpha: float, G: int, g: int, group):
-    """Per iteration ONE all-gather of batch-sized factors (Rd_l, Rh_l: B x sum of widths floats per rank) and ONE of a few KB of fp64
-    partials; h_l, delta_l once per solve; the right-hand side's mean once (the only N-sized collective, as in every form).  The ranks
-    never exchange — and after iteration 0 never read — anything N-sized (csrc/mlp/fx.inc; protocol: tests/proj_global_ref.py)."""
+def _fx_solve(vector, sync, provider, be, full, K: int, alpha: float, G: int, g: int, group, neumann: bool = False):
+    """Per iteration ONE all-gather of batch-sized factors (Rd_l, Rh_l: B x sum of widths floats per rank) and, for CG, ONE of a few KB
+    of fp64 partials; h_l, delta_l once per solve; the right-hand side's mean once (the only N-sized collective, as in every form).  The
+    ranks never exchange — and after iteration 0 never read — anything N-sized (csrc/mlp/fx.inc; protocol: tests/proj_global_ref.py).
+    ``neumann``: the series instead of CG — no scalars to gather, and a closing half pass at k = K."""
     from . import _native  # noqa: PLC0415
 
     st = _FX.get(full)
@@ -191,7 +194,7 @@ def _cg_global_factor_exchange(vector, prev, sync, provider, be, full, K: int, a
     rhs = full.views(st.v, vector)
     state = provider._state
     bufs = state.fx_buffers(G)
-    if G > 1 and not bufs.get("checked"):
+    if not neumann and G > 1 and not bufs.get("checked"):
         # the Gram blocks are [Bp x G Bp] with the SAME B valid rows in every rank's slot: checked once per set of buffers
         nb = torch.tensor([float(state.B), -float(state.B)], device=st.v.device if _backend_name(group) == "nccl" else "cpu")
         dist.all_reduce(nb, op=dist.ReduceOp.MAX, group=group)
@@ -199,32 +202,34 @@ def _cg_global_factor_exchange(vector, prev, sync, provider, be, full, K: int, a
             raise ValueError(f"cg_global (factor-exchange form): every rank must hold the same batch size; got between {-int(nb[1])} and {int(nb[0])}")
         bufs["checked"] = True
     FX_STATS["solves"] += 1
-    FX_STATS["slab_bytes_per_rank"] = bufs["slab"].shape[1] * 4
-    FX_STATS["const_bytes_per_rank"] = bufs["const"].shape[1] * 4
-    FX_STATS["scal_bytes_per_rank"] = bufs["scal"].shape[1] * 8
+    if neumann:
+        FX_STATS["neumann_solves"] = FX_STATS.get("neumann_solves", 0) + 1
+        phase, finish = provider.neumann_fx_phase, provider.neumann_fx_finish
+    else:
+        FX_STATS["slab_bytes_per_rank"] = bufs["slab"].shape[1] * 4
+        FX_STATS["const_bytes_per_rank"] = bufs["const"].shape[1] * 4
+        FX_STATS["scal_bytes_per_rank"] = bufs["scal"].shape[1] * 8
+        phase, finish = provider.cg_fx_phase, provider.cg_fx_finish
     gather = G > 1 or FX_ALWAYS_GATHER
-    provider.cg_fx_phase(rhs, 0, K, _native.BHG_CG_FX_BEGIN, G, g, alpha)
+    phase(rhs, 0, K, _native.BHG_CG_FX_BEGIN, G, g, alpha)
     if gather:
         all_gather_slots(bufs["const"], g, group)
         FX_STATS["const_gathers"] += 1
     for k in range(K):
-        provider.cg_fx_phase(rhs, k, K, _native.BHG_CG_FX_CHAIN, G, g, alpha)
+        phase(rhs, k, K, _native.BHG_CG_FX_CHAIN, G, g, alpha)
         if gather:
             all_gather_slots(bufs["slab"], g, group)
             FX_STATS["slab_gathers"] += 1
-        provider.cg_fx_phase(rhs, k, K, _native.BHG_CG_FX_GRAM, G, g, alpha)
-        if gather:
+        phase(rhs, k, K, _native.BHG_CG_FX_GRAM, G, g, alpha)
+        if gather and not neumann:
             all_gather_slots(bufs["scal"], g, group)
             FX_STATS["scal_gathers"] += 1
-    provider.cg_fx_phase(rhs, K - 1, K, _native.BHG_CG_FX_END, G, g, alpha)
-    solve = provider.cg_fx_finish(full, K, alpha)
+    if neumann:
+        phase(rhs, K, K, _native.BHG_CG_FX_CHAIN, G, g, alpha)   # the closing half pass: Rz(v_K)
+    phase(rhs, K if neumann else K - 1, K, _native.BHG_CG_FX_END, G, g, alpha)
+    solve = finish(full, K, alpha)
     provider.expects_data_parallel_mean = G > 1
-    out = provider.mixed_vjp(None, sync, solve=solve)
-    if sync:
-        return None
-    from .distributed import exchange_async  # noqa: PLC0415
-
-    return [t.clone() for t in exchange_async(out, group).wait()]
+    return _global_result(provider.mixed_vjp(None, sync, solve=solve), sync, group)
 
 
 def neumann_global(vector, curr, prev, sync, group: Optional[dist.ProcessGroup] = None):
@@ -234,8 +239,6 @@ def neumann_global(vector, curr, prev, sync, group: Optional[dist.ProcessGroup] 
     (csrc/mlp/fx.inc, bhg_mlp_neumann_fx_phase).  Needs a structure that takes that form (the weighted-CE MLP on the projected plan)."""
     assert len(curr.paths) == 0, "neumann method is not supported for higher order MLO!"
     assert dist.is_available() and dist.is_initialized(), "neumann_global needs an initialised process group"
-    from . import _native  # noqa: PLC0415
-
     config = curr.config
     be = get_backend()
     vector = list(vector)
@@ -251,38 +254,7 @@ def neumann_global(vector, curr, prev, sync, group: Optional[dist.ProcessGroup] 
     if ready is None or K <= 0 or not ready(full, K, G):
         raise NotImplementedError("neumann_global: this structure / shape does not take the factor-exchange form (>= 3 layers, widths % 32 == 0, "
                                   "a head of <= 256 classes, no accumulator vector asked for)")
-    st = _FX.get(full)
-    if st is None:
-        st = _FX[full] = _FxState(full)
-    be.flatten(full, vector, st.v, 1.0 / G)
-    if G > 1:
-        dist.all_reduce(st.v, op=dist.ReduceOp.SUM, group=group)
-        FX_STATS["rhs_all_reduces"] += 1
-    rhs = full.views(st.v, vector)
-    bufs = provider._state.fx_buffers(G)
-    FX_STATS["solves"] += 1
-    FX_STATS["neumann_solves"] = FX_STATS.get("neumann_solves", 0) + 1
-    gather = G > 1 or FX_ALWAYS_GATHER
-    provider.neumann_fx_phase(rhs, 0, K, _native.BHG_CG_FX_BEGIN, G, g, alpha)
-    if gather:
-        all_gather_slots(bufs["const"], g, group)
-        FX_STATS["const_gathers"] += 1
-    for k in range(K):
-        provider.neumann_fx_phase(rhs, k, K, _native.BHG_CG_FX_CHAIN, G, g, alpha)
-        if gather:
-            all_gather_slots(bufs["slab"], g, group)
-            FX_STATS["slab_gathers"] += 1
-        provider.neumann_fx_phase(rhs, k, K, _native.BHG_CG_FX_GRAM, G, g, alpha)
-    provider.neumann_fx_phase(rhs, K, K, _native.BHG_CG_FX_CHAIN, G, g, alpha)   # the closing half pass: Rz(v_K)
-    provider.neumann_fx_phase(rhs, K, K, _native.BHG_CG_FX_END, G, g, alpha)
-    solve = provider.neumann_fx_finish(full, K, alpha)
-    provider.expects_data_parallel_mean = G > 1
-    out = provider.mixed_vjp(None, sync, solve=solve)
-    if sync:
-        return None
-    from .distributed import exchange_async  # noqa: PLC0415
-
-    return [t.clone() for t in exchange_async(out, group).wait()]
+    return _fx_solve(vector, sync, provider, be, full, K, alpha, G, g, group, neumann=True)
 
 
 def cg_global(vector, curr, prev, sync, group: Optional[dist.ProcessGroup] = None):
@@ -295,27 +267,21 @@ def cg_global(vector, curr, prev, sync, group: Optional[dist.ProcessGroup] = Non
     be = get_backend()
     vector = list(vector)
     G, g = dist.get_world_size(group), dist.get_rank(group)
-
+    K, alpha = int(config.cg_iterations), float(config.cg_alpha)
     provider = structured_hvp_for(curr, prev)
     if provider is not None:
         provider.pad_widths = False   # the ranks exchange the real network's N-sized state between phases: no padded twin here
-    if provider is None:
-        in_grad = inner_gradient(curr)
-        hvp_fn = AutogradHVP(in_grad, curr.parameters())
-    else:
-        in_grad = None
-        hvp_fn = provider.prepare()
+    op = InnerOperator(curr, prev, K, vector, provider, curr.parameters(), graphs=False)
+    hvp_fn = op.hvp(None)
     shift = float(getattr(provider, "hvp_shift", 0.0)) if provider is not None else 0.0
 
     full = be.layout(vector)
-    K = int(config.cg_iterations)
-    alpha = float(config.cg_alpha)
     fx_ready = getattr(provider, "fused_cg_fx_ready", None)
     if GLOBAL_FORM == "auto" and fx_ready is not None and K > 0 and alpha != 0.0 and fx_ready(full, K, G):
-        return _cg_global_factor_exchange(vector, prev, sync, provider, be, full, K, alpha, G, g, group)
+        return _fx_solve(vector, sync, provider, be, full, K, alpha, G, g, group)
     ready = getattr(provider, "fused_cg_global_ready", None)
     if GLOBAL_FORM != "sharded" and ready is not None and K > 0 and alpha != 0.0 and ready(full, K):
-        return _cg_global_one_pass(vector, prev, sync, provider, be, full, K, alpha, G, group)
+        return _cg_global_one_pass(vector, sync, op, be, full, K, alpha, G, group)
     key = (id(full), G)
     st = _STATES.get(key)
     if st is None:
@@ -347,12 +313,6 @@ def cg_global(vector, curr, prev, sync, group: Optional[dist.ProcessGroup] = Non
         be.scale_flat(st.x, -alpha)
 
     all_gather_flat(st.x, st.x_full, group)
-    neg_x = full.views(st.x_full, vector)
     if provider is not None:
         provider.expects_data_parallel_mean = G > 1
-    out = provider.mixed_vjp(neg_x, sync) if provider is not None else mixed_vjp(in_grad, prev, neg_x, sync)
-    if sync:
-        return None          # accumulated through backward(): the DDP reducer of prev's module averaged it
-    from .distributed import exchange_async  # noqa: PLC0415
-
-    return [t.clone() for t in exchange_async(out, group).wait()]
+    return _global_result(op.mixed(full.views(st.x_full, vector), sync), sync, group)

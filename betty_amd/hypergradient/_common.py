@@ -1,4 +1,5 @@
-"""Shared pieces of cg/neumann: inner-gradient graph, HVP providers, final mixed VJP."""
+"""Shared pieces of cg / neumann / cg_global: inner-gradient graph, HVP sources, final mixed VJP, and InnerOperator, which picks
+one source for a solve."""
 from __future__ import annotations
 
 import contextlib
@@ -477,3 +478,50 @@ def mixed_vjp(in_grad, prev, neg_x_views: List[torch.Tensor], sync: bool, retain
         torch.autograd.backward(in_grad, inputs=upper, grad_tensors=neg_x_views, retain_graph=retain_graph)
         return None
     return list(torch.autograd.grad(in_grad, upper, grad_outputs=neg_x_views, retain_graph=retain_graph))
+
+
+class InnerOperator:
+    """The inner problem's Hessian for ONE solve of cg / neumann / cg_global: ``hvp(direction_views)`` builds the Hessian-vector
+    product, ``mixed(neg_views, sync, solve)`` is the final hop to the upper parameters through the same source.  The source is, in
+    this order: a structured provider; the persistent graphs (hypergradient_graph = "persistent"); forward-over-reverse passes
+    (hypergradient_hvp = "forward_over_reverse"); a double backward through ``inner_gradient``.  An autograd-based product of one
+    solve may be replayed as a HIP graph (GraphedHVP); ``graphs=False`` (cg_global) turns off every option but the provider and the
+    plain double backward.  ``params``: what the autograd and persistent products differentiate.  Enter ``stream()`` around the whole
+    solve: a captured product needs its autograd graph built on the capturing stream."""
+
+    def __init__(self, curr, prev, K: int, vector, provider, params, graphs: bool = True):
+        self.curr, self.prev, self.provider, self.params = curr, prev, provider, params
+        self.graphed = graphs and (provider is None or getattr(provider, "hvp_is_autograd", False)) and hvp_graph_wanted(K, vector, curr)
+        self.persist = persistent_graphs_for(curr, K, vector, prev) if graphs and provider is None else None
+        self.for_hvp = graphs and provider is None and self.persist is None and forward_over_reverse_wanted(curr)
+        self.device = vector[0].device if vector else None
+        self.in_grad, self.keep_graph, self.fwd = None, False, None
+
+    def stream(self):
+        return solve_stream(self.device, self.graphed or self.persist is not None)
+
+    def hvp(self, direction_views):
+        if self.provider is not None:
+            fn = self.provider.prepare()
+        elif self.persist is not None:
+            self.in_grad, fn, self.keep_graph = self.persist.begin_step(self.curr, list(self.params), direction_views, self.prev)
+        elif self.for_hvp:   # no double-backward graph: H p by forward-over-reverse passes
+            fn = self.fwd = ForwardOverReverseHVP(self.curr, self.prev)
+        else:
+            self.in_grad = inner_gradient(self.curr)
+            fn = AutogradHVP(self.in_grad, self.params)
+        if self.graphed and self.persist is None and not self.for_hvp:
+            fn = GraphedHVP(fn)
+        return fn
+
+    def mixed(self, neg_views, sync: bool, solve=False):
+        """``solve``: what a fused solver returned; a token (not True) tells the provider WHICH solve the views name (structured.py)."""
+        if self.provider is not None:
+            if solve and solve is not True:
+                return self.provider.mixed_vjp(neg_views, sync, solve=solve)
+            return self.provider.mixed_vjp(neg_views, sync)
+        if self.for_hvp:   # the mixed second derivative is one more forward-over-reverse pass (or the fallback's double backward)
+            return self.fwd.mixed(neg_views, sync)
+        if self.keep_graph:   # the captured autograd graph of `in_grad` outlives the step (see PersistentOpaqueGraphs.saved_versions)
+            return self.persist.mixed(self.prev, neg_views, sync)
+        return mixed_vjp(self.in_grad, self.prev, neg_views, sync)

@@ -7,7 +7,8 @@ the device (the reference synchronises the host with ``.item()``, darts.py:35).
 
 An inner problem with a structure (``hypergradient_structure``, structured.py) whose provider offers ``finite_difference`` takes
 the whole hop from it — for WeightedCEMLP two native forward passes instead of two ``training_step`` calls through autograd — and
-everything else (no structure, FSDP, a collective, upper parameters the structure does not describe) runs the opaque path below.
+everything else (no structure, FSDP, a collective, upper parameters the structure does not describe) runs the opaque path.  Both
+live in ``finite_difference``, which sama shares on its preconditioned direction.
 """
 from __future__ import annotations
 
@@ -23,9 +24,6 @@ def darts(vector, curr, prev, sync):
     is_fsdp = getattr(curr, "_strategy", "default") == "fsdp"
     be = get_backend()
     vector = list(vector)
-    weights = [w.data for w in curr.meta_trainable_parameters()]
-    upper = prev.trainable_parameters()
-
     layout = be.layout(vector)
     # eps = R / (||v|| + 1e-15)   (darts.py:29-35), 0-dim device tensors
     eps32, eps64, sumsq = be.darts_eps(layout, vector, float(config.darts_alpha))
@@ -39,17 +37,26 @@ def darts(vector, curr, prev, sync):
         norm = sq.sqrt().add_(1e-15)
         eps64 = float(config.darts_alpha) / norm.to(torch.float64)
         eps32 = eps64.to(torch.float32)
+    return finite_difference(curr, prev, layout, vector, eps32, eps64, sync, restore=not config.darts_multitask, is_fsdp=is_fsdp)
+
+
+def finite_difference(curr, prev, layout, direction, eps32, eps64, sync, restore, is_fsdp=False):
+    """The central finite difference of darts and sama along ``direction`` with radius ``eps``: the structure's own
+    ``finite_difference`` when it offers one (never under FSDP), else two ``training_step`` calls through autograd at
+    ``w +- eps * direction``.  ``restore``: put the inner weights back afterwards (the multitask variants do not)."""
     if not is_fsdp:
-        provider = structured_hvp_for(curr, prev)
-        fd = getattr(provider, "finite_difference", None)
+        fd = getattr(structured_hvp_for(curr, prev), "finite_difference", None)
         if fd is not None:
-            out = fd(layout, vector, eps32, eps64, sync, restore=not config.darts_multitask)
+            out = fd(layout, direction, eps32, eps64, sync, restore=restore)
             if out is not NotImplemented:
                 return out
+    be = get_backend()
+    weights = [w.data for w in curr.meta_trainable_parameters()]
+    upper = prev.trainable_parameters()
     two_eps = (2.0 * eps64).to(torch.float32)  # the reference divides fp32 tensors by the Python float 2*eps
 
     # w <- w + eps*v   (darts.py:37-38)
-    be.axpy_multi(layout, weights, vector, eps32, 1.0)
+    be.axpy_multi(layout, weights, direction, eps32, 1.0)
     loss_p = curr.training_step_exec(curr.cur_batch)
     # is_fsdp: the gradient of a flat shard only materialises through backward into .grad (darts.py:40-42, utils.py:9-17)
     grad_p = replace_none_with_zero(grad(loss_p, upper, allow_unused=True, is_fsdp=is_fsdp), upper)
@@ -58,7 +65,7 @@ def darts(vector, curr, prev, sync):
         prev.set_grads(upper, [-(g / two_eps) for g in grad_p])
 
     # w <- w - 2*eps*v   (darts.py:49-50)
-    be.axpy_multi(layout, weights, vector, eps32, -2.0)
+    be.axpy_multi(layout, weights, direction, eps32, -2.0)
     loss_n = curr.training_step_exec(curr.cur_batch)
     if sync:
         torch.autograd.backward(loss_n / two_eps, inputs=upper)  # darts.py:52-53 (DDP hooks fire)
@@ -67,8 +74,8 @@ def darts(vector, curr, prev, sync):
         grad_n = replace_none_with_zero(grad(loss_n, upper, allow_unused=True, is_fsdp=is_fsdp), upper)  # darts.py:55-58
 
     # restore w   (darts.py:61-63)
-    if not config.darts_multitask:
-        be.axpy_multi(layout, weights, vector, eps32, 1.0)
+    if restore:
+        be.axpy_multi(layout, weights, direction, eps32, 1.0)
 
     if sync:
         return None

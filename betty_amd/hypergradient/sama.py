@@ -4,18 +4,16 @@ Behavioural twin of /root/reference betty/hypergradient/sama.py:7-61 with
 ``precondition`` from betty/hypergradient/utils.py:24-92: the direction is first multiplied by the
 derivative of the inner optimizer's update w.r.t. the gradient (identity for SGD; the closed form
 of utils.py:37-63 for Adam, built from ``exp_avg``, ``exp_avg_sq`` and the ``last_grad`` the problem
-records in ``optimizer_step``), then the same central finite difference as ``darts`` is applied with
-radius ``sama_adam_alpha``.  The preconditioner is ONE fused kernel over the four tensor lists
-(20*N bytes) writing a flat vector; norm and weight perturbations reuse the darts kernels.  A structured inner problem whose
-provider offers ``finite_difference`` takes the hop from it on the preconditioned direction, as darts does.
+records in ``optimizer_step``), then darts' central finite difference (``darts.finite_difference``: the structure's own hop
+where it offers one, else the opaque path) is applied with radius ``sama_adam_alpha``.  The preconditioner is ONE fused kernel
+over the four tensor lists (20*N bytes) writing a flat vector; the norm reuses the darts kernel.
 """
 from __future__ import annotations
 
 import torch
 
 from ..backend import get_backend
-from .structured import structured_hvp_for
-from .utils import grad, replace_none_with_zero
+from .darts import finite_difference
 
 
 def _optimizer_kind(optimizer) -> str:
@@ -83,41 +81,9 @@ def precondition(vector, problem, be):
 def sama(vector, curr, prev, sync):
     config = curr.config
     be = get_backend()
-    vector = list(vector)
-    weights = [w.data for w in curr.meta_trainable_parameters()]
-    upper = prev.trainable_parameters()
-
-    layout, pv = precondition(vector, curr, be)  # sama.py:25
+    layout, pv = precondition(list(vector), curr, be)  # sama.py:25
     eps32, eps64, _ = be.darts_eps(layout, pv, float(config.sama_adam_alpha))  # sama.py:26-27
-    provider = structured_hvp_for(curr, prev)
-    fd = getattr(provider, "finite_difference", None)
-    if fd is not None:
-        out = fd(layout, pv, eps32, eps64, sync, restore=not config.sama_multitask)
-        if out is not NotImplemented:
-            if config.sama_multitask:   # sama.py:54-55
-                curr.synchronize_params(curr.meta_trainable_parameters(), all_reduce=True)
-            return out
-    two_eps = (2.0 * eps64).to(torch.float32)
-
-    be.axpy_multi(layout, weights, pv, eps32, 1.0)  # sama.py:29-30
-    loss_p = curr.training_step_exec(curr.cur_batch)
-    grad_p = replace_none_with_zero(grad(loss_p, upper, allow_unused=True), upper)
-    if sync:
-        prev.set_grads(upper, [-(g / two_eps) for g in grad_p])  # sama.py:34-36
-
-    be.axpy_multi(layout, weights, pv, eps32, -2.0)  # sama.py:39-40
-    loss_n = curr.training_step_exec(curr.cur_batch)
-    if sync:
-        torch.autograd.backward(loss_n / two_eps, inputs=upper)  # sama.py:42-43
-        grad_n = None
-    else:
-        grad_n = replace_none_with_zero(grad(loss_n, upper, allow_unused=True), upper)
-
-    if not config.sama_multitask:  # sama.py:51-53
-        be.axpy_multi(layout, weights, pv, eps32, 1.0)
-    else:  # sama.py:54-55: average the (deliberately un-restored) weights over ranks
+    out = finite_difference(curr, prev, layout, pv, eps32, eps64, sync, restore=not config.sama_multitask)  # sama.py:29-59
+    if config.sama_multitask:  # sama.py:54-55: average the (deliberately un-restored) weights over ranks
         curr.synchronize_params(curr.meta_trainable_parameters(), all_reduce=True)
-
-    if sync:
-        return None
-    return [(gn - gp) / two_eps for gn, gp in zip(grad_n, grad_p)]  # sama.py:57-59
+    return out

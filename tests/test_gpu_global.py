@@ -239,7 +239,7 @@ def test_factor_exchange_edge_cases_one_iteration_and_no_ridge(K, ridge, one_ran
 
 
 def _emulate_fx(parts, prev, vecs, K, alpha):
-    """Drive betty_amd/global_hvp.py::_cg_global_factor_exchange for len(parts) ranks living in this process: every all-gather is a
+    """Drive betty_amd/global_hvp.py::_fx_solve for len(parts) ranks living in this process: every all-gather is a
     copy of rank r's row into the other ranks' buffers."""
     be = get_backend()
     G = len(parts)
