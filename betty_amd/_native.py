@@ -177,6 +177,7 @@ SYMBOLS = {
         [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
          c_void_p],
     ),
+    "bhg_quad_fd": (c_int, [_PP, _PP, _PP, c_int, _CH, c_int, c_void_p, c_float, c_int, c_int, c_int, c_void_p]),
     "bhg_mwn_forward": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "bhg_mwn_backward": (
         c_int,

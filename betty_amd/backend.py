@@ -293,6 +293,24 @@ class HipBackend:
             "bhg_axpy_multi",
         )
 
+    def quad_fd(self, layout, weights, direction, out, eps32: torch.Tensor, scale: float, mode: int, restore: bool,
+                accumulate: bool) -> None:
+        """The closed-form finite-difference hop of a quadratic coupling (bhg_quad_fd): ``weights`` get the three perturbations of
+        darts.py:37-63 in axpy_multi's roundings, ``out`` = scale * direction (mode 0) or -(weights * direction) (mode 1), added to
+        ``out`` when ``accumulate``.  One launch per 128 tensors; ``eps32`` is read on the device."""
+        w = self._prep(weights, layout, writable=True)
+        d = self._prep(direction, layout)
+        o = self._prep(out, layout, writable=True)
+        tw, _k1 = self._table(w)
+        td, _k2 = self._table(d)
+        to, _k3 = self._table(o)
+        _native.check(
+            self.lib.bhg_quad_fd(tw, td, to, layout.T, layout.chunks_dev.data_ptr(), layout.n_chunks, eps32.data_ptr(), float(scale),
+                                 int(mode), int(bool(restore)), int(bool(accumulate)), _stream_ptr()),
+            "bhg_quad_fd",
+        )
+
+
 
 _backend = None
 _override = None

@@ -6,7 +6,8 @@ launches (40*N bytes) instead of ``cat`` + ``norm`` + 3*T ``add_`` calls, and ``
 the device (the reference synchronises the host with ``.item()``, darts.py:35).
 
 An inner problem with a structure (``hypergradient_structure``, structured.py) whose provider offers ``finite_difference`` takes
-the whole hop from it — for WeightedCEMLP two native forward passes instead of two ``training_step`` calls through autograd — and
+the whole hop from it — for WeightedCEMLP two native forward passes instead of two ``training_step`` calls through autograd, for
+ProximalRegularized and LogisticRegressionL2 one streaming launch and no forward pass at all (the difference is exact there) — and
 everything else (no structure, FSDP, a collective, upper parameters the structure does not describe) runs the opaque path.  Both
 live in ``finite_difference``, which sama shares on its preconditioned direction.
 """

@@ -33,6 +33,7 @@ from __future__ import annotations
 
 from typing import Callable, List, Optional, Sequence
 
+import math
 import warnings
 
 import torch
@@ -945,7 +946,105 @@ class _TorchMLPState:
         return self._fx_token
 
 
-class LogisticRegressionL2:
+# ---- closed-form finite difference of a quadratic coupling (darts, sama) ------------------------------------------------------------
+def _forward_has_side_effects(module) -> bool:
+    """Would a forward pass of ``module``, in the mode it is in, change anything besides its output?  A training-mode submodule that
+    owns buffers (batch-norm running statistics, spectral-norm vectors, ...) or is a dropout layer (it consumes RNG) says yes."""
+    for m in module.modules():
+        if not m.training:
+            continue
+        if isinstance(m, torch.nn.modules.dropout._DropoutNd) or next(m.buffers(recurse=False), None) is not None:
+            return True
+    return False
+
+
+def _graph_leaves(t) -> set:
+    """ids of the leaf tensors the autograd graph of ``t`` accumulates into."""
+    if t.grad_fn is None:
+        return {id(t)} if t.requires_grad else set()
+    seen, stack, leaves = set(), [t.grad_fn], set()
+    while stack:
+        fn = stack.pop()
+        if fn is None or fn in seen:
+            continue
+        seen.add(fn)
+        var = getattr(fn, "variable", None)
+        if var is not None:
+            leaves.add(id(var))
+        stack.extend(nxt for nxt, _ in fn.next_functions)
+    return leaves
+
+
+class _QuadraticFD:
+    """What ProximalRegularized and LogisticRegressionL2 share for ``finite_difference``: the upper parameters enter the inner loss only
+    through a term quadratic in the inner weights, so the central difference of darts.py:37-67 / sama.py:29-59 is exact and has a closed
+    form (csrc/bhg_fd_quad.hip) that needs no forward pass: one launch perturbs the live weights with the roundings of the
+    three axpys and writes the result.
+
+    The forward passes it skips have side effects the reference has — the opaque hop runs the inner network twice in whatever mode it
+    is in: batch-norm running statistics move twice, dropout consumes RNG.  So the closed form applies on its own only when no
+    training-mode submodule of ``curr.module`` owns buffers or is a dropout layer (looked at once per provider); otherwise the opaque
+    path stays unless the declaration says ``closed_form_fd=True`` (the buffers are then not touched by the hop).
+    ``closed_form_fd=False`` keeps the opaque hop always.
+
+    ``impl="hip"`` (the default) is the kernel; ``impl="torch"`` must be requested explicitly and evaluates the same formulas with ATen
+    ops on weights perturbed by the backend's own three axpys — it exists for the tests of the host logic."""
+
+    impl: Optional[str] = None
+    closed_form_fd: Optional[bool] = None
+    _fd_side_effects: Optional[bool] = None
+
+    def _quad_fd_blocker(self, layout, vector):
+        """Why not: a short reason string, or None when the closed form covers this call."""
+        curr, prev = self.curr, self.prev
+        if self.closed_form_fd is False:
+            return "declined"
+        if "fsdp" in (getattr(curr, "_strategy", "default"), getattr(prev, "_strategy", "default")):
+            return "fsdp"
+        if str(getattr(getattr(curr, "config", None), "precision", "fp32")) != "fp32" or torch.is_autocast_enabled("cuda") or torch.is_autocast_enabled("cpu"):
+            return "autocast"
+        params = list(curr.parameters())
+        meta = list(curr.meta_trainable_parameters()) if hasattr(curr, "meta_trainable_parameters") else params
+        if len(meta) != len(params) or any(a is not b for a, b in zip(meta, params)) or len(vector) != len(params) or not params:
+            return "parameters"
+        if tuple(layout.numels) != tuple(p.numel() for p in params) or any(v.shape != p.shape for v, p in zip(vector, params)):
+            return "layout"
+        hip = (self.impl or "hip") == "hip"
+        for t in [p.data for p in params] + list(vector):
+            if t.dtype != torch.float32 or t.device != params[0].device or not t.is_contiguous():
+                return "not contiguous fp32"
+            if hip and not (t.is_cuda and t.data_ptr() % 16 == 0):
+                return "not an aligned cuda tensor"
+        if self.closed_form_fd is None:
+            if self._fd_side_effects is None:
+                module = getattr(curr, "module", None)
+                self._fd_side_effects = not isinstance(module, torch.nn.Module) or _forward_has_side_effects(module)
+            if self._fd_side_effects:
+                return "the forward passes have side effects"
+        return None
+
+    def _quad_fd_launch(self, layout, vector, out, eps32, scale: float, mode: int, restore: bool, accumulate: bool):
+        """weights <- the three perturbations; out (+)= scale * v (mode 0) or -(w * v) with the unperturbed w (mode 1)."""
+        from ..backend import get_backend  # noqa: PLC0415
+
+        be = get_backend()
+        weights = [p.data for p in self.curr.parameters()]
+        if (self.impl or "hip") == "hip":
+            be.quad_fd(layout, weights, vector, out, eps32, scale, mode, restore, accumulate)
+            return
+        if self.impl != "torch":
+            raise ValueError(f"unknown impl {self.impl!r}")
+        with torch.no_grad():
+            res = [float(scale) * v for v in vector] if mode == 0 else [-(w * v) for w, v in zip(weights, vector)]
+            be.axpy_multi(layout, weights, vector, eps32, 1.0)
+            be.axpy_multi(layout, weights, vector, eps32, -2.0)
+            if restore:
+                be.axpy_multi(layout, weights, vector, eps32, 1.0)
+            for o, r in zip(out, res):
+                o.add_(r) if accumulate else o.copy_(r)
+
+
+class LogisticRegressionL2(_QuadraticFD):
     """Logistic regression with a per-weight L2 penalty (the inner problem
     of examples/logistic_regression_hpo/logistic_regression_implicit.py:80-91 and
     test/test_regression.py:47-59):
@@ -956,10 +1055,15 @@ class LogisticRegressionL2:
     (csrc/bhg_logreg.hip); the mixed derivative of g.x w.r.t. the lam TENSOR is w * x, pushed into
     ``prev``'s parameters through ``lam``'s own graph.  ``lam_fn()`` must return lam (shape [d]) as
     a function of ``prev``'s parameters.
+
+    darts / sama: the penalty is the only place lam enters, dL/dlam_j = w_j^2 / 2, so the central difference along v is
+    (w-^2 - w+^2) / (4 eps) = -w_j v_j exactly (``finite_difference``, see _QuadraticFD for ``impl`` / ``closed_form_fd``).
     """
 
-    def __init__(self, curr, prev, weight: torch.nn.Parameter, lam_fn: Callable, batch=None):
+    def __init__(self, curr, prev, weight: torch.nn.Parameter, lam_fn: Callable, batch=None, impl: Optional[str] = None,
+                 closed_form_fd: Optional[bool] = None):
         self.curr, self.prev, self.weight, self.lam_fn, self.batch = curr, prev, weight, lam_fn, batch
+        self.impl, self.closed_form_fd = impl, closed_form_fd
         params = list(curr.parameters())
         if len(params) != 1 or params[0] is not weight:
             raise ValueError("LogisticRegressionL2: curr.parameters() must be [weight]")
@@ -1004,8 +1108,30 @@ class LogisticRegressionL2:
             return None
         return list(torch.autograd.grad(self.lam, upper, grad_outputs=coeff))
 
+    def finite_difference(self, layout, vector, eps32, eps64, sync: bool, restore: bool = True):
+        """darts.py:37-67 / sama.py:29-59 in closed form: the kernel leaves the perturbed-and-restored weights and the ``d``-sized
+        cotangent -(w * v) of the lam tensor, ``lam``'s own graph carries it to ``prev``'s parameters as in ``mixed_vjp``.  None of
+        ``prepare()``'s state is needed.  NotImplemented (nothing touched) when the closed form does not cover the call."""
+        vector = list(vector)
+        if self._quad_fd_blocker(layout, vector) is not None:
+            return NotImplemented
+        upper = list(self.prev.trainable_parameters())
+        lam = self.lam_fn()   # keeps the graph to prev's parameters
+        if not torch.is_tensor(lam) or lam.dtype != torch.float32 or lam.numel() != self.weight.numel() or lam.device != self.weight.device:
+            return NotImplemented
+        leaves = _graph_leaves(lam)
+        if not upper or any(id(p) not in leaves for p in upper):
+            return NotImplemented   # an upper parameter lam does not depend on: the opaque path knows what the reference does with it
+        coeff = torch.empty_like(self.weight.data)
+        self._quad_fd_launch(layout, vector, [coeff], eps32, 0.0, 1, bool(restore), False)
+        coeff = coeff.reshape(lam.shape)
+        if sync:
+            torch.autograd.backward(lam, grad_tensors=coeff, inputs=upper)
+            return None
+        return list(torch.autograd.grad(lam, upper, grad_outputs=coeff))
 
-class ProximalRegularized:
+
+class ProximalRegularized(_QuadraticFD):
     """Inner loss = data loss + reg * ||w - theta||^2 with theta the UPPER problem's parameters, one per
     inner parameter — implicit MAML (examples/implicit_maml/main.py:87-92,122-129).
 
@@ -1015,14 +1141,19 @@ class ProximalRegularized:
         already holds in registers — the T elementwise double-backward kernels of the prox term disappear;
       * the final hop is closed form: hypergradient = +2*reg*x, i.e. ``-2*reg * (-alpha*x)`` applied to the
         flat result — no second-order autograd call at all.
+      * darts / sama need no forward pass either: dL/dtheta = -2*reg*(w - theta) is affine in w, so the central difference along v is
+        +2*reg*v exactly, whatever w, theta, the batch and the network are (``finite_difference``, see _QuadraticFD for ``impl`` /
+        ``closed_form_fd``).
     ``data_loss(batch)`` must return the loss WITHOUT the proximal term; ``prev.trainable_parameters()`` must
     align one-to-one with ``curr.parameters()``.
     """
 
     hvp_is_autograd = True   # the HVP callback is an opaque double backward: cg/neumann may replay it as a HIP graph
 
-    def __init__(self, curr, prev, data_loss: Callable, reg: float, batch=None):
+    def __init__(self, curr, prev, data_loss: Callable, reg: float, batch=None, impl: Optional[str] = None,
+                 closed_form_fd: Optional[bool] = None):
         self.curr, self.prev, self.data_loss, self.reg, self.batch = curr, prev, data_loss, float(reg), batch
+        self.impl, self.closed_form_fd = impl, closed_form_fd
         self.hvp_shift = 2.0 * self.reg
         inner, upper = list(curr.parameters()), list(prev.trainable_parameters())
         if len(inner) != len(upper) or any(a.shape != b.shape for a, b in zip(inner, upper)):
@@ -1052,3 +1183,34 @@ class ProximalRegularized:
             return None
         return grads
 
+    def finite_difference(self, layout, vector, eps32, eps64, sync: bool, restore: bool = True):
+        """darts.py:37-67 / sama.py:29-59 in closed form: one launch leaves the perturbed-and-restored weights and 2*reg*v, aligned
+        with ``prev.trainable_parameters()``.  sync=True accumulates THROUGH autograd like ``mixed_vjp`` (a DistributedDataParallel
+        reducer on the upper module fires); without such a wrapper and with ``.grad`` already allocated the kernel adds straight into
+        ``.grad``.  NotImplemented (nothing touched) when the closed form does not cover the call."""
+        vector = list(vector)
+        if self._quad_fd_blocker(layout, vector) is not None:
+            return NotImplemented
+        upper = list(self.prev.trainable_parameters())
+        if len(upper) != len(vector) or any(
+                p.shape != v.shape or p.dtype != torch.float32 or p.device != v.device for p, v in zip(upper, vector)):
+            return NotImplemented   # upper parameters that do not align with the inner ones
+        if not math.isfinite(self.reg):
+            return NotImplemented
+        scale = 2.0 * self.reg
+        if sync:
+            from torch.nn.parallel import DistributedDataParallel as DDP  # noqa: PLC0415
+
+            ddp = any(isinstance(getattr(self.prev, name, None), DDP) for name in ("fwd", "module"))
+            grads = [p.grad for p in upper]
+            hip = (self.impl or "hip") == "hip"
+            if not ddp and all(g is not None and g.dtype == torch.float32 and g.shape == p.shape and g.device == p.device
+                               and g.is_contiguous() and (not hip or g.data_ptr() % 16 == 0) for g, p in zip(grads, upper)):
+                self._quad_fd_launch(layout, vector, grads, eps32, scale, 0, bool(restore), True)
+                return None
+        out = layout.views(torch.empty(layout.flat_size, dtype=torch.float32, device=vector[0].device), vector)
+        self._quad_fd_launch(layout, vector, out, eps32, scale, 0, bool(restore), False)
+        if sync:
+            torch.autograd.backward(upper, grad_tensors=out)
+            return None
+        return out

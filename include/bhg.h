@@ -497,6 +497,22 @@ int bhg_mlp_fd_forward(const float* x, const int64_t* labels, int B, const int* 
 int bhg_mwn_fd_vjp(const float* ce_plus, const float* ce_minus, int B, const float* w1, const float* b1, const float* w2, const float* b2,
                    int H, const float* two_eps_dev, int accumulate, float* gw1, float* gb1, float* gw2, float* gb2, void* stream);
 
+/* ---- closed-form finite-difference hop of a quadratic coupling (darts, SAMA; csrc/bhg_fd_quad.hip) -----------------------------------
+ * betty/hypergradient/darts.py:37-67 (sama.py:25-59 alike) for an inner loss whose upper parameters enter only through a term quadratic
+ * in the inner weights, where the central difference (g(w-) - g(w+)) / (2 eps) is exact and needs no forward pass:
+ *   mode 0 (proximal, L = data(w) + reg ||w - theta||^2):            out_t = scale * dir_t, scale = 2 reg;
+ *   mode 1 (logistic + L2, L = mean BCE + 1/2 sum_j lam_j w_j^2):    out_t = -(w_t * dir_t), w the weights BEFORE the perturbation
+ *                                                                     (the cotangent of the lam tensor; scale is not read).
+ * accumulate != 0: out_t = out_t + that (one more fp32 add) instead of overwriting.  The same pass leaves in w what the reference's
+ * three in-place axpys leave, with the roundings of bhg_axpy_multi (a1 = 1 * eps, a2 = -2 * eps as fp32 products):
+ * ((w + a1 v) + a2 v) + a1 v when restore != 0, (w + a1 v) + a2 v otherwise (darts_multitask / sama_multitask).
+ * w / dir / out: host tables of T >= 1 device pointers to fp32 tensors of the layout's sizes (chunks_dev / n_chunks of bhg_layout_build);
+ * 4-byte alignment suffices (16-byte aligned tensors, or three tensors sharing one misalignment, take 16-byte accesses).  out must not
+ * alias w or dir.  eps_dev: fp32 device scalar (bhg_darts_eps), read on the device: no host synchronisation.  scale must be finite.
+ * Any T (128 tensors per launch, pointers in the kernel arguments: no workspace).  16 N bytes of traffic (20 N when accumulating). */
+int bhg_quad_fd(void* const* w, const void* const* dir, void* const* out, int T, const bhg_chunk* chunks_dev, int n_chunks,
+                const float* eps_dev, float scale, int mode, int restore, int accumulate, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
