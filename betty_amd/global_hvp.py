@@ -88,6 +88,12 @@ class _State:
 _STATES = {}
 
 
+def _declare(provider, name: str, value) -> None:
+    """Set what WeightedCEMLP declares (``pad_widths``, ``expects_data_parallel_mean``); a foreign provider grows no attribute."""
+    if hasattr(provider, name):
+        setattr(provider, name, value)
+
+
 def all_reduce_mean(flat: torch.Tensor, world: int, group) -> None:
     """flat <- mean over ranks, bit-identical on every rank.  RCCL: one all-reduce with the AVG operator; gloo (CPU tests)
     has no AVG."""
@@ -136,7 +142,7 @@ def _cg_global_one_pass(vector, sync, op, be, full, K: int, alpha: float, G: int
                 ONE_PASS_STATS["residual_all_reduces"] += 1
             provider.cg_global_phase(full, x, r, p, k, K, _native.BHG_CG_GLOBAL_DOTS, G, st.php, alpha)
     solve = provider.cg_global_finish(full, K, alpha)
-    provider.expects_data_parallel_mean = G > 1   # a closed-form upper hop refuses to accumulate a rank-local share
+    _declare(provider, "expects_data_parallel_mean", G > 1)   # a closed-form upper hop refuses to accumulate a rank-local share
     return _global_result(op.mixed(full.views(x, vector), sync, solve), sync, group)
 
 
@@ -192,11 +198,11 @@ def _fx_solve(vector, sync, provider, be, full, K: int, alpha: float, G: int, g:
         dist.all_reduce(st.v, op=dist.ReduceOp.SUM, group=group)
         FX_STATS["rhs_all_reduces"] += 1
     rhs = full.views(st.v, vector)
-    state = provider._state
-    bufs = state.fx_buffers(G)
+    bufs = provider.fx_buffers(G)
     if not neumann and G > 1 and not bufs.get("checked"):
         # the Gram blocks are [Bp x G Bp] with the SAME B valid rows in every rank's slot: checked once per set of buffers
-        nb = torch.tensor([float(state.B), -float(state.B)], device=st.v.device if _backend_name(group) == "nccl" else "cpu")
+        B = provider.local_batch_size()
+        nb = torch.tensor([float(B), -float(B)], device=st.v.device if _backend_name(group) == "nccl" else "cpu")
         dist.all_reduce(nb, op=dist.ReduceOp.MAX, group=group)
         if float(nb[0]) != -float(nb[1]):
             raise ValueError(f"cg_global (factor-exchange form): every rank must hold the same batch size; got between {-int(nb[1])} and {int(nb[0])}")
@@ -228,7 +234,7 @@ def _fx_solve(vector, sync, provider, be, full, K: int, alpha: float, G: int, g:
         phase(rhs, K, K, _native.BHG_CG_FX_CHAIN, G, g, alpha)   # the closing half pass: Rz(v_K)
     phase(rhs, K if neumann else K - 1, K, _native.BHG_CG_FX_END, G, g, alpha)
     solve = finish(full, K, alpha)
-    provider.expects_data_parallel_mean = G > 1
+    _declare(provider, "expects_data_parallel_mean", G > 1)
     return _global_result(provider.mixed_vjp(None, sync, solve=solve), sync, group)
 
 
@@ -246,7 +252,7 @@ def neumann_global(vector, curr, prev, sync, group: Optional[dist.ProcessGroup] 
     provider = structured_hvp_for(curr, prev)
     if provider is None:
         raise NotImplementedError("neumann_global needs a declared structure (hypergradient_structure): its form exchanges batch-sized factors")
-    provider.pad_widths = False
+    _declare(provider, "pad_widths", False)
     provider.prepare()
     full = be.layout(vector)
     K, alpha = int(config.neumann_iterations), float(config.neumann_alpha)
@@ -269,11 +275,9 @@ def cg_global(vector, curr, prev, sync, group: Optional[dist.ProcessGroup] = Non
     G, g = dist.get_world_size(group), dist.get_rank(group)
     K, alpha = int(config.cg_iterations), float(config.cg_alpha)
     provider = structured_hvp_for(curr, prev)
-    if provider is not None:
-        provider.pad_widths = False   # the ranks exchange the real network's N-sized state between phases: no padded twin here
+    _declare(provider, "pad_widths", False)   # the ranks exchange the real network's N-sized state between phases: no padded twin here
     op = InnerOperator(curr, prev, K, vector, provider, curr.parameters(), graphs=False)
     hvp_fn = op.hvp(None)
-    shift = float(getattr(provider, "hvp_shift", 0.0)) if provider is not None else 0.0
 
     full = be.layout(vector)
     fx_ready = getattr(provider, "fused_cg_fx_ready", None)
@@ -301,7 +305,7 @@ def cg_global(vector, curr, prev, sync, group: Optional[dist.ProcessGroup] = Non
         be.flatten(full, hvp, st.h_full, 1.0 / G)
         reduce_scatter_sum(st.h_full, st.hs, g, group)               # slice of the MEAN Hessian-vector product
         last = k == K - 1 and alpha != 0.0
-        args = (sl, [st.hs], st.x, st.r, st.p, alpha, k, (-alpha if last else 0.0), shift)
+        args = (sl, [st.hs], st.x, st.r, st.p, alpha, k, (-alpha if last else 0.0), op.shift)
         be.cg_phase(0, *args)                                        # partials of (cg_alpha*Hp).p over the slice
         dist.all_reduce(be.cg_partials(sl, 0, k), op=dist.ReduceOp.SUM, group=group)
         be.cg_phase(1, *args)                                        # alpha; r' = r - alpha*Hp; partials of r'.r'
@@ -313,6 +317,5 @@ def cg_global(vector, curr, prev, sync, group: Optional[dist.ProcessGroup] = Non
         be.scale_flat(st.x, -alpha)
 
     all_gather_flat(st.x, st.x_full, group)
-    if provider is not None:
-        provider.expects_data_parallel_mean = G > 1
+    _declare(provider, "expects_data_parallel_mean", G > 1)
     return _global_result(op.mixed(full.views(st.x_full, vector), sync), sync, group)

@@ -300,6 +300,8 @@ class PersistentOpaqueGraphs:
         self.sig = None
         self.state = 0          # 0: nothing seen | 1: warmed up eagerly | 2: captured | -1: gave up
         self.g1 = self.g2 = None
+        self.g3 = self.g3_key = self.g3_out = None   # the captured final hop (mixed); g3_dead: its capture failed once, eager for good
+        self.g3_dead = False
         self.static_leaves = self.spec = None
         self.in_grad = self.out = None
         self.tracked, self.versions = [], []
@@ -340,6 +342,7 @@ class PersistentOpaqueGraphs:
         if sig != self.sig or self.state == 0:      # new signature: an eager step first (warm-up on the capture stream)
             self.sig, self.state = sig, 1
             self.g1 = self.g2 = self.in_grad = self.out = None
+            self.g3 = self.g3_key = self.g3_out = None
             in_grad = inner_gradient(curr)
             return in_grad, AutogradHVP(in_grad, params), False
         if self.state == 1:                         # second step of this signature: capture G1 and G2
@@ -401,51 +404,56 @@ class PersistentOpaqueGraphs:
 
         return self.in_grad, hvp, True
 
-
-def _persistent_mixed(self, prev, neg_x_views, sync: bool):
-    """Final hop of a step whose `in_grad` lives in the persistent graph G1: the mixed second derivative (cg.py:58-68) as a THIRD
-    captured graph, G3 = autograd.grad(in_grad, upper, grad_outputs=views) — captured on the first replayed step, replayed
-    afterwards.  `sync=True` accumulates the replayed result into `.grad` (the upper modules are not DDP-wrapped here —
-    persistent graphs are not taken under DDP — so there is no reducer hook a `backward` would have to fire)."""
-    upper = list(prev.trainable_parameters())
-    key = (tuple((id(p), p.data_ptr()) for p in upper), GraphedHVP._key(neg_x_views))
-    if getattr(self, "g3_dead", False):   # a capture of this hop failed once: stay eager for good (no retry, no warning per step)
-        return mixed_vjp(self.in_grad, prev, neg_x_views, sync, retain_graph=True)
-    if getattr(self, "g3", None) is None or self.g3_key != key:
-        with self.saved_versions():
-            try:
-                g3 = torch.cuda.CUDAGraph()
-                g3.capture_begin(capture_error_mode="thread_local")
+    def mixed(self, prev, neg_x_views, sync: bool):
+        """Final hop of a step whose `in_grad` lives in the persistent graph G1: the mixed second derivative (cg.py:58-68) as a THIRD
+        captured graph, G3 = autograd.grad(in_grad, upper, grad_outputs=views) — captured on the first replayed step, replayed
+        afterwards.  `sync=True` accumulates the replayed result into `.grad` (the upper modules are not DDP-wrapped here —
+        persistent graphs are not taken under DDP — so there is no reducer hook a `backward` would have to fire)."""
+        upper = list(prev.trainable_parameters())
+        key = (tuple((id(p), p.data_ptr()) for p in upper), GraphedHVP._key(neg_x_views))
+        if self.g3_dead:   # a capture of this hop failed once: stay eager for good (no retry, no warning per step)
+            return mixed_vjp(self.in_grad, prev, neg_x_views, sync, retain_graph=True)
+        if self.g3 is None or self.g3_key != key:
+            with self.saved_versions():
                 try:
-                    outs = torch.autograd.grad(self.in_grad, upper, grad_outputs=neg_x_views, retain_graph=True)
-                finally:
-                    g3.capture_end()
-                self.g3, self.g3_key, self.g3_out = g3, key, tuple(outs)
-                GRAPH_STATS["captures"] += 1
-            except Exception as exc:   # stay eager for this hop
-                self.g3 = None
-                self.g3_dead = True
-                warnings.warn(f"betty_amd: hipGraph capture of the mixed second derivative failed ({type(exc).__name__}: {exc}); "
-                              "this hop stays eager for the rest of the run", RuntimeWarning)
-                torch.cuda.synchronize(neg_x_views[0].device)
-                return mixed_vjp(self.in_grad, prev, neg_x_views, sync, retain_graph=True)
-    self.g3.replay()
-    GRAPH_STATS["replays"] += 1
-    grads = [g.clone() for g in self.g3_out]
-    if sync:
-        for p, g in zip(upper, grads):
-            p.grad = g if p.grad is None else p.grad + g
-        return None
-    return grads
-
-
-PersistentOpaqueGraphs.mixed = _persistent_mixed
+                    g3 = torch.cuda.CUDAGraph()
+                    g3.capture_begin(capture_error_mode="thread_local")
+                    try:
+                        outs = torch.autograd.grad(self.in_grad, upper, grad_outputs=neg_x_views, retain_graph=True)
+                    finally:
+                        g3.capture_end()
+                    self.g3, self.g3_key, self.g3_out = g3, key, tuple(outs)
+                    GRAPH_STATS["captures"] += 1
+                except Exception as exc:   # stay eager for this hop
+                    self.g3 = None
+                    self.g3_dead = True
+                    warnings.warn(f"betty_amd: hipGraph capture of the mixed second derivative failed ({type(exc).__name__}: {exc}); "
+                                  "this hop stays eager for the rest of the run", RuntimeWarning)
+                    torch.cuda.synchronize(neg_x_views[0].device)
+                    return mixed_vjp(self.in_grad, prev, neg_x_views, sync, retain_graph=True)
+        self.g3.replay()
+        GRAPH_STATS["replays"] += 1
+        grads = [g.clone() for g in self.g3_out]
+        if sync:
+            for p, g in zip(upper, grads):
+                p.grad = g if p.grad is None else p.grad + g
+            return None
+        return grads
 
 
 def _uses_ddp(problem) -> bool:
     from torch.nn.parallel import DistributedDataParallel as DDP
 
     return any(isinstance(getattr(problem, name, None), DDP) for name in ("fwd", "module"))
+
+
+def precision_of(problem) -> str:
+    """``problem.config.precision`` ("fp32" when the problem has no config or the config no precision)."""
+    return str(getattr(getattr(problem, "config", None), "precision", "fp32"))
+
+
+def is_fsdp(problem) -> bool:
+    return getattr(problem, "_strategy", "default") == "fsdp"
 
 
 def persistent_graphs_for(curr, K: int, tensors, prev=None):
@@ -495,6 +503,8 @@ class InnerOperator:
         self.persist = persistent_graphs_for(curr, K, vector, prev) if graphs and provider is None else None
         self.for_hvp = graphs and provider is None and self.persist is None and forward_over_reverse_wanted(curr)
         self.device = vector[0].device if vector else None
+        # a structured provider may leave a diagonal part of the Hessian (ridge) to the recurrence kernel
+        self.shift = float(getattr(provider, "hvp_shift", 0.0))
         self.in_grad, self.keep_graph, self.fwd = None, False, None
 
     def stream(self):

@@ -74,6 +74,31 @@ def _stream() -> int:
     return int(torch.cuda.current_stream().cuda_stream)
 
 
+def _native_weight_net(lib, wn, upper, device):
+    """May the closed-form meta-weight-net (csrc/bhg_mwn.hip) stand in for ``weight_fn``?  None (autograd keeps the job), or
+    ((w1, b1, w2, b2) detached, their indices in ``upper``) when it is declared and describes exactly ``upper`` on ``device``."""
+    if wn is None:
+        return None
+    slots = wn.slots(list(upper))
+    ts = [t.detach() for t in wn.tensors()]
+    if (slots is None or ts[0].shape[0] > int(lib.bhg_mwn_max_hidden())
+            or not all(t.is_cuda and t.device == device and t.dtype == torch.float32 and t.is_contiguous() for t in ts)):
+        return None
+    return ts, slots
+
+
+def _flat_upper(upper, slots, device):
+    """ONE fresh flat fp32 buffer for an M-sized result (fresh: ``.grad`` may keep its views), its views in ``upper``'s order, and
+    the four of (w1, b1, w2, b2) picked by ``slots``."""
+    sizes = [p.numel() for p in upper]
+    flat = torch.empty(sum(sizes), dtype=torch.float32, device=device)
+    views, off = [], 0
+    for p, n in zip(upper, sizes):
+        views.append(flat[off: off + n].view(p.shape))
+        off += n
+    return flat, views, [views[i] for i in slots]
+
+
 class FusedSolve:
     """Token of ONE run of a fused solver: returned by ``cg_solve`` / ``neumann_solve``, handed back to ``mixed_coeff``
     so the state knows — by object identity, not by comparing addresses of views — that the direction it is asked about
@@ -157,15 +182,11 @@ class HipMLPState:
             raise _native.NativeLibraryError("bhg_mlp_supports_native_prepare refused this network (layer count / batch padding): there is no ATen path")
         # sample weights: the declared closed form of the meta-weight-net (one launch, writes s / B where bhg_mlp_backward reads it),
         # else the upper problem's module through autograd (keeps the graph to prev's parameters)
-        self.native_upper, self.sample_weight = False, None
-        wn = getattr(spec, "weight_net", None)
-        if wn is not None and buf.native_prepare:
-            self._upper_slots = wn.slots(list(spec.prev.trainable_parameters()))
-            ts = [t.detach() for t in wn.tensors()]
-            self.native_upper = (self._upper_slots is not None and ts[0].shape[0] <= int(lib.bhg_mwn_max_hidden()) and
-                                 all(t.is_cuda and t.device == x.device and t.dtype == torch.float32 and t.is_contiguous() for t in ts))
+        native = _native_weight_net(lib, spec.weight_net, spec.prev.trainable_parameters(), x.device)
+        self.native_upper, self.sample_weight = native is not None, None
         if self.native_upper:
-            self._wn = ts
+            self._wn, self._upper_slots = native
+            ts = self._wn
             _native.check(lib.bhg_mwn_forward(buf.ce.data_ptr(), B, ts[0].data_ptr(), ts[1].data_ptr(), ts[2].data_ptr(), ts[3].data_ptr(),
                                               ts[0].shape[0], None, buf.sd.data_ptr(), _stream()), "bhg_mwn_forward")
         else:
@@ -197,13 +218,7 @@ class HipMLPState:
             return (out, None) if with_flat else out
         ts, B = self._wn, self.B
         H = ts[0].shape[0]
-        sizes = [p.numel() for p in upper]
-        flat = torch.empty(sum(sizes), dtype=torch.float32, device=ts[0].device)   # fresh: .grad may keep its views
-        views, off = [], 0
-        for p, n in zip(upper, sizes):
-            views.append(flat[off: off + n].view(p.shape))
-            off += n
-        g = [views[i] for i in self._upper_slots]   # (w1, b1, w2, b2) -> their slots in `upper`
+        flat, views, g = _flat_upper(upper, self._upper_slots, ts[0].device)
         coeff = coeff if (coeff.dtype == torch.float32 and coeff.is_contiguous()) else coeff.to(torch.float32).contiguous()
         _native.check(
             self.lib.bhg_mwn_backward(self.buf.ce.data_ptr(), coeff.data_ptr(), B, ts[0].data_ptr(), ts[1].data_ptr(), ts[2].data_ptr(),
@@ -342,35 +357,28 @@ class HipMLPState:
             }
         return got
 
-    def cg_fx_phase(self, rhs, k: int, K: int, phase: int, world: int, rank: int, cg_alpha: float, shift: float) -> None:
-        """One phase of the factor-exchange solver on THIS rank's share of the batch (include/bhg.h); the caller all-gathers the buffer
-        the phase wrote its slot of.  ``rhs``: the replicated right-hand side's tensors (read in CHAIN of iteration 0)."""
+    def _fx_phase(self, symbol: str, rhs, k: int, K: int, phase: int, world: int, rank: int, alpha: float, shift: float) -> None:
         b = self.fx_buffers(world)
         fws = self._fused_ws(self.buf.h[0].device)
         if phase == _native.BHG_CG_FX_BEGIN:
             self._solve = None   # the workspace an earlier solve's token refers to is being rewritten
             self._fx_rhs = _native.ptr_array([t.data_ptr() for t in rhs]) + (list(rhs),)
         _native.check(
-            self.lib.bhg_mlp_cg_fx_phase(ctypes.byref(self.desc), self._fx_rhs[0], int(k), int(K), int(phase), int(world), int(rank),
-                                         b["const"].data_ptr(), b["slab"].data_ptr(), b["scal"].data_ptr(), float(cg_alpha), float(shift),
-                                         fws.data_ptr(), fws.numel(), b["xws"].data_ptr(), b["xws"].numel(), _stream()),
-            "bhg_mlp_cg_fx_phase",
+            getattr(self.lib, symbol)(ctypes.byref(self.desc), self._fx_rhs[0], int(k), int(K), int(phase), int(world), int(rank),
+                                      b["const"].data_ptr(), b["slab"].data_ptr(), b["scal"].data_ptr(), float(alpha), float(shift),
+                                      fws.data_ptr(), fws.numel(), b["xws"].data_ptr(), b["xws"].numel(), _stream()),
+            symbol,
         )
+
+    def cg_fx_phase(self, rhs, k: int, K: int, phase: int, world: int, rank: int, cg_alpha: float, shift: float) -> None:
+        """One phase of the factor-exchange solver on THIS rank's share of the batch (include/bhg.h); the caller all-gathers the buffer
+        the phase wrote its slot of.  ``rhs``: the replicated right-hand side's tensors (read in CHAIN of iteration 0)."""
+        self._fx_phase("bhg_mlp_cg_fx_phase", rhs, k, K, phase, world, rank, cg_alpha, shift)
 
     def neumann_fx_phase(self, rhs, k: int, K: int, phase: int, world: int, rank: int, alpha: float, shift: float) -> None:
         """The same for the Neumann series (bhg_mlp_neumann_fx_phase): CHAIN for k = 0 .. K (the last one is the closing half pass),
         GRAM for k = 0 .. K-1, END at k = K; the only buffer the caller gathers per iteration is the factor slab."""
-        b = self.fx_buffers(world)
-        fws = self._fused_ws(self.buf.h[0].device)
-        if phase == _native.BHG_CG_FX_BEGIN:
-            self._solve = None
-            self._fx_rhs = _native.ptr_array([t.data_ptr() for t in rhs]) + (list(rhs),)
-        _native.check(
-            self.lib.bhg_mlp_neumann_fx_phase(ctypes.byref(self.desc), self._fx_rhs[0], int(k), int(K), int(phase), int(world), int(rank),
-                                              b["const"].data_ptr(), b["slab"].data_ptr(), b["scal"].data_ptr(), float(alpha), float(shift),
-                                              fws.data_ptr(), fws.numel(), b["xws"].data_ptr(), b["xws"].numel(), _stream()),
-            "bhg_mlp_neumann_fx_phase",
-        )
+        self._fx_phase("bhg_mlp_neumann_fx_phase", rhs, k, K, phase, world, rank, alpha, shift)
 
     def neumann_fx_finish(self, layout, K: int, alpha: float) -> FusedSolve:
         """Token of the factor-exchange Neumann solve: sum_{k <= K} Rz(v_k) sits where bhg_mlp_neumann_mixed_coeff reads it (projected)."""
@@ -404,38 +412,36 @@ class HipMLPState:
         ``solve`` = the token of the fused solve whose solution is meant: the coefficient then comes from the Rz the solver
         accumulated (no R-forward pass; the only way to ask about a solution that was never materialised).  Without a token
         ``dir_views`` are read like any direction — one R-forward, whatever memory they live in."""
-        buf, B = self.buf, self.B
-        if solve is not None:
-            if solve is not getattr(self, "_solve", None):
-                raise RuntimeError("stale fused-solve token: another solve or a hand-driven HVP has reused this state's workspace")
-            if solve.kind == "neumann" and not solve.materialised:
-                lay, v_last = solve.layout, solve.v_last
-                if v_last is None:   # the factor-exchange solve: v_K never existed N-sized; its Rz is already in the sum (projected = 1)
-                    tab, _keep = None, None
-                else:
-                    views = [v_last[s: s + n] for s, n in zip(lay.starts, lay.numels)]
-                    tab, _keep = self._dir_table(views)
-                _native.check(
-                    self.lib.bhg_mlp_neumann_mixed_coeff(ctypes.byref(self.desc), tab, buf.labels.data_ptr(), buf.coeff.data_ptr(),
-                                                         solve.alpha, solve.K, int(getattr(solve, "projected", 0)), buf.fws.data_ptr(),
-                                                         buf.fws.numel(), _stream()),
-                    "bhg_mlp_neumann_mixed_coeff",
-                )
-                return buf.coeff[:B] if self.native_upper else buf.coeff[:B].clone()   # (closed-form upper VJP: consumed on this stream at once)
-            if solve.kind == "cg":
-                _native.check(
-                    self.lib.bhg_mlp_cg_mixed_coeff(ctypes.byref(self.desc), buf.labels.data_ptr(), buf.coeff.data_ptr(), solve.alpha,
-                                                    buf.fws.data_ptr(), buf.fws.numel(), _stream()),
-                    "bhg_mlp_cg_mixed_coeff",
-                )
-                return buf.coeff[:B] if self.native_upper else buf.coeff[:B].clone()   # (closed-form upper VJP: consumed on this stream at once)
-            # a materialised Neumann accumulator: read it like any direction (below)
-        tab, _keep = self._dir_table(dir_views)
-        _native.check(
-            self.lib.bhg_mlp_mixed_coeff(ctypes.byref(self.desc), tab, buf.labels.data_ptr(), buf.coeff.data_ptr(), _stream()),
-            "bhg_mlp_mixed_coeff",
-        )
-        return buf.coeff[:B] if self.native_upper else buf.coeff[:B].clone()   # (closed-form upper VJP: consumed on this stream at once)
+        buf = self.buf
+        if solve is not None and solve is not getattr(self, "_solve", None):
+            raise RuntimeError("stale fused-solve token: another solve or a hand-driven HVP has reused this state's workspace")
+        if solve is not None and solve.kind == "neumann" and not solve.materialised:
+            lay, v_last = solve.layout, solve.v_last
+            if v_last is None:   # the factor-exchange solve: v_K never existed N-sized; its Rz is already in the sum (projected = 1)
+                tab, _keep = None, None
+            else:
+                views = [v_last[s: s + n] for s, n in zip(lay.starts, lay.numels)]
+                tab, _keep = self._dir_table(views)
+            _native.check(
+                self.lib.bhg_mlp_neumann_mixed_coeff(ctypes.byref(self.desc), tab, buf.labels.data_ptr(), buf.coeff.data_ptr(),
+                                                     solve.alpha, solve.K, int(getattr(solve, "projected", 0)), buf.fws.data_ptr(),
+                                                     buf.fws.numel(), _stream()),
+                "bhg_mlp_neumann_mixed_coeff",
+            )
+        elif solve is not None and solve.kind == "cg":
+            _native.check(
+                self.lib.bhg_mlp_cg_mixed_coeff(ctypes.byref(self.desc), buf.labels.data_ptr(), buf.coeff.data_ptr(), solve.alpha,
+                                                buf.fws.data_ptr(), buf.fws.numel(), _stream()),
+                "bhg_mlp_cg_mixed_coeff",
+            )
+        else:   # no token, or a materialised Neumann accumulator: read like any direction
+            tab, _keep = self._dir_table(dir_views)
+            _native.check(
+                self.lib.bhg_mlp_mixed_coeff(ctypes.byref(self.desc), tab, buf.labels.data_ptr(), buf.coeff.data_ptr(), _stream()),
+                "bhg_mlp_mixed_coeff",
+            )
+        coeff = buf.coeff[:self.B]
+        return coeff if self.native_upper else coeff.clone()   # (closed-form upper VJP: consumed on this stream at once)
 
 
 # ---- networks whose widths are not multiples of 32: the zero-padded twin (round 6) ---------------------------------------------------
@@ -624,7 +630,7 @@ def make_state(spec, x, y):
     Ws = [lin.weight for lin in spec.layers]
     dims = tuple([Ws[0].shape[1]] + [W.shape[0] for W in Ws])
     # (L >= 3 and a head the head kernels take — <= 256 classes: the conditions under which the twin takes the fused form at all)
-    if (PAD_WIDTHS_TO_32 and getattr(spec, "pad_widths", True) and len(Ws) >= 3 and dims[-1] <= 256 and padded_dims(dims) != dims and x.is_cuda):
+    if (PAD_WIDTHS_TO_32 and spec.pad_widths and len(Ws) >= 3 and dims[-1] <= 256 and padded_dims(dims) != dims and x.is_cuda):
         return PaddedHipMLPState(spec, x, y)
     return HipMLPState(spec, x, y)
 
@@ -661,13 +667,10 @@ def fd_hop(spec, vector, eps32, two_eps, x, y, upper, sync: bool, restore: bool)
     dtab, _dk = _native.ptr_array([d.data_ptr() for d in dirs])
     _native.check(lib.bhg_mlp_fd_forward(xs.data_ptr(), ys.data_ptr(), B, dims_c, L, ptab, dtab, eps.data_ptr(), int(restore),
                                          ce[0].data_ptr(), ce[1].data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "bhg_mlp_fd_forward")
-    wn = spec.weight_net
-    ts = [t.detach() for t in wn.tensors()] if wn is not None else None
-    slots = wn.slots(upper) if wn is not None else None
-    native_upper = (ts is not None and slots is not None and ts[0].shape[0] <= int(lib.bhg_mwn_max_hidden())
-                    and all(t.is_cuda and t.device == dev and t.dtype == torch.float32 and t.is_contiguous() for t in ts))
-    if not native_upper:
+    native = _native_weight_net(lib, spec.weight_net, upper, dev)
+    if native is None:
         return spec.fd_upper_autograd(ce[0], ce[1], two_eps, upper, sync)
+    ts, slots = native
     if sync:
         for p in upper:   # darts.py:44-53 accumulate into .grad (in place, as autograd's accumulation does)
             if p.grad is None:
@@ -675,13 +678,9 @@ def fd_hop(spec, vector, eps32, two_eps, x, y, upper, sync: bool, restore: bool)
             elif not (p.grad.dtype == torch.float32 and p.grad.is_contiguous()):
                 p.grad = p.grad.to(torch.float32).contiguous()
         outs = [p.grad for p in upper]
+        g = [outs[i] for i in slots]
     else:
-        flat = torch.empty(sum(p.numel() for p in upper), dtype=torch.float32, device=dev)
-        outs, off = [], 0
-        for p in upper:
-            outs.append(flat[off: off + p.numel()].view(p.shape))
-            off += p.numel()
-    g = [outs[i] for i in slots]   # (w1, b1, w2, b2) -> their slots in `upper`
+        _flat, outs, g = _flat_upper(upper, slots, dev)
     _native.check(lib.bhg_mwn_fd_vjp(ce[0].data_ptr(), ce[1].data_ptr(), B, ts[0].data_ptr(), ts[1].data_ptr(), ts[2].data_ptr(),
                                      ts[3].data_ptr(), ts[0].shape[0], two_eps.data_ptr(), int(sync), g[0].data_ptr(), g[1].data_ptr(),
                                      g[2].data_ptr(), g[3].data_ptr(), _stream()), "bhg_mwn_fd_vjp")

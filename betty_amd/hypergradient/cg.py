@@ -55,8 +55,6 @@ def _cg(vector, op, K, sync):
     rhs = be.cg_init(layout, vector, None if skip_x else x, r, p, keep_mask=keep_mask) if keep_mask is not None else \
         be.cg_init(layout, vector, None if skip_x else x, r, p)
 
-    # a structured provider may leave a diagonal part of the Hessian (ridge) to the recurrence kernel
-    shift = float(getattr(provider, "hvp_shift", 0.0)) if provider is not None else 0.0
     if fused is not None and alpha != 0.0:
         solve = fused(layout, x, r, p, K, alpha, rhs=rhs) if keep_mask is not None else fused(layout, x, r, p, K, alpha)
         if keep_mask is not None and not solve:   # (r / p were initialised for THAT solver only: the generic loop below must not run on them)
@@ -68,7 +66,7 @@ def _cg(vector, op, K, sync):
             hvp = hvp_fn(p_views)  # H p   (cg.py:39-41)
             # cg.py:42-55 in one launch group; the last one also applies cg.py:56 and the negation
             last = k == K - 1 and alpha != 0.0
-            be.cg_step(layout, hvp, x, r, p, alpha, k, out_scale=(-alpha if last else 0.0), hvp_shift=shift)
+            be.cg_step(layout, hvp, x, r, p, alpha, k, out_scale=(-alpha if last else 0.0), hvp_shift=op.shift)
         if K > 0 and alpha == 0.0:
             be.scale_flat(x, -alpha)  # out_scale = 0 means "no final scaling" to the kernel: do cg.py:56 explicitly
         be.after_cg(layout)

@@ -16,19 +16,20 @@ from __future__ import annotations
 import torch
 
 from ..backend import get_backend
+from ._common import is_fsdp
 from .structured import structured_hvp_for
 from .utils import grad, replace_none_with_zero
 
 
 def darts(vector, curr, prev, sync):
     config = curr.config
-    is_fsdp = getattr(curr, "_strategy", "default") == "fsdp"
+    fsdp = is_fsdp(curr)
     be = get_backend()
     vector = list(vector)
     layout = be.layout(vector)
     # eps = R / (||v|| + 1e-15)   (darts.py:29-35), 0-dim device tensors
     eps32, eps64, sumsq = be.darts_eps(layout, vector, float(config.darts_alpha))
-    if is_fsdp:
+    if fsdp:
         # darts.py:31-34: every rank holds a shard of v; eps uses the norm of the whole vector.  Same fp32
         # steps as the reference: local norm -> square -> all-reduce(SUM) -> sqrt -> + 1e-15 -> R / .
         import torch.distributed as dist
@@ -38,7 +39,7 @@ def darts(vector, curr, prev, sync):
         norm = sq.sqrt().add_(1e-15)
         eps64 = float(config.darts_alpha) / norm.to(torch.float64)
         eps32 = eps64.to(torch.float32)
-    return finite_difference(curr, prev, layout, vector, eps32, eps64, sync, restore=not config.darts_multitask, is_fsdp=is_fsdp)
+    return finite_difference(curr, prev, layout, vector, eps32, eps64, sync, restore=not config.darts_multitask, is_fsdp=fsdp)
 
 
 def finite_difference(curr, prev, layout, direction, eps32, eps64, sync, restore, is_fsdp=False):

@@ -37,13 +37,12 @@ def _neumann(vector, op, K, sync):
     skip_p = bool(fused is not None and alpha != 0.0 and skips is not None and skips(layout, K))
     be.neumann_init(layout, vector, v, None if skip_p else p)  # p = v   (neumann.py:60)
 
-    shift = float(getattr(provider, "hvp_shift", 0.0)) if provider is not None else 0.0
     solve = fused(layout, v, p, K, alpha) if (fused is not None and alpha != 0.0) else False
     if not solve:   # (else the provider's own kernels ran all K iterations: v ping-pongs with a third flat vector of the layout)
         for k in range(K):
             hvp = hvp_fn(v_views)  # neumann.py:62
             last = k == K - 1 and alpha != 0.0
-            be.neumann_step(layout, hvp, v, p, alpha, out_scale=(-alpha if last else 0.0), hvp_shift=shift)  # 63-64 (+66)
+            be.neumann_step(layout, hvp, v, p, alpha, out_scale=(-alpha if last else 0.0), hvp_shift=op.shift)  # 63-64 (+66)
         if K == 0 or alpha == 0.0:
             be.scale_flat(p, -alpha)  # alpha * p (with p = v when K == 0)   (neumann.py:66)
 
