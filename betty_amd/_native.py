@@ -102,6 +102,15 @@ SYMBOLS = {
     "bhg_scale_flat": (c_int, [c_void_p, c_int64, c_float, c_void_p]),
     "bhg_darts_eps": (c_int, [_PP, c_int, _CH, c_int, c_double, c_void_p, c_void_p, c_void_p, c_void_p]),
     "bhg_axpy_multi": (c_int, [_PP, _PP, c_int, _CH, c_int, c_void_p, c_float, c_void_p, c_void_p]),
+    "bhg_fd_perturb": (c_int, [_PP, c_void_p, _PP, c_int, _CH, c_int, c_void_p, c_float, c_void_p, c_void_p]),
+    "bhg_cg_step_fd": (
+        c_int,
+        [_PP, _PP, c_void_p, c_int, _CH, c_int, c_void_p, c_void_p, c_void_p, c_float, c_int, c_float, c_float, c_int, c_void_p, c_void_p],
+    ),
+    "bhg_neumann_step_fd": (
+        c_int,
+        [_PP, _PP, c_void_p, c_int, _CH, c_int, c_void_p, c_void_p, c_float, c_float, c_float, c_void_p, c_void_p],
+    ),
     "bhg_sama_adam_precondition": (
         c_int,
         [_PP, _PP, _PP, _PP, c_int, _CH, c_int, c_void_p, c_double, c_double, c_double, c_double, c_void_p, c_void_p],

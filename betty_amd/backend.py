@@ -169,6 +169,46 @@ class HipBackend:
             "bhg_cg_step",
         )
 
+    # -- cg / neumann on a gradient pair (hypergradient/_common.py: FiniteDifferenceHVP) ---------------------------------
+    def _pair_tables(self, layout, grad_plus, grad_minus):
+        gp, gm = self._prep(grad_plus, layout), self._prep(grad_minus, layout)   # kept alive until the launch is enqueued
+        tp, kp = self._table(gp)
+        tm, km = self._table(gm)
+        return tp, tm, (gp, gm, kp, km)
+
+    def fd_perturb(self, layout, weights, w0: torch.Tensor, direction, eps32: torch.Tensor, sign: float) -> None:
+        """weights_t <- w0_t + (sign * eps) * direction_t, ``w0`` a flat snapshot of the weights (flatten), eps on the device."""
+        w = self._prep(weights, layout, writable=True)
+        d = self._prep(direction, layout)
+        tw, _k1 = self._table(w)
+        td, _k2 = self._table(d)
+        _native.check(
+            self.lib.bhg_fd_perturb(tw, w0.data_ptr(), td, layout.T, layout.chunks_dev.data_ptr(), layout.n_chunks,
+                                    eps32.data_ptr(), float(sign), layout.workspace.data_ptr(), _stream_ptr()),
+            "bhg_fd_perturb",
+        )
+
+    def cg_step_fd(self, layout, grad_plus, grad_minus, two_eps: torch.Tensor, x, r, p, cg_alpha: float, it: int,
+                   out_scale: float = 0.0, variant: Optional[int] = None, hvp_shift: float = 0.0) -> None:
+        """cg_step with H p = (grad_plus - grad_minus) / two_eps formed in registers (two_eps: 0-dim fp32 device tensor)."""
+        tp, tm, _keep = self._pair_tables(layout, grad_plus, grad_minus)
+        _native.check(
+            self.lib.bhg_cg_step_fd(tp, tm, two_eps.data_ptr(), layout.T, layout.chunks_dev.data_ptr(), layout.n_chunks,
+                                    x.data_ptr(), r.data_ptr(), p.data_ptr(), cg_alpha, it, out_scale, hvp_shift,
+                                    self._pick_variant(layout, it, variant), layout.workspace.data_ptr(), _stream_ptr()),
+            "bhg_cg_step_fd",
+        )
+
+    def neumann_step_fd(self, layout, grad_plus, grad_minus, two_eps: torch.Tensor, v, p, alpha: float, out_scale: float = 0.0,
+                        hvp_shift: float = 0.0) -> None:
+        tp, tm, _keep = self._pair_tables(layout, grad_plus, grad_minus)
+        _native.check(
+            self.lib.bhg_neumann_step_fd(tp, tm, two_eps.data_ptr(), layout.T, layout.chunks_dev.data_ptr(), layout.n_chunks,
+                                         v.data_ptr(), p.data_ptr(), alpha, out_scale, hvp_shift, layout.workspace.data_ptr(),
+                                         _stream_ptr()),
+            "bhg_neumann_step_fd",
+        )
+
     # -- phased CG for sharded state (betty_amd/global_hvp.py) ----------------------------------------------------
     def cg_phase(self, phase: int, layout, hvp, x, r, p, cg_alpha: float, it: int, out_scale: float = 0.0,
                  hvp_shift: float = 0.0) -> None:

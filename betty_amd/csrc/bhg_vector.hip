@@ -95,6 +95,37 @@ __global__ __launch_bounds__(kThreads) void k_scale_flat(float* __restrict__ fla
   }
 }
 
+// ---- where a recurrence kernel takes its H p element from -------------------------------------------
+// HvpTensors: the product, materialised by its producer (autograd, an analytic provider), one tensor list.
+// HvpGradPair: a central finite difference of first-order gradients (hypergradient/_common.py: FiniteDifferenceHVP) —
+// two tensor lists g+ = grad L(w + eps p), g- = grad L(w - eps p) and the device scalar 2*eps; every element forms
+//   hp = (g+ - g-) / two_eps     (subtraction rounded first, true fp32 division: what ATen's `(gp - gm) / two_eps` gives)
+// in registers and goes on as the kernel does with a loaded element, so no N-sized H p is ever written: one more N-sized
+// read per pass over the product instead of 12*N bytes for materialising the difference first.  Lanes past a chunk's
+// end see (0 - 0) / two_eps = 0, like a zero-filled load.
+struct HvpTensors {
+  PtrTab tab;
+  struct Ctx {};
+  __device__ __forceinline__ Ctx ctx() const { return Ctx{}; }
+  __device__ __forceinline__ float4 load(const Ctx&, const bhg_chunk& ck, int e) const {
+    return ld4(tab_ptr(tab, ck.tensor) + ck.src_off, e, ck.len);
+  }
+};
+struct HvpGradPair {
+  PtrTab gp, gm;
+  const float* two_eps;
+  struct Ctx { float d; };
+  __device__ __forceinline__ Ctx ctx() const { return Ctx{*two_eps}; }
+  __device__ __forceinline__ float4 load(const Ctx& cx, const bhg_chunk& ck, int e) const {
+    const float4 a = ld4(tab_ptr(gp, ck.tensor) + ck.src_off, e, ck.len);
+    const float4 b = ld4(tab_ptr(gm, ck.tensor) + ck.src_off, e, ck.len);
+    float4 o;
+    o.x = __fdiv_rn(sub_rn(a.x, b.x), cx.d); o.y = __fdiv_rn(sub_rn(a.y, b.y), cx.d);
+    o.z = __fdiv_rn(sub_rn(a.z, b.z), cx.d); o.w = __fdiv_rn(sub_rn(a.w, b.w), cx.d);
+    return o;
+  }
+};
+
 // ---- Neumann ----------------------------------------------------------------------------------
 // neumann.py:60  p = v (the reference aliases; we keep two flat buffers)
 __global__ __launch_bounds__(kThreads) void k_neumann_init(PtrTab tab, const bhg_chunk* __restrict__ chunks,
@@ -117,20 +148,21 @@ __global__ __launch_bounds__(kThreads) void k_neumann_init(PtrTab tab, const bhg
 // neumann.py:62-64 (+66 and the negation of 45/54 folded in when out_scale != 0):
 //   v <- v - alpha*Hv ; p <- p + v ; [p <- out_scale * p]
 // 20*N algorithmic bytes: read Hv, v, p; write v, p.
-__global__ __launch_bounds__(kThreads) void k_neumann_step(PtrTab tab, const bhg_chunk* __restrict__ chunks,
+template <typename Src>
+__global__ __launch_bounds__(kThreads) void k_neumann_step(Src src, const bhg_chunk* __restrict__ chunks,
                                                            int n_chunks, float* __restrict__ v,
                                                            float* __restrict__ p, float alpha,
                                                            float out_scale, float shift) {
+  const typename Src::Ctx cx = src.ctx();
   for (int c = blockIdx.x; c < n_chunks; c += gridDim.x) {
     const bhg_chunk ck = chunks[c];
-    const float* hsrc = tab_ptr(tab, ck.tensor) + ck.src_off;
     float* vv = v + ck.flat_off;
     float* pp = p + ck.flat_off;
     float4 h[kVecPerThread], a[kVecPerThread], b[kVecPerThread];
 #pragma unroll
     for (int i = 0; i < kVecPerThread; ++i) {
       const int e = 4 * (threadIdx.x + kThreads * i);
-      h[i] = ld4(hsrc, e, ck.len);
+      h[i] = src.load(cx, ck, e);
       a[i] = ld4(vv, e, ck.len);
       b[i] = ld4(pp, e, ck.len);
     }
@@ -197,19 +229,20 @@ __global__ __launch_bounds__(kThreads) void k_cg_init(PtrTab tab, const bhg_chun
 }
 
 // K1: den = (cg_alpha*Hp).p   (cg.py:42,44,46) — reads Hp, p: 8*N bytes.
-__global__ __launch_bounds__(kThreads) void k_cg_dot(PtrTab tab, const bhg_chunk* __restrict__ chunks,
+template <typename Src>
+__global__ __launch_bounds__(kThreads) void k_cg_dot(Src src, const bhg_chunk* __restrict__ chunks,
                                                      int n_chunks, const float* __restrict__ p,
                                                      float cg_alpha, float shift, double* __restrict__ partP) {
   __shared__ double red[kWaves];
+  const typename Src::Ctx cx = src.ctx();
   double acc = 0.0;
   for (int c = blockIdx.x; c < n_chunks; c += gridDim.x) {
     const bhg_chunk ck = chunks[c];
-    const float* hsrc = tab_ptr(tab, ck.tensor) + ck.src_off;
     float4 h[kVecPerThread], q[kVecPerThread];
 #pragma unroll
     for (int i = 0; i < kVecPerThread; ++i) {
       const int e = 4 * (threadIdx.x + kThreads * i);
-      h[i] = ld4(hsrc, e, ck.len);
+      h[i] = src.load(cx, ck, e);
       q[i] = ld4(p + ck.flat_off, e, ck.len);
     }
 #pragma unroll
@@ -228,7 +261,8 @@ __global__ __launch_bounds__(kThreads) void k_cg_dot(PtrTab tab, const bhg_chunk
 
 // K2: a = rr/den ; r' = r - a*Hp (cg.py:47,50) ; partial r'.r' (cg.py:51-52)
 // reads Hp, r; writes r: 12*N bytes.  x += a*p is deferred to K3, which reads p anyway.
-__global__ __launch_bounds__(kThreads) void k_cg_resid(PtrTab tab, const bhg_chunk* __restrict__ chunks,
+template <typename Src>
+__global__ __launch_bounds__(kThreads) void k_cg_resid(Src src, const bhg_chunk* __restrict__ chunks,
                                                        int n_chunks, float* __restrict__ r,
                                                        const float* __restrict__ p, float shift,
                                                        const double* __restrict__ partP,
@@ -239,16 +273,16 @@ __global__ __launch_bounds__(kThreads) void k_cg_resid(PtrTab tab, const bhg_chu
   const double rr = sum_partials(partR_old, (int)scal[S_NPART0 + (iter & 1)], red);
   const double den = sum_partials(partP, n_part, red);
   const float alpha = (float)rr / (float)den;  // fp32 divide of fp32 dots, as torch does
+  const typename Src::Ctx cx = src.ctx();
   double acc = 0.0;
   for (int c = blockIdx.x; c < n_chunks; c += gridDim.x) {
     const bhg_chunk ck = chunks[c];
-    const float* hsrc = tab_ptr(tab, ck.tensor) + ck.src_off;
     float* rrp = r + ck.flat_off;
     float4 h[kVecPerThread], a[kVecPerThread];
 #pragma unroll
     for (int i = 0; i < kVecPerThread; ++i) {
       const int e = 4 * (threadIdx.x + kThreads * i);
-      h[i] = ld4(hsrc, e, ck.len);
+      h[i] = src.load(cx, ck, e);
       a[i] = ld4(rrp, e, ck.len);
       if (shift != 0.f) {  // (12+4)*N bytes in this case: the direction is re-read for the diagonal term
         const float4 q = ld4(p + ck.flat_off, e, ck.len);
@@ -443,9 +477,9 @@ __device__ __forceinline__ void resident_stream(float* __restrict__ vec, const b
 // HYBRID (round 2): chunks beyond the NSLOT x G resident ones are STREAMED inside the same launch — they take part in
 // the same two grid-wide dots and are re-read like in the 3-kernel form (40 bytes per element instead of 28), so the
 // kernel has no size limit any more: N = 20 M costs 28*15.7 M + 40*4.3 M bytes in ONE launch instead of 40*20 M in three.
-template <int NSLOT, int NLDS, bool HYBRID>
+template <int NSLOT, int NLDS, bool HYBRID, typename Src = HvpTensors>
 __global__ __launch_bounds__(kResThreads, 2) void k_cg_resident(
-    PtrTab tab, const bhg_chunk* __restrict__ chunks, int n_chunks, float* __restrict__ x,
+    Src src, const bhg_chunk* __restrict__ chunks, int n_chunks, float* __restrict__ x,
     float* __restrict__ r, float* __restrict__ p, float cg_alpha, int iter, float out_scale, float shift,
     const double* __restrict__ partR_old, double* __restrict__ partR_new,
     double* __restrict__ partP, unsigned* __restrict__ barrier_words, double* __restrict__ scal,
@@ -453,6 +487,7 @@ __global__ __launch_bounds__(kResThreads, 2) void k_cg_resident(
   __shared__ double red[kResWaves];
   extern __shared__ __attribute__((aligned(16))) float4 sq[];   // NLDS x kResV x 512 float4: parked direction slices
   const int G = gridDim.x;
+  const typename Src::Ctx cx = src.ctx();
 
   float4 h[NSLOT][kResV], q[NSLOT - NLDS][kResV];
   // direction slice of slot i: LDS for the first NLDS slots (conflict-free: consecutive lanes, consecutive 16 B), else
@@ -470,11 +505,10 @@ __global__ __launch_bounds__(kResThreads, 2) void k_cg_resident(
     }
     if (c < n_chunks) {
       const bhg_chunk ck = chunks[c];
-      const float* hs = tab_ptr(tab, ck.tensor) + ck.src_off;
 #pragma unroll
       for (int j = 0; j < kResV; ++j) {
         const int e = 4 * (threadIdx.x + kResThreads * j);
-        h[i][j] = ld4(hs, e, ck.len);
+        h[i][j] = src.load(cx, ck, e);
         qv[j] = ld4(p + ck.flat_off, e, ck.len);
       }
     }
@@ -510,12 +544,11 @@ __global__ __launch_bounds__(kResThreads, 2) void k_cg_resident(
   if (HYBRID) {   // streamed chunks: (cg_alpha*Hp).p without keeping anything
     for (int c = NSLOT * G + blockIdx.x; c < n_chunks; c += G) {
       const bhg_chunk ck = chunks[c];
-      const float* hs = tab_ptr(tab, ck.tensor) + ck.src_off;
       float4 hv[kResV], qv[kResV];
 #pragma unroll
       for (int j = 0; j < kResV; ++j) {
         const int e = 4 * (threadIdx.x + kResThreads * j);
-        hv[j] = ld4(hs, e, ck.len);
+        hv[j] = src.load(cx, ck, e);
         qv[j] = ld4(p + ck.flat_off, e, ck.len);
       }
 #pragma unroll
@@ -547,12 +580,11 @@ __global__ __launch_bounds__(kResThreads, 2) void k_cg_resident(
   if (HYBRID) {   // streamed chunks: r' = r - a*Hp with Hp (and p for the shift) read again
     for (int c = NSLOT * G + blockIdx.x; c < n_chunks; c += G) {
       const bhg_chunk ck = chunks[c];
-      const float* hs = tab_ptr(tab, ck.tensor) + ck.src_off;
       float4 hv[kResV], rv[kResV];
 #pragma unroll
       for (int j = 0; j < kResV; ++j) {
         const int e = 4 * (threadIdx.x + kResThreads * j);
-        hv[j] = ld4(hs, e, ck.len);
+        hv[j] = src.load(cx, ck, e);
         rv[j] = ld4(r + ck.flat_off, e, ck.len);
         if (shift != 0.f) {
           const float4 qq = ld4(p + ck.flat_off, e, ck.len);
@@ -895,20 +927,54 @@ int bhg_neumann_init(const void* const* vec, int T, const bhg_chunk* chunks_dev,
   return BHG_OK;
 }
 
+extern "C++" {
+template <typename Src>
+static int neumann_step_launch(const Src& src, const bhg_chunk* chunks_dev, int n_chunks, float* v, float* p, float alpha,
+                               float out_scale, float hvp_shift, hipStream_t st) {
+  hipEvent_t ea, eb;
+  const bool timed = span_begin(BHG_TIMING_NEUMANN_STEP, &ea, &eb);
+  hipExtLaunchKernelGGL(k_neumann_step<Src>, dim3(grid_for(n_chunks)), dim3(kThreads), 0, st, timed ? ea : nullptr,
+                        timed ? eb : nullptr, 0, src, chunks_dev, n_chunks, v, p, alpha, out_scale, hvp_shift);
+  BHG_HIP_CHECK(hipGetLastError());
+  return BHG_OK;
+}
+}  // extern "C++"
+
 int bhg_neumann_step(const void* const* hvp, int T, const bhg_chunk* chunks_dev, int n_chunks, float* v,
                      float* p, float alpha, float out_scale, float hvp_shift, void* ws, void* stream) {
   BHG_COMMON_CHECKS(hvp);
   if (n_chunks == 0) return BHG_OK;
   BHG_REQUIRE(v && p, "state vector is NULL");
   hipStream_t st = static_cast<hipStream_t>(stream);
-  PtrTab tab;
-  if (int rc = make_table(&tab, hvp, T, ws, 0, st)) return rc;
-  hipEvent_t ea, eb;
-  const bool timed = span_begin(BHG_TIMING_NEUMANN_STEP, &ea, &eb);
-  hipExtLaunchKernelGGL(k_neumann_step, dim3(grid_for(n_chunks)), dim3(kThreads), 0, st, timed ? ea : nullptr,
-                        timed ? eb : nullptr, 0, tab, chunks_dev, n_chunks, v, p, alpha, out_scale, hvp_shift);
-  BHG_HIP_CHECK(hipGetLastError());
+  HvpTensors src;
+  if (int rc = make_table(&src.tab, hvp, T, ws, 0, st)) return rc;
+  return neumann_step_launch(src, chunks_dev, n_chunks, v, p, alpha, out_scale, hvp_shift, st);
+}
+
+// The pair form's arguments, checked before any HIP call; the two tables go to workspace slots 0 and 1 when T > kInlineT.
+#define BHG_PAIR_CHECKS()                                                                          \
+  BHG_REQUIRE((grad_plus != nullptr && grad_minus != nullptr) || T == 0, "gradient table is NULL"); \
+  BHG_REQUIRE(T >= 0 && n_chunks >= 0, "negative size");                                           \
+  BHG_REQUIRE(chunks_dev != nullptr || n_chunks == 0, "chunk table is NULL")
+static int make_pair(HvpGradPair* src, const void* const* grad_plus, const void* const* grad_minus, int T, const float* two_eps_dev,
+                     void* ws, hipStream_t st) {
+  if (int rc = make_table(&src->gp, grad_plus, T, ws, 0, st)) return rc;
+  if (int rc = make_table(&src->gm, grad_minus, T, ws, 1, st)) return rc;
+  src->two_eps = two_eps_dev;
   return BHG_OK;
+}
+
+int bhg_neumann_step_fd(const void* const* grad_plus, const void* const* grad_minus, const float* two_eps_dev, int T,
+                        const bhg_chunk* chunks_dev, int n_chunks, float* v, float* p, float alpha, float out_scale,
+                        float hvp_shift, void* ws, void* stream) {
+  BHG_PAIR_CHECKS();
+  if (n_chunks == 0) return BHG_OK;
+  BHG_REQUIRE(two_eps_dev, "two_eps is NULL");
+  BHG_REQUIRE(v && p, "state vector is NULL");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  HvpGradPair src;
+  if (int rc = make_pair(&src, grad_plus, grad_minus, T, two_eps_dev, ws, st)) return rc;
+  return neumann_step_launch(src, chunks_dev, n_chunks, v, p, alpha, out_scale, hvp_shift, st);
 }
 
 int bhg_cg_init(const void* const* vec, int T, const bhg_chunk* chunks_dev, int n_chunks, float* x, float* r,
@@ -956,6 +1022,10 @@ static bool resident_lds_instances_ok() {
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess;
     ok = ok && hipFuncSetAttribute(reinterpret_cast<const void*>(k_cg_resident<kResHyb, kResLds, true>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess;
+    ok = ok && hipFuncSetAttribute(reinterpret_cast<const void*>(k_cg_resident<kResMaxLds, kResLds, false, HvpGradPair>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess;
+    ok = ok && hipFuncSetAttribute(reinterpret_cast<const void*>(k_cg_resident<kResHyb, kResLds, true, HvpGradPair>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess;
     if (!ok) (void)hipGetLastError();
     per_device[dev] = ok ? 1 : -1;
   }
@@ -987,7 +1057,7 @@ int bhg_cg_resident_ok(void) {
     if (hipMemset(ws, 0, bytes) != hipSuccess) break;
     char* w = static_cast<char*>(ws);
     double* partR = reinterpret_cast<double*>(w + kWsPartR);
-    PtrTab tab;
+    HvpTensors tab;
     memset(&tab, 0, sizeof(tab));
     hipLaunchKernelGGL((k_cg_resident<kResMax, 0, false>), dim3(G), dim3(kResThreads), 0, nullptr, tab, (const bhg_chunk*)nullptr, 0,
                        (float*)nullptr, (float*)nullptr, (float*)nullptr, 1.0f, 0, 0.0f, 0.0f,
@@ -1021,24 +1091,11 @@ const unsigned* bhg_cg_timeout_flag_dev(const void* ws) {
   return reinterpret_cast<const unsigned*>(static_cast<const char*>(ws) + kWsBarrier) + 1;
 }
 
-int bhg_cg_step(const void* const* hvp, int T, const bhg_chunk* chunks_dev, int n_chunks, float* x, float* r,
-                float* p, float cg_alpha, int iter, float out_scale, float hvp_shift, int variant, void* ws,
-                void* stream) {
-  BHG_COMMON_CHECKS(hvp);
-  BHG_REQUIRE(ws, "workspace is NULL");
-  BHG_REQUIRE(iter >= 0, "negative iteration index");
-  if (n_chunks == 0) return BHG_OK;
-  BHG_REQUIRE(x && r && p, "state vector is NULL");
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const int cap = bhg_cg_resident_capacity_chunks();
-  if (variant == BHG_CG_AUTO) variant = bhg_cg_resident_usable(n_chunks) ? BHG_CG_RESIDENT : BHG_CG_STREAM;
-  if (variant == BHG_CG_RESIDENT && n_chunks > cap) {
-    set_error("bhg_cg_step: %d chunks exceed the resident capacity of %d", n_chunks, cap);
-    return BHG_ERR_CAPACITY;
-  }
-  BHG_REQUIRE(variant == BHG_CG_STREAM || variant == BHG_CG_RESIDENT, "unknown variant");
-  PtrTab tab;
-  if (int rc = make_table(&tab, hvp, T, ws, 0, st)) return rc;
+// One CG iteration on the product source `src` (validated by the caller): the streaming trio or one resident launch.
+extern "C++" {
+template <typename Src>
+static int cg_step_launch(const Src& src, const bhg_chunk* chunks_dev, int n_chunks, float* x, float* r, float* p, float cg_alpha,
+                          int iter, float out_scale, float hvp_shift, int variant, void* ws, hipStream_t st) {
   char* w = static_cast<char*>(ws);
   double* scal = reinterpret_cast<double*>(w + kWsScal);
   double* partP = reinterpret_cast<double*>(w + kWsPartP);
@@ -1055,9 +1112,9 @@ int bhg_cg_step(const void* const* hvp, int T, const bhg_chunk* chunks_dev, int 
   if (variant == BHG_CG_STREAM) {
     // start event rides on the first kernel, stop event on the last: the span is the whole
     // iteration's recurrence including the two inter-kernel boundaries.
-    hipExtLaunchKernelGGL(k_cg_dot, dim3(n_stream), dim3(kThreads), 0, st, timed ? ea : nullptr, nullptr, 0, tab,
+    hipExtLaunchKernelGGL(k_cg_dot<Src>, dim3(n_stream), dim3(kThreads), 0, st, timed ? ea : nullptr, nullptr, 0, src,
                           chunks_dev, n_chunks, (const float*)p, cg_alpha, hvp_shift, partP);
-    hipLaunchKernelGGL(k_cg_resid, dim3(n_stream), dim3(kThreads), 0, st, tab, chunks_dev, n_chunks, r,
+    hipLaunchKernelGGL(k_cg_resid<Src>, dim3(n_stream), dim3(kThreads), 0, st, src, chunks_dev, n_chunks, r,
                        (const float*)p, hvp_shift, (const double*)partP, (const double*)partR_old, partR_new, n_stream, iter, scal);
     hipExtLaunchKernelGGL(k_cg_dir, dim3(n_stream), dim3(kThreads), 0, st, nullptr, timed ? eb : nullptr, 0,
                           chunks_dev, n_chunks, x, (const float*)r, p, (const double*)partR_new, n_stream,
@@ -1065,27 +1122,71 @@ int bhg_cg_step(const void* const* hvp, int T, const bhg_chunk* chunks_dev, int 
   } else {
     const int G = num_cus();
     if (n_chunks <= G * kResMax) {   // register-only instance: fastest while it fits (11.5 M elements)
-      hipExtLaunchKernelGGL((k_cg_resident<kResMax, 0, false>), dim3(G), dim3(kResThreads), 0, st, timed ? ea : nullptr,
-                            timed ? eb : nullptr, 0, tab, chunks_dev, n_chunks, x, r, p, cg_alpha, iter, out_scale,
+      hipExtLaunchKernelGGL((k_cg_resident<kResMax, 0, false, Src>), dim3(G), dim3(kResThreads), 0, st, timed ? ea : nullptr,
+                            timed ? eb : nullptr, 0, src, chunks_dev, n_chunks, x, r, p, cg_alpha, iter, out_scale,
                             hvp_shift, (const double*)partR_old, partR_new, partP,
                             reinterpret_cast<unsigned*>(w + kWsBarrier), scal, spin_limit());
     } else {
       constexpr size_t lds = (size_t)kResLds * kResV * kResThreads * sizeof(float4);
       BHG_REQUIRE(resident_lds_instances_ok(), "this device does not grant the resident kernel's 144 KiB of dynamic LDS");
       if (n_chunks <= G * kResMaxLds)   // LDS-assisted instance: 9 direction slices per workgroup parked in LDS (15.7 M elements)
-        hipExtLaunchKernelGGL((k_cg_resident<kResMaxLds, kResLds, false>), dim3(G), dim3(kResThreads), lds, st, timed ? ea : nullptr,
-                              timed ? eb : nullptr, 0, tab, chunks_dev, n_chunks, x, r, p, cg_alpha, iter, out_scale,
+        hipExtLaunchKernelGGL((k_cg_resident<kResMaxLds, kResLds, false, Src>), dim3(G), dim3(kResThreads), lds, st, timed ? ea : nullptr,
+                              timed ? eb : nullptr, 0, src, chunks_dev, n_chunks, x, r, p, cg_alpha, iter, out_scale,
                               hvp_shift, (const double*)partR_old, partR_new, partP,
                               reinterpret_cast<unsigned*>(w + kWsBarrier), scal, spin_limit());
       else                              // hybrid instance: 14 resident slots per workgroup, the rest streamed in the same launch
-        hipExtLaunchKernelGGL((k_cg_resident<kResHyb, kResLds, true>), dim3(G), dim3(kResThreads), lds, st, timed ? ea : nullptr,
-                              timed ? eb : nullptr, 0, tab, chunks_dev, n_chunks, x, r, p, cg_alpha, iter, out_scale,
+        hipExtLaunchKernelGGL((k_cg_resident<kResHyb, kResLds, true, Src>), dim3(G), dim3(kResThreads), lds, st, timed ? ea : nullptr,
+                              timed ? eb : nullptr, 0, src, chunks_dev, n_chunks, x, r, p, cg_alpha, iter, out_scale,
                               hvp_shift, (const double*)partR_old, partR_new, partP,
                               reinterpret_cast<unsigned*>(w + kWsBarrier), scal, spin_limit());
     }
   }
   BHG_HIP_CHECK(hipGetLastError());
   return BHG_OK;
+}
+}  // extern "C++"
+
+// BHG_CG_AUTO -> the variant bhg_cg_resident_usable picks; a RESIDENT request beyond the capacity is an error.
+static int cg_resolve_variant(int* variant, int n_chunks) {
+  const int cap = bhg_cg_resident_capacity_chunks();
+  if (*variant == BHG_CG_AUTO) *variant = bhg_cg_resident_usable(n_chunks) ? BHG_CG_RESIDENT : BHG_CG_STREAM;
+  if (*variant == BHG_CG_RESIDENT && n_chunks > cap) {
+    set_error("bhg_cg_step: %d chunks exceed the resident capacity of %d", n_chunks, cap);
+    return BHG_ERR_CAPACITY;
+  }
+  BHG_REQUIRE(*variant == BHG_CG_STREAM || *variant == BHG_CG_RESIDENT, "unknown variant");
+  return BHG_OK;
+}
+
+int bhg_cg_step(const void* const* hvp, int T, const bhg_chunk* chunks_dev, int n_chunks, float* x, float* r,
+                float* p, float cg_alpha, int iter, float out_scale, float hvp_shift, int variant, void* ws,
+                void* stream) {
+  BHG_COMMON_CHECKS(hvp);
+  BHG_REQUIRE(ws, "workspace is NULL");
+  BHG_REQUIRE(iter >= 0, "negative iteration index");
+  if (n_chunks == 0) return BHG_OK;
+  BHG_REQUIRE(x && r && p, "state vector is NULL");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (int rc = cg_resolve_variant(&variant, n_chunks)) return rc;
+  HvpTensors src;
+  if (int rc = make_table(&src.tab, hvp, T, ws, 0, st)) return rc;
+  return cg_step_launch(src, chunks_dev, n_chunks, x, r, p, cg_alpha, iter, out_scale, hvp_shift, variant, ws, st);
+}
+
+int bhg_cg_step_fd(const void* const* grad_plus, const void* const* grad_minus, const float* two_eps_dev, int T,
+                   const bhg_chunk* chunks_dev, int n_chunks, float* x, float* r, float* p, float cg_alpha, int iter,
+                   float out_scale, float hvp_shift, int variant, void* ws, void* stream) {
+  BHG_PAIR_CHECKS();
+  BHG_REQUIRE(ws, "workspace is NULL");
+  BHG_REQUIRE(iter >= 0, "negative iteration index");
+  if (n_chunks == 0) return BHG_OK;
+  BHG_REQUIRE(two_eps_dev, "two_eps is NULL");
+  BHG_REQUIRE(x && r && p, "state vector is NULL");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (int rc = cg_resolve_variant(&variant, n_chunks)) return rc;
+  HvpGradPair src;
+  if (int rc = make_pair(&src, grad_plus, grad_minus, T, two_eps_dev, ws, st)) return rc;
+  return cg_step_launch(src, chunks_dev, n_chunks, x, r, p, cg_alpha, iter, out_scale, hvp_shift, variant, ws, st);
 }
 
 // ---- phased streaming CG iteration: the same three kernels as BHG_CG_STREAM, one call per phase, so that a caller
@@ -1118,13 +1219,13 @@ int bhg_cg_phase(int phase, const void* const* hvp, int T, const bhg_chunk* chun
     BHG_HIP_CHECK(hipGetLastError());
     return BHG_OK;
   }
-  PtrTab tab;
-  if (int rc = make_table(&tab, hvp, T, ws, 0, st)) return rc;
+  HvpTensors tab;
+  if (int rc = make_table(&tab.tab, hvp, T, ws, 0, st)) return rc;
   if (phase == 0)
-    hipLaunchKernelGGL(k_cg_dot, dim3(n_stream), dim3(kThreads), 0, st, tab, chunks_dev, n_chunks, (const float*)p, cg_alpha,
+    hipLaunchKernelGGL(k_cg_dot<HvpTensors>, dim3(n_stream), dim3(kThreads), 0, st, tab, chunks_dev, n_chunks, (const float*)p, cg_alpha,
                        hvp_shift, partP);
   else
-    hipLaunchKernelGGL(k_cg_resid, dim3(n_stream), dim3(kThreads), 0, st, tab, chunks_dev, n_chunks, r, (const float*)p,
+    hipLaunchKernelGGL(k_cg_resid<HvpTensors>, dim3(n_stream), dim3(kThreads), 0, st, tab, chunks_dev, n_chunks, r, (const float*)p,
                        hvp_shift, (const double*)partP, (const double*)partR_old, partR_new, n_stream, iter, scal);
   BHG_HIP_CHECK(hipGetLastError());
   return BHG_OK;

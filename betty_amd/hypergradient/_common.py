@@ -171,6 +171,169 @@ class ForwardOverReverseHVP:
         return grads
 
 
+# ---- finite-difference Hessian-vector product (opt-in): cg / neumann without any second-order autograd call -----------------
+#     H p ~= ( grad_w L(w + eps p) - grad_w L(w - eps p) ) / (2 eps),        eps = R / (||p|| + 1e-15)
+# Both other sources need every operator of training_step to be twice differentiable (or to have a forward-mode formula): a
+# `once_differentiable` custom Function, a fused attention kernel, a checkpointed block or a vendor op without a double backward
+# raises in the first product.  This source asks for what training itself asks for — one backward — and costs 2 K + 3 ordinary
+# passes per solve: ONE forward at the unperturbed weights w0, which is the pass that moves the module's buffers (batch-norm running
+# statistics are those of w0, as after the reference's single training_step) and advances the RNG stream; two forward / backward
+# passes per iteration; two for the final hop.  No `in_grad` graph is built at all.
+#   * the live weights are perturbed from a flat SNAPSHOT taken once per solve (bhg_fd_perturb: w <- w0 + (+-eps) p), never by
+#     in-place +eps / -2 eps / +eps steps, and the solve ends with a scatter of the snapshot: the weights come back bit for bit;
+#   * the recurrence kernels consume the two gradient lists directly (bhg_cg_step_fd / bhg_neumann_step_fd form (g+ - g-) / 2 eps in
+#     registers): no N-sized H p is written;
+#   * the final hop d/d eps grad_lambda L(w + eps u)|0 at u = -alpha x is the opaque branch of darts.finite_difference (sync
+#     semantics unchanged: DDP hooks fire through `backward`).  darts returns the NEGATIVE of that derivative along its direction,
+#     so the solvers leave +alpha x in the flat solution for this source (InnerOperator.out_sign).
+# OPT-IN: `inner_problem.hypergradient_hvp = "finite_difference"`, radius R = `inner_problem.hypergradient_fd_radius` (default: the
+# reference's darts_alpha default, 0.01).  What a user gives up is the truncation error of an fp32 central difference
+# (profiles/fd_hvp_accuracy.txt).  The same promises as forward-over-reverse: trainable parameters are parameters of
+# `problem.module`; the RNG state at the start of the solve is restored before every pass (dropout draws one set of masks); the first
+# pass updates module buffers, the others run on clones.  Where it cannot apply (fd_hvp_blocker) the double backward runs, after one
+# warning per problem, and nothing is touched.
+FD_HVP_STATS = {"solves": 0, "pairs": 0, "fallbacks": 0}
+FD_HVP_DEFAULT_RADIUS = 0.01
+
+
+def finite_difference_wanted(curr) -> bool:
+    return getattr(curr, "hypergradient_hvp", None) == "finite_difference"
+
+
+def fd_hvp_blocker(curr):
+    """None when FiniteDifferenceHVP can run on ``curr``, else the reason (a string) the double backward takes the solve."""
+    if is_fsdp(curr):
+        return "the problem is FSDP-sharded (a flat shard's gradient only materialises through backward into .grad)"
+    if len(getattr(curr, "paths", None) or []) > 0:
+        return "the problem has lower-level paths"
+    if getattr(curr, "hypergradient_graph", False) == "persistent":
+        return "hypergradient_graph = 'persistent' is set (the persistent graphs capture the double backward)"
+    if torch.is_autocast_enabled() or precision_of(curr) in ("fp16", "bf16"):
+        return "autocast is on (a half-precision difference of gradients has no digits left at this radius)"
+    for p in curr.trainable_parameters():
+        if p.dtype != torch.float32 or not p.is_contiguous() or (p.numel() > 0 and p.data_ptr() % 16 != 0):
+            return "a trainable parameter is not a contiguous, 16-byte aligned fp32 tensor"
+    return None
+
+
+def finite_difference_usable(curr) -> bool:
+    """finite_difference_wanted and not blocked; a blocked request warns once per problem and counts as a fallback."""
+    if not finite_difference_wanted(curr):
+        return False
+    why = fd_hvp_blocker(curr)
+    if why is None:
+        return True
+    FD_HVP_STATS["fallbacks"] += 1
+    if not getattr(curr, "_bhg_fd_hvp_warned", False):
+        warnings.warn(f"betty_amd: hypergradient_hvp = 'finite_difference' does not apply here: {why}; using the double backward",
+                      RuntimeWarning, stacklevel=4)
+        try:
+            curr._bhg_fd_hvp_warned = True
+        except AttributeError:
+            pass
+    return False
+
+
+class GradientPair:
+    """What FiniteDifferenceHVP hands the solvers instead of a product: grad L(w + eps p), grad L(w - eps p) and the 0-dim fp32
+    device tensor 2 eps.  cg / neumann pass it to be.cg_step_fd / be.neumann_step_fd."""
+
+    __slots__ = ("plus", "minus", "two_eps")
+
+    def __init__(self, plus, minus, two_eps):
+        self.plus, self.minus, self.two_eps = plus, minus, two_eps
+
+
+class FiniteDifferenceHVP:
+    def __init__(self, curr, prev, loss_fn=None):
+        from torch.nn.utils import stateless  # noqa: PLC0415
+
+        from ..backend import get_backend  # noqa: PLC0415
+
+        self._swap = stateless._reparametrize_module
+        self.curr, self.prev, self.module = curr, prev, curr.module
+        # what is differentiated: the problem's training_step, or (ProximalRegularized) its data loss alone
+        self.loss_fn = loss_fn if loss_fn is not None else (lambda: curr.training_step_exec(curr.cur_batch))
+        self.params = list(curr.trainable_parameters())
+        owned = {id(p) for p in self.module.parameters()}
+        if any(id(p) not in owned for p in self.params):
+            raise ValueError("hypergradient_hvp = 'finite_difference': trainable parameters must be parameters of problem.module")
+        self.radius = float(getattr(curr, "hypergradient_fd_radius", FD_HVP_DEFAULT_RADIUS))
+        self.be = get_backend()
+        self.weights = [p.data for p in self.params]
+        self.layout = self.be.layout(self.weights)
+        w0 = getattr(self.layout, "_fd_hvp_snapshot", None)
+        if w0 is None:
+            w0 = self.layout._fd_hvp_snapshot = self.layout.new_flat()
+        self.w0 = w0
+        self.be.flatten(self.layout, self.weights, self.w0)   # once per solve
+        dev = self.params[0].device
+        self._dev, self._cuda = dev, dev.type == "cuda"
+        self._rng_cpu = torch.get_rng_state()
+        self._rng_dev = torch.cuda.get_rng_state(dev) if self._cuda else None
+        self.passes, self.pairs, self.dirty = 0, 0, False
+        FD_HVP_STATS["solves"] += 1
+        # the ONE pass that moves the real buffers and the RNG stream, at w0: what the reference's single training_step does.  Its
+        # value is not used; every later pass runs on buffer clones with the RNG state of the solve's start.
+        self.loss()
+
+    def loss(self):
+        """One evaluation of the inner loss at the weights of the moment: the RNG stream of the solve's start, and — after the first
+        pass (at w0, in __init__), which moves the real ones as the reference's single training_step does — clones of the module's
+        buffers AS THEY WERE at the start of the solve, so every perturbed pass normalises with the statistics the first one saw."""
+        swap = {}
+        if self.passes > 0:
+            torch.set_rng_state(self._rng_cpu)
+            if self._cuda:
+                torch.cuda.set_rng_state(self._rng_dev, self._dev)
+            swap = {n: b.clone() for n, b in self._buffers0.items()}
+        else:
+            self._buffers0 = {n: b.detach().clone() for n, b in self.module.named_buffers()}
+        self.passes += 1
+        if not swap:
+            return self.loss_fn()
+        with self._swap(self.module, swap):
+            return self.loss_fn()
+
+    def _grad_at(self, direction_views, eps32, sign: float):
+        self.be.fd_perturb(self.layout, self.weights, self.w0, direction_views, eps32, sign)
+        self.dirty = True
+        loss = self.loss()
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            grads = torch.autograd.grad(loss, self.params, allow_unused=True)   # first order: no create_graph anywhere
+        return [torch.zeros_like(p) if g is None else g for g, p in zip(grads, self.params)]
+
+    def __call__(self, direction_views: Sequence[torch.Tensor]) -> GradientPair:
+        eps32, eps64, _ = self.be.darts_eps(self.layout, direction_views, self.radius)
+        two_eps = (2.0 * eps64).to(torch.float32)
+        plus = self._grad_at(direction_views, eps32, 1.0)
+        minus = self._grad_at(direction_views, eps32, -1.0)
+        self.pairs += 1
+        FD_HVP_STATS["pairs"] += 1
+        return GradientPair(plus, minus, two_eps)
+
+    def restore(self):
+        """The inner weights back to the snapshot, bit for bit."""
+        if self.dirty:
+            self.be.scatter(self.layout, self.w0, self.weights)
+            self.dirty = False
+
+    def mixed(self, pos_views, sync: bool):
+        """cg.py:58-68 / neumann.py:44-54 without the double backward: d/d eps grad_lambda L(w + eps u)|0 at u = -alpha x.  ``pos_views``
+        holds +alpha x = -u: darts' central difference along d is (grad(w - eps d) - grad(w + eps d)) / 2 eps, which at d = -u is the
+        derivative along u."""
+        from .darts import finite_difference  # noqa: PLC0415
+
+        self.restore()
+        eps32, eps64, _ = self.be.darts_eps(self.layout, pos_views, self.radius)
+        self.dirty = True   # the hop's in-place steps leave w0 + eps d - 2 eps d: put the snapshot back instead of a third rounding
+        try:
+            return finite_difference(self.curr, self.prev, self.layout, pos_views, eps32, eps64, sync, restore=False, opaque_loss=self.loss)
+        finally:
+            self.restore()
+
+
 # ---- hipGraph replay of an opaque Hessian-vector product ----------------------------------------------------------------
 # The double backward of a user's training_step is hundreds to thousands of small ATen launches (cfg 2's MLP: ~1.1 ms per
 # HVP, launch-bound): the K HVPs of one solve run the SAME launch sequence on the SAME addresses — the autograd graph of
@@ -492,7 +655,10 @@ class InnerOperator:
     """The inner problem's Hessian for ONE solve of cg / neumann / cg_global: ``hvp(direction_views)`` builds the Hessian-vector
     product, ``mixed(neg_views, sync, solve)`` is the final hop to the upper parameters through the same source.  The source is, in
     this order: a structured provider; the persistent graphs (hypergradient_graph = "persistent"); forward-over-reverse passes
-    (hypergradient_hvp = "forward_over_reverse"); a double backward through ``inner_gradient``.  An autograd-based product of one
+    (hypergradient_hvp = "forward_over_reverse"); central differences of first-order gradients (hypergradient_hvp =
+    "finite_difference": ``hvp`` then returns GradientPair objects and the solvers leave ``out_sign * alpha * x`` = +alpha x for
+    ``mixed``); a double backward through ``inner_gradient``.  A provider that offers ``first_order_loss`` (ProximalRegularized) keeps
+    its shift and its closed-form hop and takes the finite-difference source for its data-loss product only.  An autograd-based product of one
     solve may be replayed as a HIP graph (GraphedHVP); ``graphs=False`` (cg_global) turns off every option but the provider and the
     plain double backward.  ``params``: what the autograd and persistent products differentiate.  Enter ``stream()`` around the whole
     solve: a captured product needs its autograd graph built on the capturing stream."""
@@ -502,15 +668,31 @@ class InnerOperator:
         self.graphed = graphs and (provider is None or getattr(provider, "hvp_is_autograd", False)) and hvp_graph_wanted(K, vector, curr)
         self.persist = persistent_graphs_for(curr, K, vector, prev) if graphs and provider is None else None
         self.for_hvp = graphs and provider is None and self.persist is None and forward_over_reverse_wanted(curr)
+        self.fd_loss = getattr(provider, "first_order_loss", None)
+        self.fd_hvp = bool(graphs and (provider is None or self.fd_loss is not None) and finite_difference_usable(curr))
+        if self.fd_hvp:
+            self.persist = None
+            self.graphed = False   # nothing to capture: the product is two training_step calls
+        # sign of the flat solution the solvers hand to mixed(): -alpha x, or +alpha x for the finite-difference hop (see above)
+        self.out_sign = 1.0 if (self.fd_hvp and provider is None) else -1.0
         self.device = vector[0].device if vector else None
         # a structured provider may leave a diagonal part of the Hessian (ridge) to the recurrence kernel
         self.shift = float(getattr(provider, "hvp_shift", 0.0))
-        self.in_grad, self.keep_graph, self.fwd = None, False, None
+        self.in_grad, self.keep_graph, self.fwd, self.fd = None, False, None, None
 
     def stream(self):
         return solve_stream(self.device, self.graphed or self.persist is not None)
 
+    def close(self):
+        """End of the solve, reached on every path out of it: a finite-difference solve that raised half-way (training_step at
+        w0 +- eps p ran out of memory, ...) must not leave the user's weights perturbed."""
+        if self.fd is not None:
+            self.fd.restore()
+
     def hvp(self, direction_views):
+        if self.fd_hvp:   # no second-order call at all: H p from two first-order gradients
+            self.fd = FiniteDifferenceHVP(self.curr, self.prev, None if self.provider is None else self.fd_loss())
+            return self.fd
         if self.provider is not None:
             fn = self.provider.prepare()
         elif self.persist is not None:
@@ -526,6 +708,10 @@ class InnerOperator:
 
     def mixed(self, neg_views, sync: bool, solve=False):
         """``solve``: what a fused solver returned; a token (not True) tells the provider WHICH solve the views name (structured.py)."""
+        if self.fd is not None:
+            if self.provider is None:
+                return self.fd.mixed(neg_views, sync)   # (holds +alpha x here: out_sign)
+            self.fd.restore()
         if self.provider is not None:
             if solve and solve is not True:
                 return self.provider.mixed_vjp(neg_views, sync, solve=solve)

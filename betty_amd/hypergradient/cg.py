@@ -13,7 +13,7 @@ from __future__ import annotations
 import torch
 
 from ..backend import get_backend
-from ._common import InnerOperator
+from ._common import GradientPair, InnerOperator
 from .structured import structured_hvp_for
 
 
@@ -26,7 +26,10 @@ def cg(vector, curr, prev, sync):
     K = int(curr.config.cg_iterations)
     op = InnerOperator(curr, prev, K, vector, structured_hvp_for(curr, prev), curr.parameters())
     with op.stream():
-        return _cg(vector, op, K, sync)
+        try:
+            return _cg(vector, op, K, sync)
+        finally:
+            op.close()   # (a finite-difference solve that raised must not leave the weights perturbed)
 
 
 def _cg(vector, op, K, sync):
@@ -66,9 +69,13 @@ def _cg(vector, op, K, sync):
             hvp = hvp_fn(p_views)  # H p   (cg.py:39-41)
             # cg.py:42-55 in one launch group; the last one also applies cg.py:56 and the negation
             last = k == K - 1 and alpha != 0.0
-            be.cg_step(layout, hvp, x, r, p, alpha, k, out_scale=(-alpha if last else 0.0), hvp_shift=op.shift)
+            out_scale = op.out_sign * alpha if last else 0.0   # (-alpha; +alpha for the finite-difference hop, see InnerOperator)
+            if isinstance(hvp, GradientPair):   # two first-order gradients: (g+ - g-) / 2 eps is formed inside the step's kernels
+                be.cg_step_fd(layout, hvp.plus, hvp.minus, hvp.two_eps, x, r, p, alpha, k, out_scale=out_scale, hvp_shift=op.shift)
+            else:
+                be.cg_step(layout, hvp, x, r, p, alpha, k, out_scale=out_scale, hvp_shift=op.shift)
         if K > 0 and alpha == 0.0:
-            be.scale_flat(x, -alpha)  # out_scale = 0 means "no final scaling" to the kernel: do cg.py:56 explicitly
+            be.scale_flat(x, op.out_sign * alpha)  # out_scale = 0 means "no final scaling" to the kernel: do cg.py:56 explicitly
         be.after_cg(layout)
     # K == 0: x is identically zero, -alpha * 0 needs no pass.
 

@@ -42,11 +42,13 @@ def darts(vector, curr, prev, sync):
     return finite_difference(curr, prev, layout, vector, eps32, eps64, sync, restore=not config.darts_multitask, is_fsdp=fsdp)
 
 
-def finite_difference(curr, prev, layout, direction, eps32, eps64, sync, restore, is_fsdp=False):
+def finite_difference(curr, prev, layout, direction, eps32, eps64, sync, restore, is_fsdp=False, opaque_loss=None):
     """The central finite difference of darts and sama along ``direction`` with radius ``eps``: the structure's own
     ``finite_difference`` when it offers one (never under FSDP), else two ``training_step`` calls through autograd at
-    ``w +- eps * direction``.  ``restore``: put the inner weights back afterwards (the multitask variants do not)."""
-    if not is_fsdp:
+    ``w +- eps * direction``.  ``restore``: put the inner weights back afterwards (the multitask variants do not).
+    ``opaque_loss``: go straight to the opaque branch and evaluate the inner loss with this callable instead of a bare
+    ``training_step_exec`` (the final hop of a finite-difference cg / neumann solve, _common.FiniteDifferenceHVP.mixed)."""
+    if not is_fsdp and opaque_loss is None:
         fd = getattr(structured_hvp_for(curr, prev), "finite_difference", None)
         if fd is not None:
             out = fd(layout, direction, eps32, eps64, sync, restore=restore)
@@ -59,7 +61,7 @@ def finite_difference(curr, prev, layout, direction, eps32, eps64, sync, restore
 
     # w <- w + eps*v   (darts.py:37-38)
     be.axpy_multi(layout, weights, direction, eps32, 1.0)
-    loss_p = curr.training_step_exec(curr.cur_batch)
+    loss_p = curr.training_step_exec(curr.cur_batch) if opaque_loss is None else opaque_loss()
     # is_fsdp: the gradient of a flat shard only materialises through backward into .grad (darts.py:40-42, utils.py:9-17)
     grad_p = replace_none_with_zero(grad(loss_p, upper, allow_unused=True, is_fsdp=is_fsdp), upper)
     if sync:
@@ -68,7 +70,7 @@ def finite_difference(curr, prev, layout, direction, eps32, eps64, sync, restore
 
     # w <- w - 2*eps*v   (darts.py:49-50)
     be.axpy_multi(layout, weights, direction, eps32, -2.0)
-    loss_n = curr.training_step_exec(curr.cur_batch)
+    loss_n = curr.training_step_exec(curr.cur_batch) if opaque_loss is None else opaque_loss()
     if sync:
         torch.autograd.backward(loss_n / two_eps, inputs=upper)  # darts.py:52-53 (DDP hooks fire)
         grad_n = None

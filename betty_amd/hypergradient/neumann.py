@@ -8,7 +8,7 @@ ATen launches; the final ``alpha*p`` and the negation are folded into the last i
 from __future__ import annotations
 
 from ..backend import get_backend
-from ._common import InnerOperator
+from ._common import GradientPair, InnerOperator
 from .structured import structured_hvp_for
 
 
@@ -19,7 +19,10 @@ def neumann(vector, curr, prev, sync):
     # neumann.py:39 differentiates w.r.t. trainable_parameters() (cg uses parameters())
     op = InnerOperator(curr, prev, K, vector, structured_hvp_for(curr, prev), curr.trainable_parameters())
     with op.stream():
-        return _neumann(vector, op, K, sync)
+        try:
+            return _neumann(vector, op, K, sync)
+        finally:
+            op.close()   # (a finite-difference solve that raised must not leave the weights perturbed)
 
 
 def _neumann(vector, op, K, sync):
@@ -42,8 +45,12 @@ def _neumann(vector, op, K, sync):
         for k in range(K):
             hvp = hvp_fn(v_views)  # neumann.py:62
             last = k == K - 1 and alpha != 0.0
-            be.neumann_step(layout, hvp, v, p, alpha, out_scale=(-alpha if last else 0.0), hvp_shift=op.shift)  # 63-64 (+66)
+            out_scale = op.out_sign * alpha if last else 0.0   # (-alpha; +alpha for the finite-difference hop, see InnerOperator)
+            if isinstance(hvp, GradientPair):   # two first-order gradients: (g+ - g-) / 2 eps is formed inside the step's kernel
+                be.neumann_step_fd(layout, hvp.plus, hvp.minus, hvp.two_eps, v, p, alpha, out_scale=out_scale, hvp_shift=op.shift)
+            else:
+                be.neumann_step(layout, hvp, v, p, alpha, out_scale=out_scale, hvp_shift=op.shift)  # 63-64 (+66)
         if K == 0 or alpha == 0.0:
-            be.scale_flat(p, -alpha)  # alpha * p (with p = v when K == 0)   (neumann.py:66)
+            be.scale_flat(p, op.out_sign * alpha)  # alpha * p (with p = v when K == 0)   (neumann.py:66)
 
     return op.mixed(layout.views(p, vector), sync, solve)

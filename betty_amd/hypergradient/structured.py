@@ -916,6 +916,11 @@ class ProximalRegularized(_QuadraticFD):
 
         return hvp
 
+    def first_order_loss(self):
+        """The data loss as a callable of no arguments: what hypergradient_hvp = "finite_difference" differentiates (first order, at
+        w +- eps p) instead of ``prepare``'s double backward; the shift and the closed-form hop below stay as they are."""
+        return lambda: self.data_loss(self.batch if self.batch is not None else self.curr.cur_batch)
+
     def mixed_vjp(self, neg_x_views, sync: bool):
         self._in_grad = None  # release the double-backward graph
         grads = [(-2.0 * self.reg) * t for t in neg_x_views]  # = +2*reg*(alpha*x)

@@ -165,6 +165,28 @@ int bhg_darts_eps(const void* const* vec, int T, const bhg_chunk* chunks_dev, in
 int bhg_axpy_multi(void* const* dst, const void* const* src, int T, const bhg_chunk* chunks_dev,
                    int n_chunks, const float* coef_dev, float mul, void* ws, void* stream);
 
+/* ---- finite-difference Hessian-vector product for cg / neumann (not in the reference: its cg.py:39-41 / neumann.py:62 take
+ * H p from a double backward) ---------------------------------------------------------------------------------------------
+ *     H p ~= ( grad L(w + eps p) - grad L(w - eps p) ) / (2 eps),      eps = R / (||p|| + 1e-15)   (bhg_darts_eps)
+ * from two ordinary backward passes: no second-order autograd call, any first-order-differentiable training_step.
+ * bhg_fd_perturb: w_t <- w0_t + (sign * *eps_dev) * dir_t over a layout's tensor list (product rounded, then the add), w0_flat
+ *        a flat snapshot of the weights (bhg_flatten, taken once per solve): every perturbed point is one rounding from exact
+ *        whatever K is, and bhg_scatter(w0_flat) at the end of the solve brings the weights back bit for bit.  12*N bytes.
+ * bhg_cg_step_fd / bhg_neumann_step_fd: bhg_cg_step / bhg_neumann_step on a GRADIENT PAIR — two tensor tables grad_plus,
+ *        grad_minus and the fp32 device scalar two_eps_dev; every element forms hp = (g+ - g-) / two_eps in registers (the
+ *        subtraction rounded, then a true fp32 division) and goes on exactly as the one-table step does with its hvp element:
+ *        bit-identical x, r, p (v, p) to the one-table step fed with ATen's (g+ - g-) / two_eps, and no N-sized H p is written.
+ *        Same variants, scalars, workspace and time-out word as bhg_cg_step; 32*N bytes per resident CG iteration (28*N + one
+ *        more N-sized read), 24*N per Neumann iteration.  ws: workspace of the layout (table slots 0 and 1 when T > 32).    */
+int bhg_fd_perturb(void* const* w, const float* w0_flat, const void* const* dir, int T, const bhg_chunk* chunks_dev,
+                   int n_chunks, const float* eps_dev, float sign, void* ws, void* stream);
+int bhg_cg_step_fd(const void* const* grad_plus, const void* const* grad_minus, const float* two_eps_dev, int T,
+                   const bhg_chunk* chunks_dev, int n_chunks, float* x, float* r, float* p, float cg_alpha, int iter,
+                   float out_scale, float hvp_shift, int variant, void* ws, void* stream);
+int bhg_neumann_step_fd(const void* const* grad_plus, const void* const* grad_minus, const float* two_eps_dev, int T,
+                        const bhg_chunk* chunks_dev, int n_chunks, float* v, float* p, float alpha, float out_scale,
+                        float hvp_shift, void* ws, void* stream);
+
 /* ---- SAMA (betty/hypergradient/sama.py:25, utils.py:37-63): Adam-preconditioned direction ----------
  * out_flat = vec * scale * lr with scale built from the optimizer state (last_grad, exp_avg,
  * exp_avg_sq): one fused pass over the four tensor lists (20*N bytes) instead of ~14 ATen
