@@ -641,6 +641,12 @@ void carve_fused_ws(const bhg_mlp* m, void* base, FusedWs* w) {
   w->bytes = off;
 }
 
+// k_graw (graw.inc) closes the iteration when the Gram matrices arrive packed; its loaders sum two K-split slabs at most.
+// (k_graw: K = the padded batch = 128 in registers; round 5: larger padded batches through the K-looped instance k_grawk)
+bool graw_single_on(bool packed, int Bp) { return packed && dbg(DBG_packed_gram, 1) != 0 && dbg(DBG_graw_v2, 1) != 0 && graw_batch_ok(Bp); }
+// the keys under which k_graw computes the step length inside its own launch and applies r' = r - alpha Hp to G(r) (rnew, lin)
+bool rnew_keys_on() { return dbg(DBG_proj_small_alone, 0) == 0 && dbg(DBG_alpha_in_hoist, 1) != 0 && dbg(DBG_rnew_in_graw, 1) != 0; }
+
 // Packed copies of the constants of a solve (wskp.inc): the chain's weights in both orientations, h_l and delta_l for the Gram
 // products.  One launch, once per solve: 3 x 15 M floats moved at cfg 2, ~1 % of a CG-20 solve.
 bool packed_chain_on(const FusedWs& w) { return w.Wf[1] != nullptr && dbg(DBG_packed_chain, 1) != 0; }
@@ -674,491 +680,403 @@ int pack_operands(const bhg_mlp* m, const FusedWs& w, hipStream_t st, bool weigh
   return BHG_OK;
 }
 
-// What one pass of the HVP chain does with its weight-shaped outputs.
-struct ChainMode {
-  int mode;                     // FUSE_NONE: store H*dir into out[] | FUSE_CG | FUSE_NEUMANN
-  void* const* out;             // FUSE_NONE
-  float* fa; float* fb; float* fd;   // fused: flat bases of FuseArgs a / b / d
-  const int64_t* starts;        // fused: element offsets of the 2L tensors inside the flat vectors
-  float alpha, shift, out_scale;
-  int apply_out;
-  // FUSE_CG
-  FusedWs* ws;
-  const double* partRR_old; int nRR_old;
-  const double* partPP; int nPP;
-  double* partRR_new;
-  double* scal;
-  float cg_alpha;
-  int kpar;                     // iteration parity
-  int x_mode;                   // see FuseArgs.x_mode (applies to the lazy slices only)
-  int first;                    // first iteration of a solve (Rz(x) accumulator is set, not added to)
-  int lazy;                     // the direction at fd is the previous one; this iteration's is fa + beta * fd
-  double* rzx_acc;              // FUSE_NEUMANN without an accumulator vector: sum_k Rz(v_k) lands here (head kernel)
-  int skip_outputs;             // FUSE_CG: stop after the step length (see bhg_mlp_cg_solve)
-  int gemm_mode;                // FUSE_NONE: BHG_MLP_WSK-style mode asked for by the caller (bhg_mlp_hvp_mode)
-  const HoistPlan* hoist;       // FUSE_CG + lazy: run the hoisted form of the chain (k_hoist); NULL = the classic chain
-  const BetaArgs* beta; int beta_blocks;   // hoisted form: k_cg_beta's work rides in k_hoist's launch (iterations > 0)
-  int proj;                     // hoisted: direction products from batch-sized recurrences (k_proj_update); CG: 1 / 2, Neumann: 1
-  int stop_after_head;          // projected Neumann: the closing pass that only adds Rz(v_K) to the accumulated Rz sums
-  // global-batch CG (bhg_mlp_cg_global_phase): the iteration is cut where the ranks must talk.
-  //   gphase 1: the R-chain only; this rank's share of p.H_data p -> php[0] (k_php_local)
-  //   gphase 2: step length from the all-reduced php[0] * inv_world, then the outputs with their epilogues
-  int gphase; double* php; double inv_world;
-  int second;                   // fully projected CG: iteration 1 (the scalars k_proj_step completes are those of the FIRST iteration)
-  int lin;                      // fully projected CG: the chain's first product by linearity, update launch inside it (k_wskpl; cg_ctx_init decides)
-  int nk;                       // projected Neumann: iteration index (the row-major Rh_0 lives in two slots by its parity, see vnew)
-  const void* const* rhs;       // fully projected CG, first iteration: the right-hand side's own tensors (bhg_mlp_cg_solve_rhs) or NULL
-  int lin_head;                 // lin on a four-layer net: the update blocks ride in the HEAD launch (k_headu), the pre-head launch is the plain product
-};
+#include "mlp/chain_plan.inc"   // host only: what one pass of run_chain is told (ChainMode), decides before its first launch (ChainPlan, plan_chain) and
+                                // hands from stage to stage (ChainState)
 
-// One Hessian-vector product of the MLP in direction `dir`, its weight-shaped outputs stored (FUSE_NONE) or consumed
-// by the CG / Neumann recurrence while still on chip (fused modes).  On return everything is ordered on `st`.
-//   FUSE_NONE / FUSE_NEUMANN: the outputs of layer l only need Rd_l and Rh_{l-1}, so they run on a library-owned side
-//     stream beside the R-backward chain (event fork / join).
-//   FUSE_CG: the fused epilogues need the step length, which needs the whole R-chain (T2 comes out of the R-backward
-//     reduces) — so there is nothing to overlap: ONE stream, no events (an event record costs the stream a ~4 us
-//     bubble, a cross-stream wait ~8 us: measured, rocprofv3 timelines in profiles/), and ONE launch for all
-//     weight-shaped outputs.
-int run_chain(const bhg_mlp* m, const void* const* dir, const ChainMode& cm, hipStream_t st) {
+// ---- hoisted form: every direction product in ONE grouped launch, then the chain with the constant weights only ---------
+// The direction products G(dir): the N-sized pass over the residual (k_hoist + k_hoist_reduce), or — projected forms past the first
+// iteration — their batch-sized recurrences (k_pstep / k_proj_update); with `lin` the update blocks are only described (ChainState.lin_ps).
+int hoist_products(const bhg_mlp* m, const void* const* dir, const ChainMode& cm, const ChainPlan& pl, hipStream_t st, ChainState* cs) {
   const int L = m->L, Bp = m->Bp, B = m->B;
-  const float rho2 = cm.mode == FUSE_NONE ? m->ridge2 : 0.f;
-  const bool cg = cm.mode == FUSE_CG;
-  const bool no_side_env = dbg(DBG_mlp_no_side, 0) != 0;    // A/B switches (debug)
-  const bool no_fuse = dbg(DBG_mlp_no_fuse, 0) != 0;
-  const bool no_outer_all = dbg(DBG_mlp_no_outer_all, 0) != 0;
-  const bool neumann_side = dbg(DBG_neumann_side, 0) != 0;    // A/B: fused Neumann with side-stream outputs
-  // `single`: one stream, no events, all weight-shaped outputs in one launch after the chain
-  const bool single = cg || (cm.mode == FUSE_NEUMANN && !neumann_side && !no_outer_all);
-  const bool no_side = no_side_env || single;
-  const bool head = use_head(m);
-  BHG_REQUIRE(!cg || head, "the fused CG solver needs the narrow-head kernels");
-  SideState* ssp = nullptr;
-  if (int rc = side_state(&ssp)) return rc;
-  SideState& ss = *ssp;
-  hipStream_t side = ss.side;
-  const int tn = skinny_tile_n();
-  const int wsk = wsk_mode(cm.mode, cm.gemm_mode);
-
-  FuseArgs fbase{};
-  fbase.scal = cm.scal; fbase.part = cm.partRR_new; fbase.alpha = cm.alpha; fbase.shift = cm.shift;
-  fbase.out_scale = cm.out_scale; fbase.apply_out = cm.apply_out;
-  fbase.part_stride = cg ? cm.ws->nRR : 0;
-  fbase.kpar = cm.kpar;
-  auto fuse_at = [&](int tensor, int part_base) {
-    FuseArgs f = fbase;
-    if (cm.mode != FUSE_NONE) {
-      const int64_t o = cm.starts[tensor];
-      f.a = cm.fa + o; f.b = cm.fb ? cm.fb + o : nullptr; f.d = cm.fd + o;
-      // lazy direction: only the MFMA layers' weight slices (the small slices were updated by k_cg_beta)
-      f.lazy = cm.lazy && (tensor & 1) == 0 && !(head && tensor == 2 * (L - 1));
-      f.x_mode = (f.lazy || cm.mode == FUSE_NEUMANN) ? cm.x_mode : 0;
-      if (!cm.fb) f.x_mode = 1;   // fused CG without a solution vector: nothing reads or writes x
+  const HoistPlan* hp = pl.hp;
+  float* hbase = pl.hoist;
+  HoistArgs ha{};
+  HoistRedArgs ra{};
+  for (int i = 0; i < hp->n; ++i) {
+    const int l = hp->layer[i];
+    HoistProb& q = ha.p[i];
+    q.A = hp->bwd[i] ? m->delta[l] : m->h[l];
+    // CG: the RESIDUAL's slice — G(p) = G(r) + beta G(p_old) (k_hoist_reduce); Neumann: the direction itself
+    q.Bm = pl.cg ? ((cm.first && cm.rhs) ? static_cast<const float*>(cm.rhs[2 * l]) : cm.fa + cm.starts[2 * l]) : static_cast<const float*>(dir[2 * l]);
+    q.slabs = hbase + hp->slab_off[i];
+    q.K = hp->K[i]; q.N = hp->N[i]; q.splits = hp->splits[i]; q.rc = hp->bwd[i];
+    q.lda = hp->K[i]; q.ldb = hp->bwd[i] ? hp->N[i] : hp->K[i];
+    ha.blk0[i] = hp->blk0[i];
+    HoistRedProb& rq = ra.p[i];
+    rq.slabs = q.slabs; rq.G = hbase + hp->g_off[i]; rq.N = hp->N[i]; rq.splits = hp->splits[i];
+    if (!hp->bwd[i] && l == 0) {
+      rq.bias = static_cast<const float*>(dir[1]); rq.mask = m->mask[0]; rq.out = m->Rh[0];
+      rq.outp = pl.packed ? cm.ws->Rhp[0] : nullptr;
     }
-    f.part_base = part_base;
-    return f;
-  };
-  // r'.r' partial slots of the fused CG epilogues: [W_0 tiles][W_1 tiles]...[bias blocks]
-  int part_base_w[BHG_MLP_MAX_LAYERS], part_base_bias = 0;
-  {
-    int base = 0;
-    for (int l = 0; l < L; ++l) { part_base_w[l] = base; base += outer_blocks(m, l, head); }
-    part_base_bias = base;
   }
-
-  // CG: needs the lazy direction (G(p) = G(r) + beta G(p_old)); Neumann: the direction v is explicit, G(v) directly
-  const HoistPlan* hp = ((cg && cm.lazy) || (cm.mode == FUSE_NEUMANN && single)) ? cm.hoist : nullptr;
-  // ---- hoisted form: every direction product in ONE grouped launch, then the chain with the constant weights only ---------
-  HeadFuse head_fuse{};
-  bool fuse_head = false;
-  const bool do_chain = cm.gphase != 2;
-  // projected CG, not the last iteration (projected Neumann: EVERY iteration): the iteration ends with the G(raw) products
-  const bool proj_iter = hp && cm.proj && (cg ? (!cm.apply_out && !cm.skip_outputs) : true);
-  // round 4: the chain through the constant weights on PACKED operands (wskp.inc), the per-iteration Gram products T_l / E_l as
-  // extra workgroups of the chain launch that consumes the same packed activation (debug keys packed_chain / packed_gram: A/B)
-  const bool packed = hp && packed_chain_on(*cm.ws);
-  const bool gram_in_chain = packed && proj_iter && !cm.stop_after_head && dbg(DBG_packed_gram, 1) != 0;
-  bool sd_in_chain = false;   // first iteration: S_l, D_l rode in the first chain launch as well
-  // k_graw (graw.inc) closes the iteration when the Gram matrices arrive packed; its loaders sum two K-split slabs at most.
-  // graw_single: what the NEXT iteration's recurrences are told about the layout of G(raw) (one slab per product, not one per pair)
-  // (k_graw: K = the padded batch = 128 in registers; round 5: larger padded batches through the K-looped instance k_grawk)
-  const bool graw_single = packed && dbg(DBG_packed_gram, 1) != 0 && dbg(DBG_graw_v2, 1) != 0 && graw_batch_ok(Bp);
-  const bool graw2 = gram_in_chain && graw_single;
-  // rnew: k_graw applies r' = r - alpha Hp to G(r) itself (GrawArgs.rnew) — like graw_single, what the NEXT iteration's recurrences
-  // are told (G(r) is up to date, there is no G(raw)); the conditions are those of the step length computed inside k_graw
-  const bool rnew = graw_single && cg && cm.proj >= 2 && cm.gphase == 0 && dbg(DBG_proj_small_alone, 0) == 0 &&
-                    dbg(DBG_alpha_in_hoist, 1) != 0 && dbg(DBG_rnew_in_graw, 1) != 0;
-  // vnew (round 5): the projected Neumann solver's k_graw applies v' = v - alpha (raw + shift v) to G(v) itself and leaves Rh_0(v') packed
-  // and row-major — neumann.py:63 has no scalars to wait for — so the update launch at the top of the next iteration (k_proj_update) is
-  // gone: SIX launches per iteration instead of seven.  Like rnew a property of the whole solve.  The row-major Rh_0 alternates between
-  // m->Rh[0] and a second slot (iteration parity): the Gb_1 tiles of the launch that writes Rh_0(v') still read Rh_0(v).
-  const bool vnew = cm.mode == FUSE_NEUMANN && hp && cm.proj && graw_single && L >= 3 && dbg(DBG_neumann_vnew, 1) != 0;
-  auto rh0_slot = [&](int k) { return (k & 1) ? cm.ws->hoist + hp->rh0alt_off : m->Rh[0]; };   // Rh_0(v_k), row-major
-  // lin: the chain's first product by linearity with the update launch riding in it (k_wskpl, wskpl.inc) — like rnew a property of
-  // the whole solve: every iteration's first product, every k_graw (Rh_0(r') for the next one) and cg_iteration (the second bias's
-  // direction in slots) follow it
-  const bool lin = cm.lin != 0;
-  BHG_REQUIRE(!lin || (rnew && hp && hp->lin_ok && cm.beta && cm.beta->nt <= 16 && proj_step_merged() && L >= 4),
-              "the linear first product was planned for a solve that cannot run it");
-  PstepArgs lin_ps{};   // the update blocks' arguments, built where k_pstep would be launched, used by the first product's launch
-  int lin_nu = 0, lin_U = 4;
-  bool lin_update_pending = false;   // the update blocks ride in the launch after the first product (k_wskpu)
-  auto gp1 = [&](int par) { return cm.ws->hoist + (par ? hp->gp1alt_off : hp->g_off[hp->gf[1]]); };   // Gf_1(p): two slots (lin)
-  const bool lin_head = lin && cm.lin_head != 0;
-  auto gp2 = [&](int par) { return cm.ws->hoist + (par ? hp->gp2alt_off : hp->g_off[hp->gf[L - 2]]); };   // Gf_{L-2}(p): two slots (lin_head)
-  // Gram products riding in chain launches: ONE K slab each — every rider sits in a launch whose tiles have the same K (T_1 with
-  // the forward product through W_1; E_l and T_{l+1} with the backward product through W_l), so it ends when they do
-  auto tsplit = [&](int K) { return gram_in_chain ? 1 : gram_ksplit(K); };
-  auto esplit = [&](int l, int K) { (void)l; return gram_in_chain ? 1 : gram_ksplit(K); };
-  (void)tsplit; (void)esplit; (void)sd_in_chain;   // (read by the measurement build's Gram / G(raw) launches only)
-  if (hp && do_chain) {
-    float* hbase = cm.ws->hoist;
-    HoistArgs ha{};
-    HoistRedArgs ra{};
+  ha.blk0[hp->n] = hp->blk0[hp->n];
+  ha.n = hp->n; ha.Bp = Bp; ha.gemm_blocks = hp->blk0[hp->n];
+  const bool proj = cm.proj != 0;
+  int rblk = 0;
+  for (int i = 0; i < hp->n; ++i) { ra.blk0[i] = rblk; rblk += (Bp * (hp->N[i] / 4) + 255) / 256; }
+  ra.blk0[hp->n] = rblk;
+  if (!proj || cm.first) {   // the N-sized pass over the residual: every iteration, or (projected CG) the first one only
+    ha.do_beta = (pl.cg && !cm.first && cm.beta && !proj) ? 1 : 0;
+    ha.beta_blocks = ha.do_beta ? cm.beta_blocks : 0;
+    if (ha.do_beta) ha.beta = *cm.beta;
+    hipLaunchKernelGGL(k_hoist<FUSE_CG>, dim3(ha.gemm_blocks + (ha.do_beta ? cm.beta_blocks : 0)), dim3(256), 0, st, ha);
+    ++g_hoist_launches;
+    if (proj && pl.cg) for (int i = 0; i < hp->n; ++i) ra.p[i].G2 = hbase + hp->gr_off[i];
+    ra.n = hp->n; ra.Bp = Bp; ra.B = B; ra.first = pl.cg ? cm.first : 1; ra.scal = cm.scal;
+    hipLaunchKernelGGL(k_hoist_reduce, dim3(rblk), dim3(256), 0, st, ra);
+    // (projected forms: the iteration-invariant Gram matrices S_l = h_l h_l^T, D_l = delta_l delta_l^T are formed once per
+    //  solve — in the FIRST iteration's Gram launch, below, beside T_l and E_l: nothing needs them before its G(raw) products)
+  } else if (pl.vnew) {         // the last iteration's k_graw applied the update and left Rh_0(v'): nothing to launch
+    ++g_proj_iterations;
+  } else {                   // projected CG: G(r), G(p) from their batch-sized recurrences — nothing N-sized is read
+    ProjArgs pa{};
     for (int i = 0; i < hp->n; ++i) {
-      const int l = hp->layer[i];
-      HoistProb& q = ha.p[i];
-      q.A = hp->bwd[i] ? m->delta[l] : m->h[l];
-      // CG: the RESIDUAL's slice — G(p) = G(r) + beta G(p_old) (k_hoist_reduce); Neumann: the direction itself
-      q.Bm = cg ? ((cm.first && cm.rhs) ? static_cast<const float*>(cm.rhs[2 * l]) : cm.fa + cm.starts[2 * l]) : static_cast<const float*>(dir[2 * l]);
-      q.slabs = hbase + hp->slab_off[i];
-      q.K = hp->K[i]; q.N = hp->N[i]; q.splits = hp->splits[i]; q.rc = hp->bwd[i];
-      q.lda = hp->K[i]; q.ldb = hp->bwd[i] ? hp->N[i] : hp->K[i];
-      ha.blk0[i] = hp->blk0[i];
-      HoistRedProb& rq = ra.p[i];
-      rq.slabs = q.slabs; rq.G = hbase + hp->g_off[i]; rq.N = hp->N[i]; rq.splits = hp->splits[i];
-      if (!hp->bwd[i] && l == 0) {
-        rq.bias = static_cast<const float*>(dir[1]); rq.mask = m->mask[0]; rq.out = m->Rh[0];
-        rq.outp = packed ? cm.ws->Rhp[0] : nullptr;
+      ProjProb& q = pa.p[i];
+      q.Gr = hbase + (pl.cg ? hp->gr_off[i] : hp->g_off[i]); q.Gp = hbase + hp->g_off[i]; q.Graw = hbase + hp->graw_off[i]; q.N = hp->N[i];
+      // (products with two operand pairs leave one slab per pair, see the G(raw) launch)
+      if (!pl.graw_single && graw_split() && !(hp->bwd[i] == 0 && hp->layer[i] == 0)) q.Graw2 = q.Graw + (size_t)Bp * hp->N[i];
+      if (pl.rnew) q.Graw = nullptr;   // (the last iteration's k_graw left r' in G(r))
+      if (!hp->bwd[i] && hp->layer[i] == 0) {
+        q.bias = static_cast<const float*>(dir[1]); q.mask = m->mask[0]; q.out = m->Rh[0];
+        q.outp = pl.packed ? cm.ws->Rhp[0] : nullptr;
       }
+      pa.blk0[i] = ra.blk0[i];
     }
-    ha.blk0[hp->n] = hp->blk0[hp->n];
-    ha.n = hp->n; ha.Bp = Bp; ha.gemm_blocks = hp->blk0[hp->n];
-    const bool proj = cm.proj != 0;
-    int rblk = 0;
-    for (int i = 0; i < hp->n; ++i) { ra.blk0[i] = rblk; rblk += (Bp * (hp->N[i] / 4) + 255) / 256; }
-    ra.blk0[hp->n] = rblk;
-    if (!proj || cm.first) {   // the N-sized pass over the residual: every iteration, or (projected CG) the first one only
-      ha.do_beta = (cg && !cm.first && cm.beta && !proj) ? 1 : 0;
-      ha.beta_blocks = ha.do_beta ? cm.beta_blocks : 0;
-      if (ha.do_beta) ha.beta = *cm.beta;
-      hipLaunchKernelGGL(k_hoist<FUSE_CG>, dim3(ha.gemm_blocks + (ha.do_beta ? cm.beta_blocks : 0)), dim3(256), 0, st, ha);
-      ++g_hoist_launches;
-      if (proj && cg) for (int i = 0; i < hp->n; ++i) ra.p[i].G2 = hbase + hp->gr_off[i];
-      ra.n = hp->n; ra.Bp = Bp; ra.B = B; ra.first = cg ? cm.first : 1; ra.scal = cm.scal;
-      hipLaunchKernelGGL(k_hoist_reduce, dim3(rblk), dim3(256), 0, st, ra);
-      // (projected forms: the iteration-invariant Gram matrices S_l = h_l h_l^T, D_l = delta_l delta_l^T are formed once per
-      //  solve — in the FIRST iteration's Gram launch, below, beside T_l and E_l: nothing needs them before its G(raw) products)
-    } else if (vnew) {         // the last iteration's k_graw applied the update and left Rh_0(v'): nothing to launch
-      ++g_proj_iterations;
-    } else {                   // projected CG: G(r), G(p) from their batch-sized recurrences — nothing N-sized is read
-      ProjArgs pa{};
-      for (int i = 0; i < hp->n; ++i) {
-        ProjProb& q = pa.p[i];
-        q.Gr = hbase + (cg ? hp->gr_off[i] : hp->g_off[i]); q.Gp = hbase + hp->g_off[i]; q.Graw = hbase + hp->graw_off[i]; q.N = hp->N[i];
-        // (products with two operand pairs leave one slab per pair, see the G(raw) launch)
-        if (!graw_single && graw_split() && !(hp->bwd[i] == 0 && hp->layer[i] == 0)) q.Graw2 = q.Graw + (size_t)Bp * hp->N[i];
-        if (rnew) q.Graw = nullptr;   // (the last iteration's k_graw left r' in G(r))
-        if (!hp->bwd[i] && hp->layer[i] == 0) {
-          q.bias = static_cast<const float*>(dir[1]); q.mask = m->mask[0]; q.out = m->Rh[0];
-          q.outp = packed ? cm.ws->Rhp[0] : nullptr;
-        }
-        pa.blk0[i] = ra.blk0[i];
+    pa.blk0[hp->n] = rblk;
+    pa.n = hp->n; pa.Bp = Bp; pa.B = B; pa.kpar_prev = cm.kpar ^ 1; pa.shift = cm.shift; pa.scal = pl.cg ? cm.scal : nullptr; pa.alpha = cm.alpha;
+    if (pl.cg && cm.proj >= 2 && proj_step_merged()) {   // + the scalars and the small slices' direction update of the LAST iteration
+      ProjStepArgs g{};
+      g.pa = pa;
+      ProjScalArgs& sa = g.sa;
+      sa.part_dot = cm.ws->part_dot; sa.dot_blocks = hp->dot_blocks;
+      sa.part_raw = cm.ws->part_raw; sa.raw_blocks = graw_blocks(hp, Bp);
+      if (pl.graw_single) {   // the last iteration closed with k_graw: three partials per tile workgroup
+        const int gt = graw_tile_count(hp, Bp);
+        sa.part_dot = cm.ws->part_graw; sa.dot_blocks = gt;
+        sa.part_raw = cm.ws->part_graw + 2 * (size_t)gt; sa.raw_blocks = gt;
       }
-      pa.blk0[hp->n] = rblk;
-      pa.n = hp->n; pa.Bp = Bp; pa.B = B; pa.kpar_prev = cm.kpar ^ 1; pa.shift = cm.shift; pa.scal = cg ? cm.scal : nullptr; pa.alpha = cm.alpha;
-      if (cg && cm.proj >= 2 && proj_step_merged()) {   // + the scalars and the small slices' direction update of the LAST iteration
-        ProjStepArgs g{};
-        g.pa = pa;
-        ProjScalArgs& sa = g.sa;
-        sa.part_dot = cm.ws->part_dot; sa.dot_blocks = hp->dot_blocks;
-        sa.part_raw = cm.ws->part_raw; sa.raw_blocks = graw_blocks(hp, Bp);
-        if (graw_single) {   // the last iteration closed with k_graw: three partials per tile workgroup
-          const int gt = graw_tile_count(hp, Bp);
-          sa.part_dot = cm.ws->part_graw; sa.dot_blocks = gt;
-          sa.part_raw = cm.ws->part_graw + 2 * (size_t)gt; sa.raw_blocks = gt;
+      sa.part = cm.beta->part; sa.part_stride = cm.ws->nRR;   // the last iteration's epilogue partials (= its partRR_new)
+      sa.off0 = pl.part_base_w[L - 1]; sa.n0 = outer_blocks(m, L - 1, pl.head); sa.off1 = pl.part_base_bias; sa.n1 = bias_blocks(m);
+      sa.r_small = cm.beta->r; sa.p_small = cm.beta->p; sa.snt = cm.beta->nt;
+      int small_total = 0;
+      for (int t = 0; t < cm.beta->nt; ++t) { sa.soff[t] = cm.beta->off[t]; sa.slen[t] = cm.beta->len[t]; small_total += cm.beta->len[t]; }
+      sa.scal = cm.scal; sa.pscal = cm.ws->pscal; sa.shift = cm.shift; sa.first = cm.second; sa.kpar = cm.kpar ^ 1;
+      const int sgrid = small_total > 0 ? (small_total + kThreads - 1) / kThreads : 1;
+      g.update_blocks = rblk;
+      g.r_b0 = cm.fa + cm.starts[1];
+      g.p0_rd = cm.second ? cm.fd + cm.starts[1] : cm.ws->pb0[cm.kpar ^ 1];
+      g.p0_wr = cm.ws->pb0[cm.kpar];
+      if (pl.graw_single && cm.beta->nt <= 16 && dbg(DBG_pstep_v2, 1) != 0) {   // the same work, arguments laid out for two round trips
+        PstepArgs ps{};
+        PstepHdr& h = ps.h;
+        // U float4s per thread of an update block: every block repeats the scalar phase (~12 KB of partials), so fewer, fatter
+        // blocks (944 -> 238 at cfg 2) repeat it less often
+        const int pu = pl.lin ? 4 : dbg(DBG_pstep_unroll, 4);
+        const int U = pu >= 4 ? 4 : (pu >= 2 ? 2 : 1);
+        int ublk = 0;
+        for (int i = 0; i < hp->n; ++i) { h.blk0[i] = ublk; ublk += (Bp * (hp->N[i] / 4) + 256 * U - 1) / (256 * U); }
+        h.blk0[hp->n] = ublk;
+        const int rblk = ublk;   // (shadows the one-float4-per-thread count of k_proj_step / k_hoist_reduce)
+        h.n = pa.n; h.Bp = pa.Bp; h.B = pa.B; h.kpar_prev = pa.kpar_prev; h.shift = pa.shift; h.update_blocks = rblk;
+        h.scal = sa.scal; h.r_b0 = g.r_b0; h.p0_rd = g.p0_rd; h.p0_wr = g.p0_wr; h.r_small = sa.r_small; h.p_small = sa.p_small;
+        h.part_dot = sa.part_dot; h.part_raw = sa.part_raw; h.part = sa.part; h.pscal = sa.pscal;
+        h.dot_blocks = sa.dot_blocks; h.raw_blocks = sa.raw_blocks; h.part_stride = sa.part_stride;
+        h.off0 = sa.off0; h.n0 = sa.n0; h.off1 = sa.off1; h.n1 = sa.n1; h.first = sa.first; h.kpar = sa.kpar; h.snt = sa.snt;
+        for (int i = 0; i < hp->n; ++i) {
+          const ProjProb& q = pa.p[i];
+          ps.p[i] = {q.Gr, q.Gp, q.Graw, q.bias, q.mask, q.out, q.outp, q.N, q.Graw ? 1 : 0};
+          if (pl.lin && i == hp->gf[1]) { ps.p[i].Gp = pl.gp1(cm.kpar ^ 1); ps.p[i].X = pl.gp1(cm.kpar); ps.p[i].xkind = 2; }
+          if (pl.lin_head && i == hp->gf[L - 2]) { ps.p[i].Gp = pl.gp2(cm.kpar ^ 1); ps.p[i].X = pl.gp2(cm.kpar); ps.p[i].xkind = 2; }
+          if (pl.lin) ps.p[i].outp = nullptr;   // (nobody reads a packed Rh_0(p): the first product runs on Rh_0(r'))
         }
-        sa.part = cm.beta->part; sa.part_stride = cm.ws->nRR;   // the last iteration's epilogue partials (= its partRR_new)
-        sa.off0 = part_base_w[L - 1]; sa.n0 = outer_blocks(m, L - 1, head); sa.off1 = part_base_bias; sa.n1 = bias_blocks(m);
-        sa.r_small = cm.beta->r; sa.p_small = cm.beta->p; sa.snt = cm.beta->nt;
-        int small_total = 0;
-        for (int t = 0; t < cm.beta->nt; ++t) { sa.soff[t] = cm.beta->off[t]; sa.slen[t] = cm.beta->len[t]; small_total += cm.beta->len[t]; }
-        sa.scal = cm.scal; sa.pscal = cm.ws->pscal; sa.shift = cm.shift; sa.first = cm.second; sa.kpar = cm.kpar ^ 1;
-        const int sgrid = small_total > 0 ? (small_total + kThreads - 1) / kThreads : 1;
-        g.update_blocks = rblk;
-        g.r_b0 = cm.fa + cm.starts[1];
-        g.p0_rd = cm.second ? cm.fd + cm.starts[1] : cm.ws->pb0[cm.kpar ^ 1];
-        g.p0_wr = cm.ws->pb0[cm.kpar];
-        if (graw_single && cm.beta->nt <= 16 && dbg(DBG_pstep_v2, 1) != 0) {   // the same work, arguments laid out for two round trips
-          PstepArgs ps{};
-          PstepHdr& h = ps.h;
-          // U float4s per thread of an update block: every block repeats the scalar phase (~12 KB of partials), so fewer, fatter
-          // blocks (944 -> 238 at cfg 2) repeat it less often
-          const int pu = lin ? 4 : dbg(DBG_pstep_unroll, 4);
-          const int U = pu >= 4 ? 4 : (pu >= 2 ? 2 : 1);
-          int ublk = 0;
-          for (int i = 0; i < hp->n; ++i) { h.blk0[i] = ublk; ublk += (Bp * (hp->N[i] / 4) + 256 * U - 1) / (256 * U); }
-          h.blk0[hp->n] = ublk;
-          const int rblk = ublk;   // (shadows the one-float4-per-thread count of k_proj_step / k_hoist_reduce)
-          h.n = pa.n; h.Bp = pa.Bp; h.B = pa.B; h.kpar_prev = pa.kpar_prev; h.shift = pa.shift; h.update_blocks = rblk;
-          h.scal = sa.scal; h.r_b0 = g.r_b0; h.p0_rd = g.p0_rd; h.p0_wr = g.p0_wr; h.r_small = sa.r_small; h.p_small = sa.p_small;
-          h.part_dot = sa.part_dot; h.part_raw = sa.part_raw; h.part = sa.part; h.pscal = sa.pscal;
-          h.dot_blocks = sa.dot_blocks; h.raw_blocks = sa.raw_blocks; h.part_stride = sa.part_stride;
-          h.off0 = sa.off0; h.n0 = sa.n0; h.off1 = sa.off1; h.n1 = sa.n1; h.first = sa.first; h.kpar = sa.kpar; h.snt = sa.snt;
-          for (int i = 0; i < hp->n; ++i) {
-            const ProjProb& q = pa.p[i];
-            ps.p[i] = {q.Gr, q.Gp, q.Graw, q.bias, q.mask, q.out, q.outp, q.N, q.Graw ? 1 : 0};
-            if (lin && i == hp->gf[1]) { ps.p[i].Gp = gp1(cm.kpar ^ 1); ps.p[i].X = gp1(cm.kpar); ps.p[i].xkind = 2; }
-            if (lin_head && i == hp->gf[L - 2]) { ps.p[i].Gp = gp2(cm.kpar ^ 1); ps.p[i].X = gp2(cm.kpar); ps.p[i].xkind = 2; }
-            if (lin) ps.p[i].outp = nullptr;   // (nobody reads a packed Rh_0(p): the first product runs on Rh_0(r'))
+        if (pl.lin) {
+          h.p1_rd = cm.second ? cm.fd + cm.starts[3] : cm.ws->pb1[cm.kpar ^ 1];
+          h.p1_wr = cm.ws->pb1[cm.kpar];
+          h.gran = cm.ws->gran;
+          h.rb0_copy = hbase + hp->rb0c_off;
+          h.prio = dbg(DBG_lin_prio, 0);
+          h.withhold = dbg(DBG_lin_withhold_beta, 0);   // (tests: the pollers' bounded wait, see poll_beta)
+          // launched update blocks (debug key lin_nub; 0 = one per virtual block): few, fat blocks leave most CUs to the tiles
+          // (1 = as many as leave the launch ONE workgroup per CU with the ragged row tiling: that instance needs 288 registers)
+          int nub = dbg(DBG_lin_nub, 0);
+          if (nub > 0) {
+            WskpProb tq{};
+            tq.RA = Bp; tq.RB = m->dims[2]; tq.B = B; tq.nsplit = 1;
+            wskp_tiling(&tq, true);
+            const int tiles = ((tq.nfull * (tq.RB / 32) + tq.nstrip + 7) & ~7) + (Bp / 32) * (Bp / 32);
+            const int room = chip_cus() - tiles - sgrid;
+            if (nub == 1 || nub > room) nub = room;
           }
-          if (lin) {
-            h.p1_rd = cm.second ? cm.fd + cm.starts[3] : cm.ws->pb1[cm.kpar ^ 1];
-            h.p1_wr = cm.ws->pb1[cm.kpar];
-            h.gran = cm.ws->gran;
-            h.rb0_copy = hbase + hp->rb0c_off;
-            h.prio = dbg(DBG_lin_prio, 0);
-            h.withhold = dbg(DBG_lin_withhold_beta, 0);   // (tests: the pollers' bounded wait, see poll_beta)
-            // launched update blocks (debug key lin_nub; 0 = one per virtual block): few, fat blocks leave most CUs to the tiles
-            // (1 = as many as leave the launch ONE workgroup per CU with the ragged row tiling: that instance needs 288 registers)
-            int nub = dbg(DBG_lin_nub, 0);
-            if (nub > 0) {
-              WskpProb tq{};
-              tq.RA = Bp; tq.RB = m->dims[2]; tq.B = B; tq.nsplit = 1;
-              wskp_tiling(&tq, true);
-              const int tiles = ((tq.nfull * (tq.RB / 32) + tq.nstrip + 7) & ~7) + (Bp / 32) * (Bp / 32);
-              const int room = chip_cus() - tiles - sgrid;
-              if (nub == 1 || nub > room) nub = room;
-            }
-            h.nub = (nub > 0 && nub < rblk) ? nub : 0;
-          }
-          for (int t = 0; t < sa.snt; ++t) { ps.t.slen[t] = sa.slen[t]; ps.t.soff[t] = sa.soff[t]; }
-          if (lin) { lin_ps = ps; lin_nu = (h.nub > 0 ? h.nub : rblk) + sgrid; lin_U = U; }
+          h.nub = (nub > 0 && nub < rblk) ? nub : 0;
+        }
+        for (int t = 0; t < sa.snt; ++t) { ps.t.slen[t] = sa.slen[t]; ps.t.soff[t] = sa.soff[t]; }
+        if (pl.lin) { cs->lin_ps = ps; cs->lin_nu = (h.nub > 0 ? h.nub : rblk) + sgrid; cs->lin_U = U; }
 #ifdef BHG_AB   // (debug key pstep_unroll)
-          else if (U == 2) hipLaunchKernelGGL(k_pstep<2>, dim3(rblk + sgrid), dim3(256), 0, st, ps);
-          else if (U == 1) hipLaunchKernelGGL(k_pstep<1>, dim3(rblk + sgrid), dim3(256), 0, st, ps);
+        else if (U == 2) hipLaunchKernelGGL(k_pstep<2>, dim3(rblk + sgrid), dim3(256), 0, st, ps);
+        else if (U == 1) hipLaunchKernelGGL(k_pstep<1>, dim3(rblk + sgrid), dim3(256), 0, st, ps);
 #endif
-          else hipLaunchKernelGGL(k_pstep<4>, dim3(rblk + sgrid), dim3(256), 0, st, ps);
-        } else {
+        else hipLaunchKernelGGL(k_pstep<4>, dim3(rblk + sgrid), dim3(256), 0, st, ps);
+      } else {
 #ifdef BHG_AB
-          hipLaunchKernelGGL(k_proj_step, dim3(rblk + sgrid), dim3(256), 0, st, g);
+        hipLaunchKernelGGL(k_proj_step, dim3(rblk + sgrid), dim3(256), 0, st, g);
 #else
-          BHG_REQUIRE(false, "internal: every plan of the product takes k_pstep (<= 16 small tensors, the packed closing launch)");
+        BHG_REQUIRE(false, "internal: every plan of the product takes k_pstep (<= 16 small tensors, the packed closing launch)");
 #endif
-        }
-      } else {
-        hipLaunchKernelGGL(k_proj_update, dim3(rblk), dim3(256), 0, st, pa);
       }
-      ++g_proj_iterations;
-    }
-    const int staged_mink = dbg(DBG_hoist_staged_mink, 256);
-    // forward chain: Rh_l = mask_l * (Rh_{l-1} W_l^T + Gf_l + c_l)
-    for (int l = 1; l + 1 < L; ++l) {
-      const int K = m->dims[l], N = m->dims[l + 1];
-      const float* c = static_cast<const float*>(dir[2 * l + 1]);
-      const float* Gf = hbase + hp->g_off[hp->gf[l]];
-      if (packed) {
-      if (lin && l == 1) {   // by linearity on Rh_0(r'), the update blocks in the same launch (wskpl.inc)
-        BHG_REQUIRE(cm.first || lin_nu > 0, "no update blocks for the linear first product");
-        WskplArgs la{};
-        WskpProb& q = la.a;
-        q.Ap = cm.first ? cm.ws->Rhp[0] : hbase + hp->rh0rp_off;   // (first iteration: p = r, Rh_0 from the N-sized pass)
-        q.Bq = cm.ws->Wf[1]; q.RA = Bp; q.RB = N; q.K = K; q.B = B; q.nsplit = 1;
-        q.mask = m->mask[1]; q.out = m->Rh[1]; q.outp = cm.ws->Rhp[1];
-        q.znew = hbase + hp->z1_off[cm.kpar];
-        if (cm.first) { q.addend = Gf; q.bias = c; }
-        else {
-          q.addend = hbase + hp->gr_off[hp->gf[1]]; q.addend2 = gp1(cm.kpar ^ 1);
-          q.bias = cm.fa + cm.starts[3]; q.bias2 = lin_ps.h.p1_rd;
-          q.zold = hbase + hp->z1_off[cm.kpar ^ 1];
-          q.gran = cm.ws->gran;
-        }
-        const int rider_blocks = gram_in_chain ? (Bp / 32) * (Bp / 32) : 0;
-        wskp_tiling(&q, false);
-        int na = (q.nfull * (q.RB / 32) + q.nstrip + 7) & ~7;
-        if (dbg(DBG_wskp_ragged, 1) == 2 || (dbg(DBG_wskp_ragged, 1) == 1 && na + rider_blocks > chip_cus()) ||
-            (!cm.first && lin_ps.h.nub > 0)) {
-          wskp_tiling(&q, true);
-          na = (q.nfull * (q.RB / 32) + q.nstrip + 7) & ~7;
-        }
-        la.na = na;
-        if (gram_in_chain) {   // T_1 = h_1 Rh_0^T, linear as well: T_1(p') = T_1(r') + beta T_1(p); two slots by parity
-          float* tnew = hbase + hp->tslab_off[1] + (size_t)cm.kpar * Bp * Bp;
-          float* tnewp = graw2 ? hbase + hp->tslabp_off[1] + (size_t)cm.kpar * Bp * Bp : nullptr;
-          la.r0 = {cm.ws->hpk[1], q.Ap, tnew, tnewp, K, 0};
-          la.r0_old = cm.first ? nullptr : hbase + hp->tslab_off[1] + (size_t)(cm.kpar ^ 1) * Bp * Bp;
-        }
-        la.nu = cm.first ? 0 : lin_nu;
-        // (debug key lin_order = 1: small blocks, tiles, update blocks — measured 66 us per iteration against 59.7: the update waves,
-        //  dispatched last, are the YOUNGEST on their SIMDs and lose every arbitration to the tiles' waves; dispatched first they win it)
-        // update blocks in the NEXT launch — when that is the pre-head product (L = 4), whose tiles leave raw K-split slabs and read
-        // nothing the update blocks write; a deeper net's second product adds Gf_2(p) in its epilogue, so its update blocks stay here
-        const bool upd_next = !cm.first && L == 4 && dbg(DBG_lin_update_next, 1) != 0 && lin_ps.h.nub == 0;
-        if (upd_next) {   // only the small slices' blocks (the first publishes beta) ride here, ahead of the tiles
-          la.ns = lin_nu - lin_ps.h.update_blocks;
-          la.nt = na + rider_blocks;
-        } else if (!cm.first && L > 4 && lin_ps.h.nub == 0) {   // deeper nets: [small blocks][update blocks][tiles] — publisher first
-          la.ns = lin_nu - lin_ps.h.update_blocks;
-          la.nt = na + rider_blocks;
-          la.upd_first = 1;
-        } else
-        if (!cm.first && dbg(DBG_lin_order, 0) != 0) {
-          la.ns = lin_nu - (lin_ps.h.nub > 0 ? lin_ps.h.nub : lin_ps.h.update_blocks);
-          la.nt = na + rider_blocks;
-        }
-        la.ps = lin_ps;
-        // (measurement arm lin_update_next = 0 on a four-layer net: the update blocks are dispatched AHEAD of the block that publishes
-        //  beta and poll for it — they must all fit on the chip beside it; the wait is bounded either way, this keeps the arm honest)
-        BHG_REQUIRE(cm.first || la.ns > 0 || lin_ps.h.update_blocks <= 2 * chip_cus(),
-                    "update blocks ahead of the publisher would not all be resident: use the default order");
-        const int grid = (upd_next ? la.ns : la.nu) + na + rider_blocks;
-        lin_update_pending = upd_next;
-        BHG_REQUIRE(cm.first || lin_U == 4, "the update blocks inside k_wskpl are built for four float4 per thread");
-#ifdef BHG_AB   // (debug key lin_nub)
-        if (la.ps.h.nub > 0) hipLaunchKernelGGL((k_wskpl<2, 4, true>), dim3(grid), dim3(64 * kWskpWaves), 0, st, la); else
-#endif
-        hipLaunchKernelGGL((k_wskpl<2, 4, false>), dim3(grid), dim3(64 * kWskpWaves), 0, st, la);
-        ++g_lin_launches;
-        if (cm.first)   // r|b0 as k_graw's tiles will read it (its bias blocks update the slice in the same launch)
-          BHG_HIP_CHECK(hipMemcpyAsync(hbase + hp->rb0c_off, cm.fa + cm.starts[1], sizeof(float) * (size_t)m->dims[1],
-                                       hipMemcpyDeviceToDevice, st));
-      } else {
-        WskpBuilder wb;
-        WskpProb q{};
-        q.Ap = cm.ws->Rhp[l - 1]; q.Bq = cm.ws->Wf[l]; q.RA = Bp; q.RB = N; q.K = K; q.B = B; q.nsplit = 1;
-        if (l == L - 2) {   // raw K-split slabs: the head kernel combines them itself (adds Gf and c_l, applies the mask)
-          // one workgroup per CU including the Gram product riding along: a second round of workgroups would start when the
-          // first ends (probe: 240 + 32 workgroups 9.1 us, 192 + 48 5.4 us)
-          const int riders = (gram_in_chain && l == 1) ? (Bp / 32) * (Bp / 32) : 0;
-          const int tiles_l = (Bp / 32) * (N / 32);
-          int sp = (chip_cus() - riders) / tiles_l;
-          const int cap = pick_splits((N + tn - 1) / tn, K, 1);                  // what m->partial was sized for
-          if (sp > cap) sp = cap;
-          if (sp > K / 64) sp = K / 64;
-          if (sp < 1) sp = 1;
-          q.nsplit = sp; q.raw = 1; q.out = m->partial;
-          // (lin_head, past the first iteration: the head forms Gf(p') = Gf(r') + beta Gf(p) itself — k_headu, see there)
-          head_fuse = {m->partial, sp, Bp * N, c, m->mask[l], m->Rh[l], (lin_head && !cm.first) ? hbase + hp->gr_off[hp->gf[l]] : Gf};
-          fuse_head = true;
-        } else {
-          q.bias = c; q.mask = m->mask[l]; q.addend = Gf; q.out = m->Rh[l]; q.outp = cm.ws->Rhp[l];
-        }
-        wb.add(q);
-        if (gram_in_chain && l == 1) {   // T_1 = h_1 Rh_0^T (same K as this launch's tiles)
-          WskpProb t{};
-          t.Ap = cm.ws->hpk[l]; t.Bq = cm.ws->Rhp[l - 1]; t.RA = Bp; t.RB = Bp; t.K = K; t.B = B;
-          t.nsplit = 1; t.raw = 1; t.out = hbase + hp->tslab_off[l]; t.outp = graw2 ? hbase + hp->tslabp_off[l] : nullptr;
-          wb.add(t);
-        }
-        if (lin_update_pending && wb.g.n == 1 && !lin_head) {   // (l = 2: nothing this product reads is written by the update blocks)
-          launch_wskpu(wb.g.p[0], lin_ps, lin_ps.h.update_blocks, st);
-          lin_update_pending = false;
-        } else wb.launch(st);
-      }
-        if (gram_in_chain && cm.first && l == 1) {   // once per solve: S_l = h_l h_l^T, D_l = delta_l delta_l^T (launches of their own:
-          WskpBuilder sb;                            // beside the first chain product they would stretch it — K up to d_0)
-          for (int j = 0; j + 1 < L; ++j) {
-            WskpProb u{};
-            u.Ap = cm.ws->hpk[j]; u.Bq = cm.ws->hpk[j]; u.RA = Bp; u.RB = Bp; u.K = m->dims[j]; u.B = B; u.raw = 1;
-            u.nsplit = 1;   // (constant over the solve: one slab)
-            u.out = hbase + hp->s_off[j]; u.outp = hbase + hp->sp_off[j];
-            if (!sb.add(u)) { sb.launch(st); sb.add(u); }
-            if (j >= 1) {
-              u.Ap = cm.ws->dpk[j]; u.Bq = cm.ws->dpk[j]; u.K = m->dims[j + 1]; u.out = hbase + hp->d_off[j]; u.outp = hbase + hp->dp_off[j];
-              if (!sb.add(u)) { sb.launch(st); sb.add(u); }
-            }
-          }
-          sb.launch(st);
-          sd_in_chain = true;
-        }
-        continue;
-      }
-      if (l == L - 2) {   // the head kernel combines this layer's slabs itself (and adds Gf)
-        GemmArgs a{};
-        a.pr[0] = {m->Rh[l - 1], m->W[l], K, K};
-        a.pairs = 1; a.M = Bp; a.N = N; a.K = K;
-        a.splits = pick_splits((N + tn - 1) / tn, K, 1);
-        a.out = m->partial; a.ldo = N; a.out_rows = Bp;
-        launch_gemm<LAYOUT_KC, LAYOUT_KC>(a, tn, st);
-        head_fuse = {m->partial, a.splits, Bp * N, c, m->mask[l], m->Rh[l], Gf};
-        fuse_head = true;
-      } else {
-        WskArgs w{};
-        w.pr[0] = {m->Rh[l - 1], m->W[l], K, K}; w.pairs = 1; w.M = Bp; w.N = N; w.K = K; w.B = B;
-        w.bias = c; w.mask = m->mask[l]; w.out = m->Rh[l]; w.addend = Gf;
-        launch_gemm_wsk<LAYOUT_KC>(w, st, K >= staged_mink);
-      }
-    }
-    BHG_REQUIRE(!lin_update_pending || lin_head, "the update blocks found no launch to ride in");
-    if (lin_update_pending) {   // the head launch with the update blocks behind the head's rows (k_headu)
-      const int l = L - 1, K = m->dims[l], N = m->dims[l + 1];
-      BHG_REQUIRE(fuse_head && cg && packed && N <= 12 && K <= 512, "k_headu was planned for a head it cannot run");
-      HeaduArgs ha{};
-      ha.Rh = (const float*)m->Rh[l - 1]; ha.h = m->h[l]; ha.W = m->W[l]; ha.V = static_cast<const float*>(dir[2 * l]);
-      ha.cb = static_cast<const float*>(dir[2 * l + 1]); ha.prob = m->prob; ha.sd = m->sd; ha.rd = m->Rd[l];
-      ha.K = K; ha.C = N; ha.B = B; ha.mode = HEAD_JVP;
-      ha.delta_top = (const float*)m->delta[l]; ha.mask_prev = (const float*)m->mask[l - 1]; ha.rd_prev = m->Rd[l - 1];
-      ha.fz = head_fuse;
-      ha.partT1 = cm.ws->partT1; ha.partT2h = cm.ws->partT2h; ha.rz_out = cm.ws->rz; ha.rzx_acc = cm.rzx_acc; ha.rzx_first = cm.first;
-      ha.rows = Bp; ha.rd_prev_p = cm.ws->Rdp[l - 1];
-      ha.addend2 = gp2(cm.kpar ^ 1); ha.gran = cm.ws->gran;
-      ha.nu = lin_ps.h.update_blocks; ha.ps = lin_ps; ha.head_first = dbg(DBG_headu_head_first, 1);
-      hipLaunchKernelGGL(k_headu<4>, dim3(ha.nu + Bp), dim3(256), (size_t)K * sizeof(float), st, ha);
-      lin_update_pending = false;
     } else {
-      const int l = L - 1, K = m->dims[l], N = m->dims[l + 1];
-      launch_head_forward(st, Bp, (const float*)m->Rh[l - 1], m->h[l], m->W[l], static_cast<const float*>(dir[2 * l]),
-                          static_cast<const float*>(dir[2 * l + 1]), m->prob, m->sd, m->Rd[l], K, N, B, HEAD_JVP, nullptr, nullptr,
-                          (const float*)m->delta[l], (const float*)m->mask[l - 1], m->Rd[l - 1], &head_fuse,
-                          cg ? cm.ws->partT1 : nullptr, cg ? cm.ws->partT2h : nullptr, cg ? cm.ws->rz : nullptr, cm.rzx_acc, cm.first,
-                          packed ? cm.ws->Rdp[l - 1] : nullptr);
+      hipLaunchKernelGGL(k_proj_update, dim3(rblk), dim3(256), 0, st, pa);
     }
-    if (cm.stop_after_head) {   // (projected Neumann's closing pass: Rz(v_K) is in the accumulator now)
-      BHG_HIP_CHECK(hipGetLastError());
-      return BHG_OK;
+    ++g_proj_iterations;
+  }
+  return BHG_OK;
+}
+
+// lin: the chain's first product (through W_1) by linearity on Rh_0(r'), the update blocks in the same launch (k_wskpl, wskpl.inc)
+int lin_first_product(const bhg_mlp* m, const void* const* dir, const ChainMode& cm, const ChainPlan& pl, hipStream_t st, ChainState* cs) {
+  const int L = m->L, Bp = m->Bp, B = m->B, K = m->dims[1], N = m->dims[2];
+  const HoistPlan* hp = pl.hp;
+  float* hbase = pl.hoist;
+  const float* c = static_cast<const float*>(dir[3]);
+  const float* Gf = hbase + hp->g_off[hp->gf[1]];
+  BHG_REQUIRE(cm.first || cs->lin_nu > 0, "no update blocks for the linear first product");
+  WskplArgs la{};
+  WskpProb& q = la.a;
+  q.Ap = cm.first ? cm.ws->Rhp[0] : hbase + hp->rh0rp_off;   // (first iteration: p = r, Rh_0 from the N-sized pass)
+  q.Bq = cm.ws->Wf[1]; q.RA = Bp; q.RB = N; q.K = K; q.B = B; q.nsplit = 1;
+  q.mask = m->mask[1]; q.out = m->Rh[1]; q.outp = cm.ws->Rhp[1];
+  q.znew = hbase + hp->z1_off[cm.kpar];
+  if (cm.first) { q.addend = Gf; q.bias = c; }
+  else {
+    q.addend = hbase + hp->gr_off[hp->gf[1]]; q.addend2 = pl.gp1(cm.kpar ^ 1);
+    q.bias = cm.fa + cm.starts[3]; q.bias2 = cs->lin_ps.h.p1_rd;
+    q.zold = hbase + hp->z1_off[cm.kpar ^ 1];
+    q.gran = cm.ws->gran;
+  }
+  const int rider_blocks = pl.gram_in_chain ? (Bp / 32) * (Bp / 32) : 0;
+  wskp_tiling(&q, false);
+  int na = (q.nfull * (q.RB / 32) + q.nstrip + 7) & ~7;
+  if (dbg(DBG_wskp_ragged, 1) == 2 || (dbg(DBG_wskp_ragged, 1) == 1 && na + rider_blocks > chip_cus()) ||
+      (!cm.first && cs->lin_ps.h.nub > 0)) {
+    wskp_tiling(&q, true);
+    na = (q.nfull * (q.RB / 32) + q.nstrip + 7) & ~7;
+  }
+  la.na = na;
+  if (pl.gram_in_chain) {   // T_1 = h_1 Rh_0^T, linear as well: T_1(p') = T_1(r') + beta T_1(p); two slots by parity
+    float* tnew = hbase + hp->tslab_off[1] + (size_t)cm.kpar * Bp * Bp;
+    float* tnewp = pl.graw2 ? hbase + hp->tslabp_off[1] + (size_t)cm.kpar * Bp * Bp : nullptr;
+    la.r0 = {cm.ws->hpk[1], q.Ap, tnew, tnewp, K, 0};
+    la.r0_old = cm.first ? nullptr : hbase + hp->tslab_off[1] + (size_t)(cm.kpar ^ 1) * Bp * Bp;
+  }
+  la.nu = cm.first ? 0 : cs->lin_nu;
+  // (debug key lin_order = 1: small blocks, tiles, update blocks — measured 66 us per iteration against 59.7: the update waves,
+  //  dispatched last, are the YOUNGEST on their SIMDs and lose every arbitration to the tiles' waves; dispatched first they win it)
+  // update blocks in the NEXT launch — when that is the pre-head product (L = 4), whose tiles leave raw K-split slabs and read
+  // nothing the update blocks write; a deeper net's second product adds Gf_2(p) in its epilogue, so its update blocks stay here
+  const bool upd_next = !cm.first && L == 4 && dbg(DBG_lin_update_next, 1) != 0 && cs->lin_ps.h.nub == 0;
+  if (upd_next) {   // only the small slices' blocks (the first publishes beta) ride here, ahead of the tiles
+    la.ns = cs->lin_nu - cs->lin_ps.h.update_blocks;
+    la.nt = na + rider_blocks;
+  } else if (!cm.first && L > 4 && cs->lin_ps.h.nub == 0) {   // deeper nets: [small blocks][update blocks][tiles] — publisher first
+    la.ns = cs->lin_nu - cs->lin_ps.h.update_blocks;
+    la.nt = na + rider_blocks;
+    la.upd_first = 1;
+  } else
+  if (!cm.first && dbg(DBG_lin_order, 0) != 0) {
+    la.ns = cs->lin_nu - (cs->lin_ps.h.nub > 0 ? cs->lin_ps.h.nub : cs->lin_ps.h.update_blocks);
+    la.nt = na + rider_blocks;
+  }
+  la.ps = cs->lin_ps;
+  // (measurement arm lin_update_next = 0 on a four-layer net: the update blocks are dispatched AHEAD of the block that publishes
+  //  beta and poll for it — they must all fit on the chip beside it; the wait is bounded either way, this keeps the arm honest)
+  BHG_REQUIRE(cm.first || la.ns > 0 || cs->lin_ps.h.update_blocks <= 2 * chip_cus(),
+              "update blocks ahead of the publisher would not all be resident: use the default order");
+  const int grid = (upd_next ? la.ns : la.nu) + na + rider_blocks;
+  cs->lin_update_pending = upd_next;
+  BHG_REQUIRE(cm.first || cs->lin_U == 4, "the update blocks inside k_wskpl are built for four float4 per thread");
+#ifdef BHG_AB   // (debug key lin_nub)
+  if (la.ps.h.nub > 0) hipLaunchKernelGGL((k_wskpl<2, 4, true>), dim3(grid), dim3(64 * kWskpWaves), 0, st, la); else
+#endif
+  hipLaunchKernelGGL((k_wskpl<2, 4, false>), dim3(grid), dim3(64 * kWskpWaves), 0, st, la);
+  ++g_lin_launches;
+  if (cm.first)   // r|b0 as k_graw's tiles will read it (its bias blocks update the slice in the same launch)
+    BHG_HIP_CHECK(hipMemcpyAsync(hbase + hp->rb0c_off, cm.fa + cm.starts[1], sizeof(float) * (size_t)m->dims[1],
+                                 hipMemcpyDeviceToDevice, st));
+  return BHG_OK;
+}
+
+int hoist_forward(const bhg_mlp* m, const void* const* dir, const ChainMode& cm, const ChainPlan& pl, hipStream_t st, int staged_mink,
+                  ChainState* cs) {
+  const int L = m->L, Bp = m->Bp, B = m->B;
+  const HoistPlan* hp = pl.hp;
+  float* hbase = pl.hoist;
+  // forward chain: Rh_l = mask_l * (Rh_{l-1} W_l^T + Gf_l + c_l)
+  for (int l = 1; l + 1 < L; ++l) {
+    const int K = m->dims[l], N = m->dims[l + 1];
+    const float* c = static_cast<const float*>(dir[2 * l + 1]);
+    const float* Gf = hbase + hp->g_off[hp->gf[l]];
+    if (pl.packed) {
+    if (pl.lin && l == 1) {
+      if (int rc = lin_first_product(m, dir, cm, pl, st, cs)) return rc;
+    } else {
+      WskpBuilder wb;
+      WskpProb q{};
+      q.Ap = cm.ws->Rhp[l - 1]; q.Bq = cm.ws->Wf[l]; q.RA = Bp; q.RB = N; q.K = K; q.B = B; q.nsplit = 1;
+      if (l == L - 2) {   // raw K-split slabs: the head kernel combines them itself (adds Gf and c_l, applies the mask)
+        // one workgroup per CU including the Gram product riding along: a second round of workgroups would start when the
+        // first ends (probe: 240 + 32 workgroups 9.1 us, 192 + 48 5.4 us)
+        const int riders = (pl.gram_in_chain && l == 1) ? (Bp / 32) * (Bp / 32) : 0;
+        const int tiles_l = (Bp / 32) * (N / 32);
+        int sp = (chip_cus() - riders) / tiles_l;
+        const int cap = pick_splits((N + pl.tn - 1) / pl.tn, K, 1);                  // what m->partial was sized for
+        if (sp > cap) sp = cap;
+        if (sp > K / 64) sp = K / 64;
+        if (sp < 1) sp = 1;
+        q.nsplit = sp; q.raw = 1; q.out = m->partial;
+        // (lin_head, past the first iteration: the head forms Gf(p') = Gf(r') + beta Gf(p) itself — k_headu, see there)
+        cs->head_fuse = {m->partial, sp, Bp * N, c, m->mask[l], m->Rh[l], (pl.lin_head && !cm.first) ? hbase + hp->gr_off[hp->gf[l]] : Gf};
+        cs->fuse_head = true;
+      } else {
+        q.bias = c; q.mask = m->mask[l]; q.addend = Gf; q.out = m->Rh[l]; q.outp = cm.ws->Rhp[l];
+      }
+      wb.add(q);
+      if (pl.gram_in_chain && l == 1) {   // T_1 = h_1 Rh_0^T (same K as this launch's tiles)
+        WskpProb t{};
+        t.Ap = cm.ws->hpk[l]; t.Bq = cm.ws->Rhp[l - 1]; t.RA = Bp; t.RB = Bp; t.K = K; t.B = B;
+        t.nsplit = 1; t.raw = 1; t.out = hbase + hp->tslab_off[l]; t.outp = pl.graw2 ? hbase + hp->tslabp_off[l] : nullptr;
+        wb.add(t);
+      }
+      if (cs->lin_update_pending && wb.g.n == 1 && !pl.lin_head) {   // (l = 2: nothing this product reads is written by the update blocks)
+        launch_wskpu(wb.g.p[0], cs->lin_ps, cs->lin_ps.h.update_blocks, st);
+        cs->lin_update_pending = false;
+      } else wb.launch(st);
     }
-    // backward chain: Rd_{l-1} = mask_{l-1} * (Rd_l W_l + Gb_l); T2_l = 2 <Gb_l, Rh_{l-1}> from the tile epilogue
-    for (int l = L - 2; l >= 1; --l) {
-      const int K = m->dims[l + 1], N = m->dims[l];
-      if (packed) {
-        WskpBuilder wb;
-        WskpProb q{};
-        q.Ap = cm.ws->Rdp[l]; q.Bq = cm.ws->Wb[l]; q.RA = Bp; q.RB = N; q.K = K; q.B = B; q.nsplit = 1;
-        q.mask = m->mask[l - 1]; q.addend = hbase + hp->g_off[hp->gb[l]]; q.out = m->Rd[l - 1];
-        q.outp = l >= 2 ? cm.ws->Rdp[l - 1] : nullptr;
-        if (cg) { q.rh = m->Rh[l - 1]; q.partT2 = cm.ws->partT2 + cm.ws->t2_off[l]; }
-        wb.add(q);
-        if (gram_in_chain) {   // E_l = delta_l Rd_l^T, and T_{l+1} = h_{l+1} Rh_l^T: both reduce over d_{l+1}, like this launch's tiles
-          WskpProb t{};
-          t.Ap = cm.ws->dpk[l]; t.Bq = cm.ws->Rdp[l]; t.RA = Bp; t.RB = Bp; t.K = K; t.B = B;
-          t.nsplit = 1; t.raw = 1; t.out = hbase + hp->eslab_off[l]; t.outp = graw2 ? hbase + hp->eslabp_off[l] : nullptr;
-          wb.add(t);
-          if (l + 1 <= L - 2) {
-            t.Ap = cm.ws->hpk[l + 1]; t.Bq = cm.ws->Rhp[l];
-            t.out = hbase + hp->tslab_off[l + 1]; t.outp = graw2 ? hbase + hp->tslabp_off[l + 1] : nullptr;
-            wb.add(t);
+      if (pl.gram_in_chain && cm.first && l == 1) {   // once per solve: S_l = h_l h_l^T, D_l = delta_l delta_l^T (launches of their own:
+        WskpBuilder sb;                            // beside the first chain product they would stretch it — K up to d_0)
+        for (int j = 0; j + 1 < L; ++j) {
+          WskpProb u{};
+          u.Ap = cm.ws->hpk[j]; u.Bq = cm.ws->hpk[j]; u.RA = Bp; u.RB = Bp; u.K = m->dims[j]; u.B = B; u.raw = 1;
+          u.nsplit = 1;   // (constant over the solve: one slab)
+          u.out = hbase + hp->s_off[j]; u.outp = hbase + hp->sp_off[j];
+          if (!sb.add(u)) { sb.launch(st); sb.add(u); }
+          if (j >= 1) {
+            u.Ap = cm.ws->dpk[j]; u.Bq = cm.ws->dpk[j]; u.K = m->dims[j + 1]; u.out = hbase + hp->d_off[j]; u.outp = hbase + hp->dp_off[j];
+            if (!sb.add(u)) { sb.launch(st); sb.add(u); }
           }
         }
-        wb.launch(st);
-        continue;
+        sb.launch(st);
+        cs->sd_in_chain = true;
       }
+      continue;
+    }
+    if (l == L - 2) {   // the head kernel combines this layer's slabs itself (and adds Gf)
+      GemmArgs a{};
+      a.pr[0] = {m->Rh[l - 1], m->W[l], K, K};
+      a.pairs = 1; a.M = Bp; a.N = N; a.K = K;
+      a.splits = pick_splits((N + pl.tn - 1) / pl.tn, K, 1);
+      a.out = m->partial; a.ldo = N; a.out_rows = Bp;
+      launch_gemm<LAYOUT_KC, LAYOUT_KC>(a, pl.tn, st);
+      cs->head_fuse = {m->partial, a.splits, Bp * N, c, m->mask[l], m->Rh[l], Gf};
+      cs->fuse_head = true;
+    } else {
       WskArgs w{};
-      w.pr[0] = {m->Rd[l], m->W[l], K, N}; w.pairs = 1; w.M = Bp; w.N = N; w.K = K; w.B = B;
-      w.mask = m->mask[l - 1]; w.out = m->Rd[l - 1]; w.addend = hbase + hp->g_off[hp->gb[l]];
-      if (cg) { w.rh = m->Rh[l - 1]; w.partT2 = cm.ws->partT2 + cm.ws->t2_off[l]; }
-      launch_gemm_wsk<LAYOUT_RC>(w, st, K >= staged_mink);
+      w.pr[0] = {m->Rh[l - 1], m->W[l], K, K}; w.pairs = 1; w.M = Bp; w.N = N; w.K = K; w.B = B;
+      w.bias = c; w.mask = m->mask[l]; w.out = m->Rh[l]; w.addend = Gf;
+      launch_gemm_wsk<LAYOUT_KC>(w, st, K >= staged_mink);
     }
   }
-  // ---- R-forward ------------------------------------------------------------------------------------
-  for (int l = 0; l < L && !hp && do_chain; ++l) {
+  BHG_REQUIRE(!cs->lin_update_pending || pl.lin_head, "the update blocks found no launch to ride in");
+  return BHG_OK;
+}
+
+// The head launch of the hoisted form: Rd_{L-1} and Rd_{L-2}, the pre-head product's slabs combined on the way (ChainState.head_fuse)
+int hoist_head(const bhg_mlp* m, const void* const* dir, const ChainMode& cm, const ChainPlan& pl, hipStream_t st, ChainState* cs) {
+  const int L = m->L, Bp = m->Bp, B = m->B;
+  if (cs->lin_update_pending) {   // the head launch with the update blocks behind the head's rows (k_headu)
+    const int l = L - 1, K = m->dims[l], N = m->dims[l + 1];
+    BHG_REQUIRE(cs->fuse_head && pl.cg && pl.packed && N <= 12 && K <= 512, "k_headu was planned for a head it cannot run");
+    HeaduArgs ha{};
+    ha.Rh = (const float*)m->Rh[l - 1]; ha.h = m->h[l]; ha.W = m->W[l]; ha.V = static_cast<const float*>(dir[2 * l]);
+    ha.cb = static_cast<const float*>(dir[2 * l + 1]); ha.prob = m->prob; ha.sd = m->sd; ha.rd = m->Rd[l];
+    ha.K = K; ha.C = N; ha.B = B; ha.mode = HEAD_JVP;
+    ha.delta_top = (const float*)m->delta[l]; ha.mask_prev = (const float*)m->mask[l - 1]; ha.rd_prev = m->Rd[l - 1];
+    ha.fz = cs->head_fuse;
+    ha.partT1 = cm.ws->partT1; ha.partT2h = cm.ws->partT2h; ha.rz_out = cm.ws->rz; ha.rzx_acc = cm.rzx_acc; ha.rzx_first = cm.first;
+    ha.rows = Bp; ha.rd_prev_p = cm.ws->Rdp[l - 1];
+    ha.addend2 = pl.gp2(cm.kpar ^ 1); ha.gran = cm.ws->gran;
+    ha.nu = cs->lin_ps.h.update_blocks; ha.ps = cs->lin_ps; ha.head_first = dbg(DBG_headu_head_first, 1);
+    hipLaunchKernelGGL(k_headu<4>, dim3(ha.nu + Bp), dim3(256), (size_t)K * sizeof(float), st, ha);
+    cs->lin_update_pending = false;
+  } else {
+    const int l = L - 1, K = m->dims[l], N = m->dims[l + 1];
+    launch_head_forward(st, Bp, (const float*)m->Rh[l - 1], m->h[l], m->W[l], static_cast<const float*>(dir[2 * l]),
+                        static_cast<const float*>(dir[2 * l + 1]), m->prob, m->sd, m->Rd[l], K, N, B, HEAD_JVP, nullptr, nullptr,
+                        (const float*)m->delta[l], (const float*)m->mask[l - 1], m->Rd[l - 1], &cs->head_fuse,
+                        pl.cg ? cm.ws->partT1 : nullptr, pl.cg ? cm.ws->partT2h : nullptr, pl.cg ? cm.ws->rz : nullptr, cm.rzx_acc, cm.first,
+                        pl.packed ? cm.ws->Rdp[l - 1] : nullptr);
+  }
+  return BHG_OK;
+}
+
+void hoist_backward(const bhg_mlp* m, const ChainMode& cm, const ChainPlan& pl, hipStream_t st, int staged_mink) {
+  const int L = m->L, Bp = m->Bp, B = m->B;
+  const HoistPlan* hp = pl.hp;
+  float* hbase = pl.hoist;
+  // backward chain: Rd_{l-1} = mask_{l-1} * (Rd_l W_l + Gb_l); T2_l = 2 <Gb_l, Rh_{l-1}> from the tile epilogue
+  for (int l = L - 2; l >= 1; --l) {
+    const int K = m->dims[l + 1], N = m->dims[l];
+    if (pl.packed) {
+      WskpBuilder wb;
+      WskpProb q{};
+      q.Ap = cm.ws->Rdp[l]; q.Bq = cm.ws->Wb[l]; q.RA = Bp; q.RB = N; q.K = K; q.B = B; q.nsplit = 1;
+      q.mask = m->mask[l - 1]; q.addend = hbase + hp->g_off[hp->gb[l]]; q.out = m->Rd[l - 1];
+      q.outp = l >= 2 ? cm.ws->Rdp[l - 1] : nullptr;
+      if (pl.cg) { q.rh = m->Rh[l - 1]; q.partT2 = cm.ws->partT2 + cm.ws->t2_off[l]; }
+      wb.add(q);
+      if (pl.gram_in_chain) {   // E_l = delta_l Rd_l^T, and T_{l+1} = h_{l+1} Rh_l^T: both reduce over d_{l+1}, like this launch's tiles
+        WskpProb t{};
+        t.Ap = cm.ws->dpk[l]; t.Bq = cm.ws->Rdp[l]; t.RA = Bp; t.RB = Bp; t.K = K; t.B = B;
+        t.nsplit = 1; t.raw = 1; t.out = hbase + hp->eslab_off[l]; t.outp = pl.graw2 ? hbase + hp->eslabp_off[l] : nullptr;
+        wb.add(t);
+        if (l + 1 <= L - 2) {
+          t.Ap = cm.ws->hpk[l + 1]; t.Bq = cm.ws->Rhp[l];
+          t.out = hbase + hp->tslab_off[l + 1]; t.outp = pl.graw2 ? hbase + hp->tslabp_off[l + 1] : nullptr;
+          wb.add(t);
+        }
+      }
+      wb.launch(st);
+      continue;
+    }
+    WskArgs w{};
+    w.pr[0] = {m->Rd[l], m->W[l], K, N}; w.pairs = 1; w.M = Bp; w.N = N; w.K = K; w.B = B;
+    w.mask = m->mask[l - 1]; w.out = m->Rd[l - 1]; w.addend = hbase + hp->g_off[hp->gb[l]];
+    if (pl.cg) { w.rh = m->Rh[l - 1]; w.partT2 = cm.ws->partT2 + cm.ws->t2_off[l]; }
+    launch_gemm_wsk<LAYOUT_RC>(w, st, K >= staged_mink);
+  }
+}
+
+// The whole R-chain in its hoisted form.  (projected Neumann's closing pass stops after the head: Rz(v_K) is in the accumulator then)
+int chain_hoisted(const bhg_mlp* m, const void* const* dir, const ChainMode& cm, const ChainPlan& pl, hipStream_t st, ChainState* cs) {
+  if (int rc = hoist_products(m, dir, cm, pl, st, cs)) return rc;
+  const int staged_mink = dbg(DBG_hoist_staged_mink, 256);
+  if (int rc = hoist_forward(m, dir, cm, pl, st, staged_mink, cs)) return rc;
+  if (int rc = hoist_head(m, dir, cm, pl, st, cs)) return rc;
+  if (!cm.stop_after_head) hoist_backward(m, cm, pl, st, staged_mink);
+  return BHG_OK;
+}
+
+// ---- R-forward (the classic chain: the direction products inside the chain's own GEMMs) ------------------------------------------
+void chain_forward(const bhg_mlp* m, const void* const* dir, const ChainMode& cm, const ChainPlan& pl, hipStream_t st, ChainState* cs) {
+  const int L = m->L, Bp = m->Bp, B = m->B;
+  for (int l = 0; l < L; ++l) {
     const int K = m->dims[l], N = m->dims[l + 1];
     const float* V = static_cast<const float*>(dir[2 * l]);
     const float* c = static_cast<const float*>(dir[2 * l + 1]);
-    if (head && l == L - 1) {
+    if (pl.head && l == L - 1) {
       launch_head_forward(st, Bp, l > 0 ? (const float*)m->Rh[l - 1] : nullptr, m->h[l], m->W[l], V, c, m->prob, m->sd,
                           m->Rd[l], K, N, B, HEAD_JVP, nullptr, nullptr, l > 0 ? (const float*)m->delta[l] : nullptr,
                           l > 0 ? (const float*)m->mask[l - 1] : nullptr, l > 0 ? m->Rd[l - 1] : nullptr,
-                          fuse_head ? &head_fuse : nullptr, cg ? cm.ws->partT1 : nullptr, cg ? cm.ws->partT2h : nullptr,
-                          cg ? cm.ws->rz : nullptr, cm.rzx_acc, cm.first);
+                          cs->fuse_head ? &cs->head_fuse : nullptr, pl.cg ? cm.ws->partT1 : nullptr, pl.cg ? cm.ws->partT2h : nullptr,
+                          pl.cg ? cm.ws->rz : nullptr, cm.rzx_acc, cm.first);
       continue;
     }
     GemmArgs a{};
@@ -1168,22 +1086,22 @@ int run_chain(const bhg_mlp* m, const void* const* dir, const ChainMode& cm, hip
     a.pairs = 1;
     if (l > 0) { a.pr[1] = {m->Rh[l - 1], m->W[l], K, K}; a.pairs = 2; }  // Rh_{l-1} W_l^T
     a.M = Bp; a.N = N; a.K = K;
-    const bool to_head = head && l == L - 2 && !no_fuse && (N & 3) == 0 && (size_t)N * sizeof(float) <= 64 * 1024;
-    if (wsk_wanted(wsk, a.pairs, K) && !to_head && l + 1 < L) {
+    const bool to_head = pl.head && l == L - 2 && !pl.no_fuse && (N & 3) == 0 && (size_t)N * sizeof(float) <= 64 * 1024;
+    if (wsk_wanted(pl.wsk, a.pairs, K) && !to_head && l + 1 < L) {
       // in-workgroup split-K: the 32 x 32 tile is summed, biased and masked before it leaves the chip (no reduce launch)
       WskArgs w{};
       w.pr[0] = a.pr[0]; w.pr[1] = a.pr[1]; w.pairs = a.pairs; w.M = Bp; w.N = N; w.K = K; w.B = B;
       w.bias = c; w.mask = m->mask[l]; w.out = m->Rh[l]; w.scal = cm.scal;
       if (wsk_eligible(w)) { launch_gemm_wsk<LAYOUT_KC>(w, st); continue; }
     }
-    a.splits = pick_splits((N + tn - 1) / tn, K, a.pairs);
+    a.splits = pick_splits((N + pl.tn - 1) / pl.tn, K, a.pairs);
     a.out = m->partial; a.ldo = N; a.out_rows = Bp;
-    launch_gemm<LAYOUT_KC, LAYOUT_KC>(a, tn, st);
+    launch_gemm<LAYOUT_KC, LAYOUT_KC>(a, pl.tn, st);
     const int slab = Bp * N;
     if (to_head) {
       // the head kernel of the next layer combines these slabs itself (one launch less on the chain)
-      head_fuse = {m->partial, a.splits, slab, c, m->mask[l], m->Rh[l]};
-      fuse_head = true;
+      cs->head_fuse = {m->partial, a.splits, slab, c, m->mask[l], m->Rh[l]};
+      cs->fuse_head = true;
     } else if (l + 1 < L) {
       launch_reduce_mask(st, m->partial, a.splits, slab, c, m->mask[l], m->Rh[l], Bp, N, B);
     } else {
@@ -1191,99 +1109,104 @@ int run_chain(const bhg_mlp* m, const void* const* dir, const ChainMode& cm, hip
                          a.splits, slab, c, m->prob, m->sd, m->Rd[l], Bp, N, B);
     }
   }
+}
 
-  // ---- weight-shaped outputs: launch descriptions ----------------------------------------------------------
-  auto outer_args = [&](int l, GemmArgs* ga, size_t* lds, bool* fast) {
-    const int Mo = m->dims[l + 1], No = m->dims[l];
-    const float* V = static_cast<const float*>(dir[2 * l]);
-    GemmArgs a{};
-    a.pr[0] = {m->Rd[l], m->h[l], Mo, No};              // Rd_l^T h_{l-1}
-    a.pairs = 1;
-    if (l > 0) { a.pr[1] = {m->delta[l], m->Rh[l - 1], Mo, No}; a.pairs = 2; }  // delta_l^T Rh_{l-1}
-    a.M = Mo; a.N = No; a.K = B;                        // only the B valid batch rows contribute
-    a.splits = 1;
-    a.out = cm.mode == FUSE_NONE ? static_cast<float*>(cm.out[2 * l]) : nullptr; a.ldo = No; a.out_rows = 0;
-    a.addend = rho2 != 0.f ? V : nullptr; a.addend_scale = rho2;
-    a.kstages = (B + kOH - 1) / kOH < 2 ? 2 : (B + kOH - 1) / kOH;   // <= 64 K rows per pipeline stage
-    const int Kh = (((B + a.kstages - 1) / a.kstages) + 1) & ~1;      // (see k_outer)
-    *lds = (size_t)Kh * (kTM + kTN) * sizeof(float);
-    const size_t lds_c = (size_t)kTM * kCPad * sizeof(float);
-    if (*lds < lds_c) *lds = lds_c;
-    bool f = Mo % kTM == 0 && No % kTN == 0 && (a.ldo & 3) == 0;
-    for (int i = 0; i < a.pairs; ++i) f = f && (a.pr[i].lda & 3) == 0 && (a.pr[i].ldb & 3) == 0;
-    if (cm.mode != FUSE_NONE) f = f && (cm.starts[2 * l] & 3) == 0;   // 16-B aligned state slices
-    const bool no_fast = dbg(DBG_mlp_no_fast, 0) != 0;
-    *fast = f && !no_fast;
-    *ga = a;
-  };
-  auto head_outer_args = [&](int l) {
-    HeadOuterArgs ha{};
-    ha.rd = m->Rd[l]; ha.h = m->h[l]; ha.delta = m->delta[l]; ha.Rh = l > 0 ? m->Rh[l - 1] : nullptr;
-    ha.V = static_cast<const float*>(dir[2 * l]); ha.rho2 = rho2;
-    ha.out = cm.mode == FUSE_NONE ? static_cast<float*>(cm.out[2 * l]) : nullptr;
-    ha.N = m->dims[l]; ha.C = m->dims[l + 1]; ha.B = B;
-    return ha;
-  };
-  auto launch_outer = [&](int l, hipStream_t s) {
-    const FuseArgs fz = fuse_at(2 * l, part_base_w[l]);
-    if (head && l == L - 1) {
-      const HeadOuterArgs ha = head_outer_args(l);
-      const dim3 grid((ha.N + 63) / 64, ha.C);
+// ---- weight-shaped outputs: launch descriptions ----------------------------------------------------------
+void outer_args(const bhg_mlp* m, const void* const* dir, const ChainMode& cm, const ChainPlan& pl, int l, GemmArgs* ga, size_t* lds,
+                bool* fast) {
+  const int B = m->B, Mo = m->dims[l + 1], No = m->dims[l];
+  const float* V = static_cast<const float*>(dir[2 * l]);
+  GemmArgs a{};
+  a.pr[0] = {m->Rd[l], m->h[l], Mo, No};              // Rd_l^T h_{l-1}
+  a.pairs = 1;
+  if (l > 0) { a.pr[1] = {m->delta[l], m->Rh[l - 1], Mo, No}; a.pairs = 2; }  // delta_l^T Rh_{l-1}
+  a.M = Mo; a.N = No; a.K = B;                        // only the B valid batch rows contribute
+  a.splits = 1;
+  a.out = cm.mode == FUSE_NONE ? static_cast<float*>(cm.out[2 * l]) : nullptr; a.ldo = No; a.out_rows = 0;
+  a.addend = pl.rho2 != 0.f ? V : nullptr; a.addend_scale = pl.rho2;
+  a.kstages = (B + kOH - 1) / kOH < 2 ? 2 : (B + kOH - 1) / kOH;   // <= 64 K rows per pipeline stage
+  const int Kh = (((B + a.kstages - 1) / a.kstages) + 1) & ~1;      // (see k_outer)
+  *lds = (size_t)Kh * (kTM + kTN) * sizeof(float);
+  const size_t lds_c = (size_t)kTM * kCPad * sizeof(float);
+  if (*lds < lds_c) *lds = lds_c;
+  bool f = Mo % kTM == 0 && No % kTN == 0 && (a.ldo & 3) == 0;
+  for (int i = 0; i < a.pairs; ++i) f = f && (a.pr[i].lda & 3) == 0 && (a.pr[i].ldb & 3) == 0;
+  if (cm.mode != FUSE_NONE) f = f && (cm.starts[2 * l] & 3) == 0;   // 16-B aligned state slices
+  const bool no_fast = dbg(DBG_mlp_no_fast, 0) != 0;
+  *fast = f && !no_fast;
+  *ga = a;
+}
+HeadOuterArgs head_outer_args(const bhg_mlp* m, const void* const* dir, const ChainMode& cm, const ChainPlan& pl, int l) {
+  HeadOuterArgs ha{};
+  ha.rd = m->Rd[l]; ha.h = m->h[l]; ha.delta = m->delta[l]; ha.Rh = l > 0 ? m->Rh[l - 1] : nullptr;
+  ha.V = static_cast<const float*>(dir[2 * l]); ha.rho2 = pl.rho2;
+  ha.out = cm.mode == FUSE_NONE ? static_cast<float*>(cm.out[2 * l]) : nullptr;
+  ha.N = m->dims[l]; ha.C = m->dims[l + 1]; ha.B = m->B;
+  return ha;
+}
+// H(W_l) in a launch of its own, on stream `s`
+void launch_outer(const bhg_mlp* m, const void* const* dir, const ChainMode& cm, const ChainPlan& pl, int l, hipStream_t s) {
+  const FuseArgs fz = fuse_at(cm, pl, 2 * l, pl.part_base_w[l]);
+  if (pl.head && l == pl.L - 1) {
+    const HeadOuterArgs ha = head_outer_args(m, dir, cm, pl, l);
+    const dim3 grid((ha.N + 63) / 64, ha.C);
 #define BHG_HEAD_OUTER(RH, MODE) hipLaunchKernelGGL((k_head_outer<RH, MODE>), grid, dim3(256), 0, s, ha, fz)
-      if (l > 0) {
-        if (cm.mode == FUSE_CG) BHG_HEAD_OUTER(true, FUSE_CG);
-        else if (cm.mode == FUSE_NEUMANN) BHG_HEAD_OUTER(true, FUSE_NEUMANN);
-        else BHG_HEAD_OUTER(true, FUSE_NONE);
-      } else {
-        if (cm.mode == FUSE_CG) BHG_HEAD_OUTER(false, FUSE_CG);
-        else if (cm.mode == FUSE_NEUMANN) BHG_HEAD_OUTER(false, FUSE_NEUMANN);
-        else BHG_HEAD_OUTER(false, FUSE_NONE);
-      }
-#undef BHG_HEAD_OUTER
-      return;
+    if (l > 0) {
+      if (cm.mode == FUSE_CG) BHG_HEAD_OUTER(true, FUSE_CG);
+      else if (cm.mode == FUSE_NEUMANN) BHG_HEAD_OUTER(true, FUSE_NEUMANN);
+      else BHG_HEAD_OUTER(true, FUSE_NONE);
+    } else {
+      if (cm.mode == FUSE_CG) BHG_HEAD_OUTER(false, FUSE_CG);
+      else if (cm.mode == FUSE_NEUMANN) BHG_HEAD_OUTER(false, FUSE_NEUMANN);
+      else BHG_HEAD_OUTER(false, FUSE_NONE);
     }
-    GemmArgs a; size_t lds; bool fast;
-    outer_args(l, &a, &lds, &fast);
-    dim3 grid((a.N + kTN - 1) / kTN, (a.M + kTM - 1) / kTM, 1);
+#undef BHG_HEAD_OUTER
+    return;
+  }
+  GemmArgs a; size_t lds; bool fast;
+  outer_args(m, dir, cm, pl, l, &a, &lds, &fast);
+  dim3 grid((a.N + kTN - 1) / kTN, (a.M + kTM - 1) / kTM, 1);
 #define BHG_OUTER(MODE)                                                                   \
   do {                                                                                    \
     if (fast) hipLaunchKernelGGL((k_outer<true, MODE>), grid, dim3(256), lds, s, a, fz);  \
     else hipLaunchKernelGGL((k_outer<false, MODE>), grid, dim3(256), lds, s, a, fz);      \
   } while (0)
-    if (cm.mode == FUSE_CG) BHG_OUTER(FUSE_CG);
-    else if (cm.mode == FUSE_NEUMANN) BHG_OUTER(FUSE_NEUMANN);
-    else BHG_OUTER(FUSE_NONE);
+  if (cm.mode == FUSE_CG) BHG_OUTER(FUSE_CG);
+  else if (cm.mode == FUSE_NEUMANN) BHG_OUTER(FUSE_NEUMANN);
+  else BHG_OUTER(FUSE_NONE);
 #undef BHG_OUTER
-  };
-  BiasArgs ba{};
+}
+// The bias outputs' launch and the step length's arguments: described once, used by whichever closing launch carries them.
+struct ChainOutputs {
+  BiasArgs ba; int bias_blk; FuseArgs bias_fz;
+  AlphaArgs aa;   // fused CG: the step length from the batch-sized factors (k_cg_alpha)
+};
+void describe_outputs(const bhg_mlp* m, const void* const* dir, const ChainMode& cm, const ChainPlan& pl, ChainOutputs* od) {
+  const int L = m->L, B = m->B;
+  *od = ChainOutputs{};
+  BiasArgs& ba = od->ba;
   int bias_blk = 0;
-  {
-    ba.L = L; ba.B = B; ba.rho2 = rho2;
-    for (int l = 0; l < L; ++l) {
-      ba.rd[l] = m->Rd[l];
-      ba.c[l] = static_cast<const float*>(dir[2 * l + 1]);
-      ba.out[l] = cm.mode == FUSE_NONE ? static_cast<float*>(cm.out[2 * l + 1]) : nullptr;
-      ba.foff[l] = cm.mode == FUSE_NONE ? 0 : cm.starts[2 * l + 1];
-      ba.n[l] = m->dims[l + 1];
-      ba.blk0[l] = bias_blk;
-      bias_blk += (m->dims[l + 1] + 63) / 64;
-    }
-    ba.blk0[L] = bias_blk;
-    // fully projected CG (k_proj_step): the first bias's slice of the direction lives in the slot dir[1] names
-    if (cg && cm.proj >= 2 && hp && proj_step_merged()) ba.d0 = static_cast<const float*>(dir[1]);
-    if (lin) ba.d1 = static_cast<const float*>(dir[3]);
+  ba.L = L; ba.B = B; ba.rho2 = pl.rho2;
+  for (int l = 0; l < L; ++l) {
+    ba.rd[l] = m->Rd[l];
+    ba.c[l] = static_cast<const float*>(dir[2 * l + 1]);
+    ba.out[l] = cm.mode == FUSE_NONE ? static_cast<float*>(cm.out[2 * l + 1]) : nullptr;
+    ba.foff[l] = cm.mode == FUSE_NONE ? 0 : cm.starts[2 * l + 1];
+    ba.n[l] = m->dims[l + 1];
+    ba.blk0[l] = bias_blk;
+    bias_blk += (m->dims[l + 1] + 63) / 64;
   }
-  FuseArgs bias_fz = fbase;
-  bias_fz.a = cm.fa; bias_fz.b = cm.fb; bias_fz.d = cm.fd; bias_fz.part_base = part_base_bias;   // offsets travel in ba.foff
+  ba.blk0[L] = bias_blk;
+  od->bias_blk = bias_blk;
+  // fully projected CG (k_proj_step): the first bias's slice of the direction lives in the slot dir[1] names
+  if (pl.cg && cm.proj >= 2 && pl.hp && proj_step_merged()) ba.d0 = static_cast<const float*>(dir[1]);
+  if (pl.lin) ba.d1 = static_cast<const float*>(dir[3]);
+  FuseArgs& bias_fz = od->bias_fz;
+  bias_fz = pl.fbase;
+  bias_fz.a = cm.fa; bias_fz.b = cm.fb; bias_fz.d = cm.fd; bias_fz.part_base = pl.part_base_bias;   // offsets travel in ba.foff
   if (cm.mode != FUSE_NONE && !cm.fb) bias_fz.x_mode = 1;
-  auto launch_bias = [&](hipStream_t s) {
-    if (cm.mode == FUSE_CG) hipLaunchKernelGGL(k_bias_hvp<FUSE_CG>, dim3(bias_blk), dim3(256), 0, s, ba, bias_fz);
-    else if (cm.mode == FUSE_NEUMANN) hipLaunchKernelGGL(k_bias_hvp<FUSE_NEUMANN>, dim3(bias_blk), dim3(256), 0, s, ba, bias_fz);
-    else hipLaunchKernelGGL(k_bias_hvp<FUSE_NONE>, dim3(bias_blk), dim3(256), 0, s, ba, bias_fz);
-  };
-
-  AlphaArgs aa{};   // fused CG: the step length from the batch-sized factors (k_cg_alpha)
-  if (cg) {
+  if (pl.cg) {
+    AlphaArgs& aa = od->aa;
     aa.partT1 = cm.ws->partT1; aa.partT2h = L >= 2 ? cm.ws->partT2h : nullptr; aa.B = B;
     aa.partT2 = cm.ws->partT2; aa.nT2 = cm.ws->nT2;
     aa.partPP = cm.partPP; aa.nPP = cm.nPP;
@@ -1292,20 +1215,29 @@ int run_chain(const bhg_mlp* m, const void* const* dir, const ChainMode& cm, hip
     aa.rz = cm.ws->rz; aa.rzx = cm.ws->rzx; aa.nrz = B * m->dims[L]; aa.first = cm.first; aa.kpar = cm.kpar;
     if (cm.gphase == 2) { aa.php_ext = cm.php; aa.inv_world = cm.inv_world; }
   }
-  // ---- R-backward (main stream) [overlapped with the weight-shaped outputs on the side stream unless FUSE_CG] ----------
-  for (int l = L - 1; l >= 1 && !hp && do_chain; --l) {
-    if (!single) {   // Rd_l is ready on the main stream here: hand H(W_l) to the side stream
-      if (no_side) {
-        launch_outer(l, st);
+}
+void launch_bias(const ChainMode& cm, const ChainOutputs& od, hipStream_t s) {
+  if (cm.mode == FUSE_CG) hipLaunchKernelGGL(k_bias_hvp<FUSE_CG>, dim3(od.bias_blk), dim3(256), 0, s, od.ba, od.bias_fz);
+  else if (cm.mode == FUSE_NEUMANN) hipLaunchKernelGGL(k_bias_hvp<FUSE_NEUMANN>, dim3(od.bias_blk), dim3(256), 0, s, od.ba, od.bias_fz);
+  else hipLaunchKernelGGL(k_bias_hvp<FUSE_NONE>, dim3(od.bias_blk), dim3(256), 0, s, od.ba, od.bias_fz);
+}
+
+// ---- R-backward (main stream) [overlapped with the weight-shaped outputs on the side stream unless `single`] ----------
+int chain_backward(const bhg_mlp* m, const void* const* dir, const ChainMode& cm, const ChainPlan& pl, hipStream_t st) {
+  const int L = m->L, Bp = m->Bp, B = m->B;
+  for (int l = L - 1; l >= 1; --l) {
+    if (!pl.single) {   // Rd_l is ready on the main stream here: hand H(W_l) to the side stream
+      if (pl.no_side) {
+        launch_outer(m, dir, cm, pl, l, st);
       } else {
-        BHG_HIP_CHECK(hipEventRecord(ss.ev_rd[l], st));
-        BHG_HIP_CHECK(hipStreamWaitEvent(side, ss.ev_rd[l], 0));
-        launch_outer(l, side);
+        BHG_HIP_CHECK(hipEventRecord(pl.ss->ev_rd[l], st));
+        BHG_HIP_CHECK(hipStreamWaitEvent(pl.ss->side, pl.ss->ev_rd[l], 0));
+        launch_outer(m, dir, cm, pl, l, pl.ss->side);
       }
     }
     const int K = m->dims[l + 1], N = m->dims[l];  // Rd_{l-1}[Bp][N] = delta_l[Bp][K] V_l[K][N] + Rd_l W_l
     const float* V = static_cast<const float*>(dir[2 * l]);
-    if (head && l == L - 1) continue;  // Rd_{L-2} was produced by the fused k_head_forward
+    if (pl.head && l == L - 1) continue;  // Rd_{L-2} was produced by the fused k_head_forward
     GemmArgs a{};
     a.pr[0] = {m->delta[l], V, K, N};
     if (cm.lazy) a.pr[0] = {m->delta[l], cm.fa + cm.starts[2 * l], K, N, cm.fd + cm.starts[2 * l], 1};
@@ -1313,29 +1245,29 @@ int run_chain(const bhg_mlp* m, const void* const* dir, const ChainMode& cm, hip
     a.pr[1] = {m->Rd[l], m->W[l], K, N};
     a.pairs = 2;
     a.M = Bp; a.N = N; a.K = K;
-    const bool wsk_short = wsk_wanted(wsk, 2, K);
-    if (wsk_short || (wsk == 3 && !cm.lazy)) {   // mode 3: long R-backward reductions in the LDS-staged form (no lazy direction)
+    const bool wsk_short = wsk_wanted(pl.wsk, 2, K);
+    if (wsk_short || (pl.wsk == 3 && !cm.lazy)) {   // mode 3: long R-backward reductions in the LDS-staged form (no lazy direction)
       WskArgs w{};
       w.pr[0] = a.pr[0]; w.pr[1] = a.pr[1]; w.pairs = 2; w.M = Bp; w.N = N; w.K = K; w.B = B;
       w.mask = m->mask[l - 1]; w.out = m->Rd[l - 1]; w.scal = cm.scal;
-      if (cg) { w.rh = m->Rh[l - 1]; w.partT2 = cm.ws->partT2 + cm.ws->t2_off[l]; }
+      if (pl.cg) { w.rh = m->Rh[l - 1]; w.partT2 = cm.ws->partT2 + cm.ws->t2_off[l]; }
       // (the T2 partial slots were carved for the reduce launch's block count: one per 1024 outputs, like the tiles here)
-      if (wsk_eligible(w) && (!cg || (Bp / 32) * (N / 32) == reduce_blocks(Bp * N, N))) {
+      if (wsk_eligible(w) && (!pl.cg || (Bp / 32) * (N / 32) == reduce_blocks(Bp * N, N))) {
         launch_gemm_wsk<LAYOUT_RC>(w, st, !wsk_short);
         continue;
       }
     }
-    a.splits = pick_splits((N + tn - 1) / tn, K, 2);
-    if (cg) {
+    a.splits = pick_splits((N + pl.tn - 1) / pl.tn, K, 2);
+    if (pl.cg) {
       // the two products land in separate slabs (each workgroup takes twice the K range of ONE pair: same count and
       // length of K loops), so the reduce can dot delta_l V_l with Rh_{l-1} on its way: T2_l
       if (a.splits < 2) a.splits = 2;
       a.pair_split = a.splits / 2;
     }
     a.out = m->partial; a.ldo = N; a.out_rows = Bp;
-    launch_gemm<LAYOUT_KC, LAYOUT_RC>(a, tn, st);
+    launch_gemm<LAYOUT_KC, LAYOUT_RC>(a, pl.tn, st);
     const int slab = Bp * N;
-    if (cg) {
+    if (pl.cg) {
       const int blocks = reduce_blocks(slab, N);
       double* pt2 = cm.ws->partT2 + cm.ws->t2_off[l];
       if ((N & 3) == 0)
@@ -1348,279 +1280,328 @@ int run_chain(const bhg_mlp* m, const void* const* dir, const ChainMode& cm, hip
       launch_reduce_mask(st, m->partial, a.splits, slab, nullptr, m->mask[l - 1], m->Rd[l - 1], Bp, N, B);
     }
   }
+  return BHG_OK;
+}
 
-  if (cg && cm.gphase == 1) {   // global-batch CG: the chain is done; this rank's p.H_data p for the caller's all-reduce
-    hipLaunchKernelGGL(k_php_local, dim3(1), dim3(kThreads), 0, st, aa, cm.php);
-    BHG_HIP_CHECK(hipGetLastError());
-    return BHG_OK;
+// ---- the closing launches of a `single` pass ------------------------------------------------------------------------------------
+// projected forms: G(raw) of this iteration for the next one's recurrences (k_graw / k_grawk), the small slices' outputs riding along
+int close_graw(const bhg_mlp* m, const void* const* dir, const ChainMode& cm, const ChainPlan& pl, const ChainOutputs& od, hipStream_t st,
+               const ChainState& cs, bool small_in_graw, bool alpha_in_gram, bool alpha_in_hoist) {
+  const int L = m->L, Bp = m->Bp, B = m->B;
+  const HoistPlan* hp = pl.hp;
+  float* hbase = pl.hoist;
+#ifndef BHG_AB
+  // (product: the Gram products rode in the chain launches and the closing launch is k_graw / k_grawk in EVERY plan — the hoist plan
+  //  carves the packed operands whenever it is taken, the padded batch is a multiple of 128; round 3's Gram launch and its k_hoist
+  //  form of the G(raw) products live on in the measurement build)
+  BHG_REQUIRE(pl.graw2, "internal: the packed closing launch must apply");
+#else
+  WskGroupArgs g{};
+  int blk = 0;
+  for (int l = 1; l + 1 < L && !pl.gram_in_chain; ++l) {
+    const int st_ = gram_ksplit(m->dims[l]), se_ = gram_ksplit(m->dims[l + 1]);
+    g.p[g.n] = {m->h[l], m->Rh[l - 1], hbase + hp->tslab_off[l], Bp, Bp, m->dims[l], B, st_};       // T_l = h_l Rh_{l-1}^T
+    g.blk0[g.n++] = blk; blk += (Bp / 32) * (Bp / 32) * st_;
+    g.p[g.n] = {m->delta[l], m->Rd[l], hbase + hp->eslab_off[l], Bp, Bp, m->dims[l + 1], B, se_};   // E_l = delta_l Rd_l^T
+    g.blk0[g.n++] = blk; blk += (Bp / 32) * (Bp / 32) * se_;
   }
-  if (single) {
-    // ---- the step length, then every weight-shaped output with the recurrence in its epilogue
-    // projected CG, not the last iteration: the step length rides in the launch of this iteration's Gram products
-    // (projected Neumann: EVERY iteration — the closing pass needs G(raw) of the last one)
-    const bool alpha_alone = dbg(DBG_proj_alpha_alone, 0) != 0 || gram_in_chain;   // A/B (packed Gram products: no Gram launch to ride in)
-    const bool small_alone = dbg(DBG_proj_small_alone, 0) != 0;   // A/B
-    const bool small_in_graw = proj_iter && (cm.proj >= 2 || !cg) && !small_alone;
-    // fully projected CG with the Gram products in the chain launches: nothing is left between the chain and the G(raw) launch but
-    // the step length — and its only readers inside that launch are the small slices' blocks, which recompute it from the same
-    // partials (alpha_compute, bit-identical in every block); the first of them publishes it and completes Rz(x)
-    const bool alpha_in_hoist = cg && proj_iter && cm.proj >= 2 && small_in_graw && gram_in_chain && cm.gphase == 0 &&
-                                dbg(DBG_alpha_in_hoist, 1) != 0;
-    const bool alpha_in_gram = cg && proj_iter && !alpha_alone;
-    if (cg && !alpha_in_gram && !alpha_in_hoist) hipLaunchKernelGGL(k_cg_alpha, dim3(1), dim3(kThreads), 0, st, aa);
-    if (cg && cm.skip_outputs) {   // last iteration of a solve without a solution vector: r', p' and x are all dead
+  for (int l = 0; cm.first && !cs.sd_in_chain && l + 1 < L; ++l) {   // once per solve: S_l, D_l
+    g.p[g.n] = {m->h[l], m->h[l], hbase + hp->s_off[l], Bp, Bp, m->dims[l], B, 1};
+    g.blk0[g.n++] = blk; blk += (Bp / 32) * (Bp / 32);
+    if (l >= 1) {
+      g.p[g.n] = {m->delta[l], m->delta[l], hbase + hp->d_off[l], Bp, Bp, m->dims[l + 1], B, 1};
+      g.blk0[g.n++] = blk; blk += (Bp / 32) * (Bp / 32);
+    }
+  }
+  g.blk0[g.n] = blk;
+  if (alpha_in_gram) { g.do_alpha = 1; g.alpha = od.aa; }
+  if (blk + (alpha_in_gram ? 1 : 0) > 0) launch_wsk_group(g, blk + (alpha_in_gram ? 1 : 0), st);
+#endif
+  const bool full = pl.cg && cm.proj >= 2;   // fully projected CG: r.raw, p.raw, raw.raw from batch-sized arrays (k_pstep)
+  SmallOutArgs so{};
+  int small_blocks = 0;
+  if (small_in_graw) {   // the small slices' outputs (head weight, biases) with their CG epilogue: block classes of the closing launch
+    so.head = head_outer_args(m, dir, cm, pl, L - 1);
+    so.hf = fuse_at(cm, pl, 2 * (L - 1), pl.part_base_w[L - 1]);
+    so.head_gx = (so.head.N + 63) / 64;
+    so.head_blocks = so.head_gx * so.head.C;
+    so.head_has_rh = L > 1;
+    so.ba.L = od.ba.L; so.ba.B = od.ba.B; so.ba.rho2 = od.ba.rho2;
+    for (int l = 0; l < L; ++l) {
+      so.ba.rd[l] = od.ba.rd[l]; so.ba.c[l] = od.ba.c[l]; so.ba.out[l] = od.ba.out[l]; so.ba.n[l] = od.ba.n[l]; so.ba.blk0[l] = od.ba.blk0[l];
+      so.ba.foff[l] = od.ba.foff[l];
+    }
+    so.ba.blk0[L] = od.ba.blk0[L];
+    so.ba.d0 = od.ba.d0; so.ba.d1 = pl.lin ? static_cast<const float*>(dir[3]) : nullptr;
+    so.bf = od.bias_fz;
+    so.bias_blocks = od.bias_blk;
+    small_blocks = so.head_blocks + od.bias_blk;
+  }
+  if (pl.graw2) {   // round 4: packed Gram matrices -> k_graw (64 x 32 tiles, inner products in the tile epilogue, one slab per product)
+    GrawArgs ka{};
+    const int ct = graw_cols(hp, Bp);
+    // CT = 32: the small slices' blocks lead the grid; CT = 64: the tiles do (one CU each), the small blocks fill second slots
+    const bool small_first = ct == 32;
+    int gb = small_first ? (small_blocks + 15) & ~15 : 0;   // (every table entry a multiple of 16)
+    int real_tiles = 0;
+    for (int i = 0; i < hp->n; ++i) {
+      const int l = hp->layer[i];
+      GrawProb& q = ka.p[i];
+      if (!hp->bwd[i]) {   // Gf_l(raw) = S_l Rd_l + T_l delta_l
+        q.A1 = hbase + hp->sp_off[l]; q.B1 = m->Rd[l];
+        if (l >= 1) { q.A2 = hbase + hp->tslabp_off[l] + ((pl.lin && l == 1) ? (size_t)cm.kpar * Bp * Bp : 0); q.B2 = m->delta[l]; }
+      } else {             // Gb_l(raw) = E_l h_l + D_l Rh_{l-1}
+        q.A1 = hbase + hp->eslabp_off[l]; q.B1 = m->h[l];
+        q.A2 = hbase + hp->dp_off[l]; q.B2 = (pl.vnew && l == 1) ? pl.rh0_slot(cm.nk) : m->Rh[l - 1];
+      }
+      q.Gr = q.Gp = q.B1;   // (always loadable)
+      if (pl.vnew) q.Gr = q.Gp = hbase + hp->g_off[i];   // G(v): updated in place by the tile that owns the element
+      if (full) {           // the inner products' partner: Rd_l (= B1) forward, Rh_{l-1} (= B2) backward
+        q.Gr = hbase + hp->gr_off[i];
+        q.Gp = (pl.lin && i == hp->gf[1]) ? pl.gp1(cm.kpar) : ((pl.lin_head && i == hp->gf[L - 2]) ? pl.gp2(cm.kpar) : hbase + hp->g_off[i]);
+        q.dots = hp->bwd[i] ? 2 : 1;
+      }
+      q.Graw = hbase + hp->graw_off[i]; q.N = hp->N[i];
+      q.pb0 = real_tiles;
+      real_tiles += (Bp / 64) * (hp->N[i] / ct);
+      // every column tile with all its Bp / 64 row groups: groups of one tile 8 blocks apart (one XCD), column tiles padded to 8
+      ka.blk0[i] = gb; gb += (Bp / 64) * (((hp->N[i] / ct) + 7) & ~7);
+    }
+    ka.blk0[hp->n] = gb; ka.tile_end = gb;
+    BHG_REQUIRE(real_tiles == graw_tile_count(hp, Bp) && real_tiles <= hp->graw_tiles, "tile count of k_graw and of the plan disagree");
+    ka.n = hp->n; ka.Bp = Bp; ka.B = B;
+    ka.part = cm.ws->part_graw; ka.npart = real_tiles;
+    ka.small_blocks = small_blocks; ka.so = so;
+    ka.small0 = small_first ? 0 : gb;
+    if (!small_first) gb += small_blocks;
+    if (alpha_in_hoist) { ka.do_alpha = 1; ka.alpha = od.aa; }
+    BHG_REQUIRE(!pl.rnew || (alpha_in_hoist && full), "k_graw was to apply the residual step but has no step length");
+    ka.rnew = (pl.rnew || pl.vnew) ? 1 : 0;
+    if (pl.vnew) {   // Rh_0(v') for the next iteration's first product (packed) and for its k_graw (row-major, the other slot)
+      ka.nalpha = cm.alpha; ka.nshift = cm.shift;
+      ka.rh0p = cm.ws->Rhp[0]; ka.rh0 = pl.rh0_slot(cm.nk + 1); ka.mask0 = m->mask[0];
+      ka.rb0 = ka.pb0s = static_cast<const float*>(dir[1]); ka.rh0_prod = hp->gf[0];
+    }
+    if (pl.lin) {   // Rh_0(r') for the next iteration's first product; beta's granules cleared for its publication
+      ka.rh0p = hbase + hp->rh0rp_off; ka.mask0 = m->mask[0]; ka.rb0 = hbase + hp->rb0c_off;
+      ka.pb0s = static_cast<const float*>(dir[1]); ka.gran = cm.ws->gran; ka.rh0_prod = hp->gf[0];
+    }
+#ifdef BHG_AB   // (debug key graw_cols = 64)
+    if (ct == 64) {
+      if (pl.cg) hipLaunchKernelGGL(k_graw64<FUSE_CG>, dim3(gb), dim3(64 * kGrawWaves), 0, st, ka);
+      else hipLaunchKernelGGL(k_graw64<FUSE_NEUMANN>, dim3(gb), dim3(64 * kGrawWaves), 0, st, ka);
+    } else
+#endif
+    if (Bp != 128) {   // the K-looped instance (32-column tiles)
+      if (pl.cg) hipLaunchKernelGGL(k_grawk<FUSE_CG>, dim3(gb), dim3(64 * kGrawWaves), 0, st, ka);
+      else hipLaunchKernelGGL(k_grawk<FUSE_NEUMANN>, dim3(gb), dim3(64 * kGrawWaves), 0, st, ka);
+    } else if (pl.cg) hipLaunchKernelGGL(k_graw<FUSE_CG>, dim3(gb), dim3(64 * kGrawWaves), 0, st, ka);
+    else hipLaunchKernelGGL(k_graw<FUSE_NEUMANN>, dim3(gb), dim3(64 * kGrawWaves), 0, st, ka);
+  }
+#ifdef BHG_AB
+  HoistArgs ga{};
+  int gblk = 0;
+  const int ntm = Bp / kTM;
+  for (int i = 0; i < hp->n && !pl.graw2; ++i) {
+    const int l = hp->layer[i];
+    HoistProb& q = ga.p[i];
+    if (!hp->bwd[i]) {   // Gf_l(raw) = S_l Rd_l + T_l delta_l
+      q.A = hbase + hp->s_off[l]; q.Bm = m->Rd[l];
+      if (l >= 1) { q.A2 = hbase + hp->tslab_off[l]; q.B2m = m->delta[l]; q.a2_slabs = pl.gram_slabs(m->dims[l]); }
+    } else {             // Gb_l(raw) = E_l h_l + D_l Rh_{l-1}
+      q.A = hbase + hp->eslab_off[l]; q.Bm = m->h[l]; q.a_slabs = pl.gram_slabs(m->dims[l + 1]);
+      q.A2 = hbase + hp->d_off[l]; q.B2m = m->Rh[l - 1];
+    }
+    q.slabs = hbase + hp->graw_off[i];
+    q.a_slab_stride = Bp * Bp;
+    if (full) q.X = hp->bwd[i] ? (const float*)m->Rh[l - 1] : (const float*)m->Rd[l];   // raw.raw's share: <X, G(raw)>
+    q.K = Bp; q.N = hp->N[i]; q.splits = (q.A2 && graw_split()) ? 2 : 1; q.rc = 1; q.lda = Bp; q.ldb = hp->N[i];
+    ga.blk0[i] = gblk; gblk += (hp->N[i] / 32) * ntm * q.splits;
+  }
+  ga.blk0[hp->n] = gblk;
+  ga.n = hp->n; ga.Bp = Bp; ga.gemm_blocks = gblk; ga.do_beta = 0;
+  if (full && !pl.graw2) {   // the projected inner products r.raw, p.raw ride behind the tiles
+    int dblk = 0, nd = 0;
+    for (int i = 0; i < hp->n; ++i) {
+      const int l = hp->layer[i];
+      ga.dp[nd] = {hbase + hp->gr_off[i], hbase + hp->g_off[i], hp->bwd[i] ? (const float*)m->Rh[l - 1] : (const float*)m->Rd[l], hp->N[i]};
+      ga.dblk0[nd++] = dblk; dblk += dot_blocks_of(Bp * (hp->N[i] / 4));
+    }
+    ga.dblk0[nd] = dblk;
+    ga.nd = nd; ga.dot_blocks = dblk; ga.B = B; ga.part_dot = cm.ws->part_dot; ga.part_raw = cm.ws->part_raw;
+    BHG_REQUIRE(gblk == graw_blocks(hp, Bp), "tile count of the G(raw) launch and of its raw.raw partials disagree");
+    BHG_REQUIRE(dblk == hp->dot_blocks, "dot block count of the plan and of the launch disagree");
+  }
+  if (small_in_graw) {
+    ga.so = so;
+    ga.small_blocks = small_blocks;
+    if (alpha_in_hoist) { ga.do_alpha = 1; ga.alpha = od.aa; }
+  }
+  if (pl.graw2) {
+  } else if (pl.cg) hipLaunchKernelGGL(k_hoist<FUSE_CG>, dim3(gblk + ga.dot_blocks + ga.small_blocks), dim3(256), 0, st, ga);
+  else hipLaunchKernelGGL(k_hoist<FUSE_NEUMANN>, dim3(gblk + ga.dot_blocks + ga.small_blocks), dim3(256), 0, st, ga);
+#endif
+  return BHG_OK;
+}
+
+// the weight-shaped outputs with the recurrence in their epilogue: whatever the G(raw) launch did not carry
+int close_outputs(const bhg_mlp* m, const void* const* dir, const ChainMode& cm, const ChainPlan& pl, const ChainOutputs& od, hipStream_t st,
+                  bool small_in_graw) {
+  const int L = m->L;
+  const HoistPlan* hp = pl.hp;
+  // one launch for all outputs when every MFMA layer is all-interior
+  // (fully projected CG: the MFMA layers' slices of r and p are not materialised — only the small slices' blocks launch)
+  const bool proj_full = hp && ((pl.cg && cm.proj >= 2) || (!pl.cg && cm.proj));   // no N-sized state: only the small slices' blocks
+  const int n_mfma = proj_full ? 0 : (pl.head ? L - 1 : L);
+  OuterAllArgs oa{};
+  bool all_fast = !pl.no_outer_all && n_mfma <= kOuterAllMax && pl.head;
+  size_t lds_max = 0;
+  int order[BHG_MLP_MAX_LAYERS];
+  // dispatch order = tile order: the layer with the most tiles first (measured 260 vs 256 steps/s against
+  // "two-pair tiles first"; BHG_OUTER_ORDER_BY_WORK selects the latter)
+  const bool work_first = dbg(DBG_outer_order_by_work, 0) != 0;
+  auto weight = [&](int l) { return !work_first ? (double)outer_blocks(m, l, pl.head) : (l > 0 ? 2.0 : 1.0) * 1e9 + outer_blocks(m, l, pl.head); };
+  for (int i = 0; i < n_mfma; ++i) order[i] = i;
+  for (int i = 1; i < n_mfma; ++i)   // insertion sort, descending
+    for (int j = i; j > 0 && weight(order[j]) > weight(order[j - 1]); --j) { int t = order[j]; order[j] = order[j - 1]; order[j - 1] = t; }
+  int blk = 0;
+  for (int i = 0; i < n_mfma && all_fast; ++i) {
+    const int l = order[i];
+    size_t lds; bool fast;
+    outer_args(m, dir, cm, pl, l, &oa.g[i], &lds, &fast);
+    all_fast = all_fast && fast;
+    if (lds > lds_max) lds_max = lds;
+    oa.f[i] = fuse_at(cm, pl, 2 * l, pl.part_base_w[l]);
+    oa.gx[i] = (oa.g[i].N + kTN - 1) / kTN;
+    oa.blk0[i] = blk;
+    blk += outer_blocks(m, l, pl.head);
+  }
+  if (small_in_graw) {
+    // (the small slices' blocks already ran in k_hoist's launch)
+  } else if (all_fast) {
+    oa.n = n_mfma;
+    oa.blk0[n_mfma] = blk;
+    oa.head = head_outer_args(m, dir, cm, pl, L - 1);
+    oa.hf = fuse_at(cm, pl, 2 * (L - 1), pl.part_base_w[L - 1]);
+    oa.head_gx = (oa.head.N + 63) / 64;
+    oa.head_blocks = oa.head_gx * oa.head.C;
+    oa.head_has_rh = L > 1;
+    oa.bf = od.bias_fz;
+    const int total = blk + oa.head_blocks + od.bias_blk;
+    if (lds_max < (size_t)kTM * kCPad * sizeof(float)) lds_max = (size_t)kTM * kCPad * sizeof(float);
+    const bool no_pre = dbg(DBG_outer_no_pre, 0) != 0;   // A/B runs
+    (void)no_pre;
+    const int stagger = dbg(DBG_outer_stagger, 1);
+    oa.stagger = stagger;
+#ifdef BHG_AB
+    if (no_pre) {
+      if (pl.cg) hipLaunchKernelGGL((k_outer_all<FUSE_CG, false>), dim3(total), dim3(256), lds_max, st, oa, od.ba);
+      else hipLaunchKernelGGL((k_outer_all<FUSE_NEUMANN, false>), dim3(total), dim3(256), lds_max, st, oa, od.ba);
+    } else
+#endif
+    {
+      if (pl.cg) hipLaunchKernelGGL((k_outer_all<FUSE_CG, true>), dim3(total), dim3(256), lds_max, st, oa, od.ba);
+      else hipLaunchKernelGGL((k_outer_all<FUSE_NEUMANN, true>), dim3(total), dim3(256), lds_max, st, oa, od.ba);
+    }
+  } else {
+    for (int l = L - 1; l >= 0; --l) launch_outer(m, dir, cm, pl, l, st);
+    launch_bias(cm, od, st);
+  }
+#ifdef BHG_AB
+  if (proj_full && pl.cg && !proj_step_merged()) {   // r'.r', beta, p'.p' of the iteration from batch-sized quantities (k_proj_scalars)
+    BHG_REQUIRE(all_fast || small_in_graw, "the fully projected CG solver needs the single-launch output path");
+    ProjScalArgs sa{};
+    sa.part_dot = cm.ws->part_dot; sa.dot_blocks = hp->dot_blocks;
+    sa.part_raw = cm.ws->part_raw; sa.raw_blocks = graw_blocks(hp, m->Bp);
+    if (pl.graw_single) {
+      const int gt = graw_tile_count(hp, m->Bp);
+      sa.part_dot = cm.ws->part_graw; sa.dot_blocks = gt;
+      sa.part_raw = cm.ws->part_graw + 2 * (size_t)gt; sa.raw_blocks = gt;
+    }
+    sa.part = cm.partRR_new; sa.part_stride = cm.ws->nRR;
+    sa.off0 = pl.part_base_w[L - 1]; sa.n0 = outer_blocks(m, L - 1, pl.head); sa.off1 = pl.part_base_bias; sa.n1 = od.bias_blk;
+    sa.r_small = cm.beta->r; sa.p_small = cm.beta->p; sa.snt = cm.beta->nt;
+    for (int t = 0; t < cm.beta->nt; ++t) { sa.soff[t] = cm.beta->off[t]; sa.slen[t] = cm.beta->len[t]; }
+    sa.scal = cm.scal; sa.pscal = cm.ws->pscal; sa.shift = cm.shift; sa.first = cm.first; sa.kpar = cm.kpar;
+    int small_total = 0;
+    for (int t = 0; t < cm.beta->nt; ++t) small_total += cm.beta->len[t];
+    const int sgrid = small_total > 0 ? (small_total + kThreads - 1) / kThreads : 1;
+    hipLaunchKernelGGL(k_proj_scalars, dim3(sgrid), dim3(kThreads), 0, st, sa);
+  }
+#endif
+  return BHG_OK;
+}
+
+// the step length, then every weight-shaped output with the recurrence in its epilogue
+int chain_close(const bhg_mlp* m, const void* const* dir, const ChainMode& cm, const ChainPlan& pl, const ChainOutputs& od, hipStream_t st,
+                const ChainState& cs) {
+  // projected CG, not the last iteration: the step length rides in the launch of this iteration's Gram products
+  // (projected Neumann: EVERY iteration — the closing pass needs G(raw) of the last one)
+  const bool alpha_alone = dbg(DBG_proj_alpha_alone, 0) != 0 || pl.gram_in_chain;   // A/B (packed Gram products: no Gram launch to ride in)
+  const bool small_alone = dbg(DBG_proj_small_alone, 0) != 0;   // A/B
+  const bool small_in_graw = pl.proj_iter && (cm.proj >= 2 || !pl.cg) && !small_alone;
+  // fully projected CG with the Gram products in the chain launches: nothing is left between the chain and the G(raw) launch but
+  // the step length — and its only readers inside that launch are the small slices' blocks, which recompute it from the same
+  // partials (alpha_compute, bit-identical in every block); the first of them publishes it and completes Rz(x)
+  const bool alpha_in_hoist = pl.cg && pl.proj_iter && cm.proj >= 2 && small_in_graw && pl.gram_in_chain && cm.gphase == 0 &&
+                              dbg(DBG_alpha_in_hoist, 1) != 0;
+  const bool alpha_in_gram = pl.cg && pl.proj_iter && !alpha_alone;
+  if (pl.cg && !alpha_in_gram && !alpha_in_hoist) hipLaunchKernelGGL(k_cg_alpha, dim3(1), dim3(kThreads), 0, st, od.aa);
+  if (pl.cg && cm.skip_outputs) return BHG_OK;   // last iteration of a solve without a solution vector: r', p' and x are all dead
+  if (pl.proj_iter)
+    if (int rc = close_graw(m, dir, cm, pl, od, st, cs, small_in_graw, alpha_in_gram, alpha_in_hoist)) return rc;
+  return close_outputs(m, dir, cm, pl, od, st, small_in_graw);
+}
+
+// One Hessian-vector product of the MLP in direction `dir`, its weight-shaped outputs stored (FUSE_NONE) or consumed
+// by the CG / Neumann recurrence while still on chip (fused modes).  On return everything is ordered on `st`.
+//   FUSE_NONE / FUSE_NEUMANN: the outputs of layer l only need Rd_l and Rh_{l-1}, so they run on a library-owned side
+//     stream beside the R-backward chain (event fork / join).
+//   FUSE_CG: the fused epilogues need the step length, which needs the whole R-chain (T2 comes out of the R-backward
+//     reduces) — so there is nothing to overlap: ONE stream, no events (an event record costs the stream a ~4 us
+//     bubble, a cross-stream wait ~8 us: measured, rocprofv3 timelines in profiles/), and ONE launch for all
+//     weight-shaped outputs.
+// Read top to bottom this is the launch sequence of one HVP; what each stage depends on is in its arguments (ChainPlan, ChainState).
+int run_chain(const bhg_mlp* m, const void* const* dir, const ChainMode& cm, hipStream_t st) {
+  ChainPlan pl;
+  if (int rc = plan_chain(m, cm, &pl)) return rc;
+  ChainState cs;
+  if (pl.do_chain && pl.hp) {
+    if (int rc = chain_hoisted(m, dir, cm, pl, st, &cs)) return rc;
+    if (cm.stop_after_head) {   // (projected Neumann's closing pass: Rz(v_K) is in the accumulator now)
       BHG_HIP_CHECK(hipGetLastError());
       return BHG_OK;
     }
-    if (proj_iter) {   // projected CG: G(raw) of this iteration for the next one's recurrences
-      float* hbase = cm.ws->hoist;
-#ifndef BHG_AB
-      // (product: the Gram products rode in the chain launches and the closing launch is k_graw / k_grawk in EVERY plan — the hoist plan
-      //  carves the packed operands whenever it is taken, the padded batch is a multiple of 128; round 3's Gram launch and its k_hoist
-      //  form of the G(raw) products live on in the measurement build)
-      BHG_REQUIRE(graw2, "internal: the packed closing launch must apply");
-#else
-      WskGroupArgs g{};
-      int blk = 0;
-      for (int l = 1; l + 1 < L && !gram_in_chain; ++l) {
-        const int st_ = gram_ksplit(m->dims[l]), se_ = gram_ksplit(m->dims[l + 1]);
-        g.p[g.n] = {m->h[l], m->Rh[l - 1], hbase + hp->tslab_off[l], Bp, Bp, m->dims[l], B, st_};       // T_l = h_l Rh_{l-1}^T
-        g.blk0[g.n++] = blk; blk += (Bp / 32) * (Bp / 32) * st_;
-        g.p[g.n] = {m->delta[l], m->Rd[l], hbase + hp->eslab_off[l], Bp, Bp, m->dims[l + 1], B, se_};   // E_l = delta_l Rd_l^T
-        g.blk0[g.n++] = blk; blk += (Bp / 32) * (Bp / 32) * se_;
-      }
-      for (int l = 0; cm.first && !sd_in_chain && l + 1 < L; ++l) {   // once per solve: S_l, D_l
-        g.p[g.n] = {m->h[l], m->h[l], hbase + hp->s_off[l], Bp, Bp, m->dims[l], B, 1};
-        g.blk0[g.n++] = blk; blk += (Bp / 32) * (Bp / 32);
-        if (l >= 1) {
-          g.p[g.n] = {m->delta[l], m->delta[l], hbase + hp->d_off[l], Bp, Bp, m->dims[l + 1], B, 1};
-          g.blk0[g.n++] = blk; blk += (Bp / 32) * (Bp / 32);
-        }
-      }
-      g.blk0[g.n] = blk;
-      if (alpha_in_gram) { g.do_alpha = 1; g.alpha = aa; }
-      if (blk + (alpha_in_gram ? 1 : 0) > 0) launch_wsk_group(g, blk + (alpha_in_gram ? 1 : 0), st);
-#endif
-      const bool full = cg && cm.proj >= 2;   // fully projected CG: r.raw, p.raw, raw.raw from batch-sized arrays (k_pstep)
-      SmallOutArgs so{};
-      int small_blocks = 0;
-      if (small_in_graw) {   // the small slices' outputs (head weight, biases) with their CG epilogue: block classes of the closing launch
-        so.head = head_outer_args(L - 1);
-        so.hf = fuse_at(2 * (L - 1), part_base_w[L - 1]);
-        so.head_gx = (so.head.N + 63) / 64;
-        so.head_blocks = so.head_gx * so.head.C;
-        so.head_has_rh = L > 1;
-        so.ba.L = ba.L; so.ba.B = ba.B; so.ba.rho2 = ba.rho2;
-        for (int l = 0; l < L; ++l) {
-          so.ba.rd[l] = ba.rd[l]; so.ba.c[l] = ba.c[l]; so.ba.out[l] = ba.out[l]; so.ba.n[l] = ba.n[l]; so.ba.blk0[l] = ba.blk0[l];
-          so.ba.foff[l] = ba.foff[l];
-        }
-        so.ba.blk0[L] = ba.blk0[L];
-        so.ba.d0 = ba.d0; so.ba.d1 = lin ? static_cast<const float*>(dir[3]) : nullptr;
-        so.bf = bias_fz;
-        so.bias_blocks = bias_blk;
-        small_blocks = so.head_blocks + bias_blk;
-      }
-      if (graw2) {   // round 4: packed Gram matrices -> k_graw (64 x 32 tiles, inner products in the tile epilogue, one slab per product)
-        GrawArgs ka{};
-        const int ct = graw_cols(hp, Bp);
-        // CT = 32: the small slices' blocks lead the grid; CT = 64: the tiles do (one CU each), the small blocks fill second slots
-        const bool small_first = ct == 32;
-        int gb = small_first ? (small_blocks + 15) & ~15 : 0;   // (every table entry a multiple of 16)
-        int real_tiles = 0;
-        for (int i = 0; i < hp->n; ++i) {
-          const int l = hp->layer[i];
-          GrawProb& q = ka.p[i];
-          if (!hp->bwd[i]) {   // Gf_l(raw) = S_l Rd_l + T_l delta_l
-            q.A1 = hbase + hp->sp_off[l]; q.B1 = m->Rd[l];
-            if (l >= 1) { q.A2 = hbase + hp->tslabp_off[l] + ((lin && l == 1) ? (size_t)cm.kpar * Bp * Bp : 0); q.B2 = m->delta[l]; }
-          } else {             // Gb_l(raw) = E_l h_l + D_l Rh_{l-1}
-            q.A1 = hbase + hp->eslabp_off[l]; q.B1 = m->h[l];
-            q.A2 = hbase + hp->dp_off[l]; q.B2 = (vnew && l == 1) ? rh0_slot(cm.nk) : m->Rh[l - 1];
-          }
-          q.Gr = q.Gp = q.B1;   // (always loadable)
-          if (vnew) q.Gr = q.Gp = hbase + hp->g_off[i];   // G(v): updated in place by the tile that owns the element
-          if (full) {           // the inner products' partner: Rd_l (= B1) forward, Rh_{l-1} (= B2) backward
-            q.Gr = hbase + hp->gr_off[i];
-            q.Gp = (lin && i == hp->gf[1]) ? gp1(cm.kpar) : ((lin_head && i == hp->gf[L - 2]) ? gp2(cm.kpar) : hbase + hp->g_off[i]);
-            q.dots = hp->bwd[i] ? 2 : 1;
-          }
-          q.Graw = hbase + hp->graw_off[i]; q.N = hp->N[i];
-          q.pb0 = real_tiles;
-          real_tiles += (Bp / 64) * (hp->N[i] / ct);
-          // every column tile with all its Bp / 64 row groups: groups of one tile 8 blocks apart (one XCD), column tiles padded to 8
-          ka.blk0[i] = gb; gb += (Bp / 64) * (((hp->N[i] / ct) + 7) & ~7);
-        }
-        ka.blk0[hp->n] = gb; ka.tile_end = gb;
-        BHG_REQUIRE(real_tiles == graw_tile_count(hp, Bp) && real_tiles <= hp->graw_tiles, "tile count of k_graw and of the plan disagree");
-        ka.n = hp->n; ka.Bp = Bp; ka.B = B;
-        ka.part = cm.ws->part_graw; ka.npart = real_tiles;
-        ka.small_blocks = small_blocks; ka.so = so;
-        ka.small0 = small_first ? 0 : gb;
-        if (!small_first) gb += small_blocks;
-        if (alpha_in_hoist) { ka.do_alpha = 1; ka.alpha = aa; }
-        BHG_REQUIRE(!rnew || (alpha_in_hoist && full), "k_graw was to apply the residual step but has no step length");
-        ka.rnew = (rnew || vnew) ? 1 : 0;
-        if (vnew) {   // Rh_0(v') for the next iteration's first product (packed) and for its k_graw (row-major, the other slot)
-          ka.nalpha = cm.alpha; ka.nshift = cm.shift;
-          ka.rh0p = cm.ws->Rhp[0]; ka.rh0 = rh0_slot(cm.nk + 1); ka.mask0 = m->mask[0];
-          ka.rb0 = ka.pb0s = static_cast<const float*>(dir[1]); ka.rh0_prod = hp->gf[0];
-        }
-        if (lin) {   // Rh_0(r') for the next iteration's first product; beta's granules cleared for its publication
-          ka.rh0p = hbase + hp->rh0rp_off; ka.mask0 = m->mask[0]; ka.rb0 = hbase + hp->rb0c_off;
-          ka.pb0s = static_cast<const float*>(dir[1]); ka.gran = cm.ws->gran; ka.rh0_prod = hp->gf[0];
-        }
-#ifdef BHG_AB   // (debug key graw_cols = 64)
-        if (ct == 64) {
-          if (cg) hipLaunchKernelGGL(k_graw64<FUSE_CG>, dim3(gb), dim3(64 * kGrawWaves), 0, st, ka);
-          else hipLaunchKernelGGL(k_graw64<FUSE_NEUMANN>, dim3(gb), dim3(64 * kGrawWaves), 0, st, ka);
-        } else
-#endif
-        if (Bp != 128) {   // the K-looped instance (32-column tiles)
-          if (cg) hipLaunchKernelGGL(k_grawk<FUSE_CG>, dim3(gb), dim3(64 * kGrawWaves), 0, st, ka);
-          else hipLaunchKernelGGL(k_grawk<FUSE_NEUMANN>, dim3(gb), dim3(64 * kGrawWaves), 0, st, ka);
-        } else if (cg) hipLaunchKernelGGL(k_graw<FUSE_CG>, dim3(gb), dim3(64 * kGrawWaves), 0, st, ka);
-        else hipLaunchKernelGGL(k_graw<FUSE_NEUMANN>, dim3(gb), dim3(64 * kGrawWaves), 0, st, ka);
-      }
-#ifdef BHG_AB
-      HoistArgs ga{};
-      int gblk = 0;
-      const int ntm = Bp / kTM;
-      for (int i = 0; i < hp->n && !graw2; ++i) {
-        const int l = hp->layer[i];
-        HoistProb& q = ga.p[i];
-        if (!hp->bwd[i]) {   // Gf_l(raw) = S_l Rd_l + T_l delta_l
-          q.A = hbase + hp->s_off[l]; q.Bm = m->Rd[l];
-          if (l >= 1) { q.A2 = hbase + hp->tslab_off[l]; q.B2m = m->delta[l]; q.a2_slabs = gram_in_chain ? tsplit(m->dims[l]) : gram_ksplit(m->dims[l]); }
-        } else {             // Gb_l(raw) = E_l h_l + D_l Rh_{l-1}
-          q.A = hbase + hp->eslab_off[l]; q.Bm = m->h[l]; q.a_slabs = gram_in_chain ? esplit(l, m->dims[l + 1]) : gram_ksplit(m->dims[l + 1]);
-          q.A2 = hbase + hp->d_off[l]; q.B2m = m->Rh[l - 1];
-        }
-        q.slabs = hbase + hp->graw_off[i];
-        q.a_slab_stride = Bp * Bp;
-        if (full) q.X = hp->bwd[i] ? (const float*)m->Rh[l - 1] : (const float*)m->Rd[l];   // raw.raw's share: <X, G(raw)>
-        q.K = Bp; q.N = hp->N[i]; q.splits = (q.A2 && graw_split()) ? 2 : 1; q.rc = 1; q.lda = Bp; q.ldb = hp->N[i];
-        ga.blk0[i] = gblk; gblk += (hp->N[i] / 32) * ntm * q.splits;
-      }
-      ga.blk0[hp->n] = gblk;
-      ga.n = hp->n; ga.Bp = Bp; ga.gemm_blocks = gblk; ga.do_beta = 0;
-      if (full && !graw2) {   // the projected inner products r.raw, p.raw ride behind the tiles
-        int dblk = 0, nd = 0;
-        for (int i = 0; i < hp->n; ++i) {
-          const int l = hp->layer[i];
-          ga.dp[nd] = {hbase + hp->gr_off[i], hbase + hp->g_off[i], hp->bwd[i] ? (const float*)m->Rh[l - 1] : (const float*)m->Rd[l], hp->N[i]};
-          ga.dblk0[nd++] = dblk; dblk += dot_blocks_of(Bp * (hp->N[i] / 4));
-        }
-        ga.dblk0[nd] = dblk;
-        ga.nd = nd; ga.dot_blocks = dblk; ga.B = B; ga.part_dot = cm.ws->part_dot; ga.part_raw = cm.ws->part_raw;
-        BHG_REQUIRE(gblk == graw_blocks(hp, Bp), "tile count of the G(raw) launch and of its raw.raw partials disagree");
-        BHG_REQUIRE(dblk == hp->dot_blocks, "dot block count of the plan and of the launch disagree");
-      }
-      if (small_in_graw) {
-        ga.so = so;
-        ga.small_blocks = small_blocks;
-        if (alpha_in_hoist) { ga.do_alpha = 1; ga.alpha = aa; }
-      }
-      if (graw2) {
-      } else if (cg) hipLaunchKernelGGL(k_hoist<FUSE_CG>, dim3(gblk + ga.dot_blocks + ga.small_blocks), dim3(256), 0, st, ga);
-      else hipLaunchKernelGGL(k_hoist<FUSE_NEUMANN>, dim3(gblk + ga.dot_blocks + ga.small_blocks), dim3(256), 0, st, ga);
-#endif
-    }
-    // one launch for all outputs when every MFMA layer is all-interior
-    // (fully projected CG: the MFMA layers' slices of r and p are not materialised — only the small slices' blocks launch)
-    const bool proj_full = hp && ((cg && cm.proj >= 2) || (!cg && cm.proj));   // no N-sized state: only the small slices' blocks
-    const int n_mfma = proj_full ? 0 : (head ? L - 1 : L);
-    OuterAllArgs oa{};
-    bool all_fast = !no_outer_all && n_mfma <= kOuterAllMax && head;
-    size_t lds_max = 0;
-    int order[BHG_MLP_MAX_LAYERS];
-    // dispatch order = tile order: the layer with the most tiles first (measured 260 vs 256 steps/s against
-    // "two-pair tiles first"; BHG_OUTER_ORDER_BY_WORK selects the latter)
-    const bool work_first = dbg(DBG_outer_order_by_work, 0) != 0;
-    auto weight = [&](int l) { return !work_first ? (double)outer_blocks(m, l, head) : (l > 0 ? 2.0 : 1.0) * 1e9 + outer_blocks(m, l, head); };
-    for (int i = 0; i < n_mfma; ++i) order[i] = i;
-    for (int i = 1; i < n_mfma; ++i)   // insertion sort, descending
-      for (int j = i; j > 0 && weight(order[j]) > weight(order[j - 1]); --j) { int t = order[j]; order[j] = order[j - 1]; order[j - 1] = t; }
-    int blk = 0;
-    for (int i = 0; i < n_mfma && all_fast; ++i) {
-      const int l = order[i];
-      size_t lds; bool fast;
-      outer_args(l, &oa.g[i], &lds, &fast);
-      all_fast = all_fast && fast;
-      if (lds > lds_max) lds_max = lds;
-      oa.f[i] = fuse_at(2 * l, part_base_w[l]);
-      oa.gx[i] = (oa.g[i].N + kTN - 1) / kTN;
-      oa.blk0[i] = blk;
-      blk += outer_blocks(m, l, head);
-    }
-    if (small_in_graw) {
-      // (the small slices' blocks already ran in k_hoist's launch)
-    } else if (all_fast) {
-      oa.n = n_mfma;
-      oa.blk0[n_mfma] = blk;
-      oa.head = head_outer_args(L - 1);
-      oa.hf = fuse_at(2 * (L - 1), part_base_w[L - 1]);
-      oa.head_gx = (oa.head.N + 63) / 64;
-      oa.head_blocks = oa.head_gx * oa.head.C;
-      oa.head_has_rh = L > 1;
-      oa.bf = bias_fz;
-      const int total = blk + oa.head_blocks + bias_blk;
-      if (lds_max < (size_t)kTM * kCPad * sizeof(float)) lds_max = (size_t)kTM * kCPad * sizeof(float);
-      const bool no_pre = dbg(DBG_outer_no_pre, 0) != 0;   // A/B runs
-      (void)no_pre;
-      const int stagger = dbg(DBG_outer_stagger, 1);
-      oa.stagger = stagger;
-#ifdef BHG_AB
-      if (no_pre) {
-        if (cg) hipLaunchKernelGGL((k_outer_all<FUSE_CG, false>), dim3(total), dim3(256), lds_max, st, oa, ba);
-        else hipLaunchKernelGGL((k_outer_all<FUSE_NEUMANN, false>), dim3(total), dim3(256), lds_max, st, oa, ba);
-      } else
-#endif
-      {
-        if (cg) hipLaunchKernelGGL((k_outer_all<FUSE_CG, true>), dim3(total), dim3(256), lds_max, st, oa, ba);
-        else hipLaunchKernelGGL((k_outer_all<FUSE_NEUMANN, true>), dim3(total), dim3(256), lds_max, st, oa, ba);
-      }
-    } else {
-      for (int l = L - 1; l >= 0; --l) launch_outer(l, st);
-      launch_bias(st);
-    }
-#ifdef BHG_AB
-    if (proj_full && cg && !proj_step_merged()) {   // r'.r', beta, p'.p' of the iteration from batch-sized quantities (k_proj_scalars)
-      BHG_REQUIRE(all_fast || small_in_graw, "the fully projected CG solver needs the single-launch output path");
-      ProjScalArgs sa{};
-      sa.part_dot = cm.ws->part_dot; sa.dot_blocks = hp->dot_blocks;
-      sa.part_raw = cm.ws->part_raw; sa.raw_blocks = graw_blocks(hp, Bp);
-      if (graw_single) {
-        const int gt = graw_tile_count(hp, Bp);
-        sa.part_dot = cm.ws->part_graw; sa.dot_blocks = gt;
-        sa.part_raw = cm.ws->part_graw + 2 * (size_t)gt; sa.raw_blocks = gt;
-      }
-      sa.part = cm.partRR_new; sa.part_stride = cm.ws->nRR;
-      sa.off0 = part_base_w[L - 1]; sa.n0 = outer_blocks(m, L - 1, head); sa.off1 = part_base_bias; sa.n1 = bias_blk;
-      sa.r_small = cm.beta->r; sa.p_small = cm.beta->p; sa.snt = cm.beta->nt;
-      for (int t = 0; t < cm.beta->nt; ++t) { sa.soff[t] = cm.beta->off[t]; sa.slen[t] = cm.beta->len[t]; }
-      sa.scal = cm.scal; sa.pscal = cm.ws->pscal; sa.shift = cm.shift; sa.first = cm.first; sa.kpar = cm.kpar;
-      int small_total = 0;
-      for (int t = 0; t < cm.beta->nt; ++t) small_total += cm.beta->len[t];
-      const int sgrid = small_total > 0 ? (small_total + kThreads - 1) / kThreads : 1;
-      hipLaunchKernelGGL(k_proj_scalars, dim3(sgrid), dim3(kThreads), 0, st, sa);
-    }
-#endif
+  }
+  if (pl.do_chain && !pl.hp) chain_forward(m, dir, cm, pl, st, &cs);
+  ChainOutputs od;
+  describe_outputs(m, dir, cm, pl, &od);
+  if (pl.do_chain && !pl.hp)
+    if (int rc = chain_backward(m, dir, cm, pl, st)) return rc;
+
+  if (pl.cg && cm.gphase == 1) {   // global-batch CG: the chain is done; this rank's p.H_data p for the caller's all-reduce
+    hipLaunchKernelGGL(k_php_local, dim3(1), dim3(kThreads), 0, st, od.aa, cm.php);
+    BHG_HIP_CHECK(hipGetLastError());
+    return BHG_OK;
+  }
+  if (pl.single) {
+    if (int rc = chain_close(m, dir, cm, pl, od, st, cs)) return rc;
     BHG_HIP_CHECK(hipGetLastError());
     return BHG_OK;
   }
 
-  if (L > 1 && !no_side) {  // the bias terms need every Rd_l (complete on the main stream now); they run beside H(W_0)
-    BHG_HIP_CHECK(hipEventRecord(ss.ev_rd[0], st));
-    BHG_HIP_CHECK(hipStreamWaitEvent(side, ss.ev_rd[0], 0));
-    launch_bias(side);
+  const bool fork = m->L > 1 && !pl.no_side;
+  if (fork) {  // the bias terms need every Rd_l (complete on the main stream now); they run beside H(W_0)
+    BHG_HIP_CHECK(hipEventRecord(pl.ss->ev_rd[0], st));
+    BHG_HIP_CHECK(hipStreamWaitEvent(pl.ss->side, pl.ss->ev_rd[0], 0));
+    launch_bias(cm, od, pl.ss->side);
   } else {
-    launch_bias(st);
+    launch_bias(cm, od, st);
   }
-  launch_outer(0, st);  // needs Rd_0, the end of the chain
-  if (L > 1 && !no_side) {
-    BHG_HIP_CHECK(hipEventRecord(ss.ev_join, side));
-    BHG_HIP_CHECK(hipStreamWaitEvent(st, ss.ev_join, 0));
+  launch_outer(m, dir, cm, pl, 0, st);  // needs Rd_0, the end of the chain
+  if (fork) {
+    BHG_HIP_CHECK(hipEventRecord(pl.ss->ev_join, pl.ss->side));
+    BHG_HIP_CHECK(hipStreamWaitEvent(st, pl.ss->ev_join, 0));
   }
   BHG_HIP_CHECK(hipGetLastError());
   return BHG_OK;
@@ -1779,9 +1760,8 @@ static void cg_ctx_init(CgCtx* c, const bhg_mlp* m, float* x, float* r, float* p
   // (BHG_MLP_PROJ: 0 off | 1 default | 9 level 1 even without a solution vector — the A/B arm of level 2)
   c->proj_level = (!c->hoist || !c->hplan.proj_ok || proj_mode() == 0 || global) ? 0 : ((proj_mode() == 9 || x) ? 1 : 2);
   // the chain's first product by linearity (k_wskpl): fully projected CG closing with k_graw that applies the residual step (the
-  // conditions of run_chain's graw_single and rnew), a net with a product between the first and the pre-head one, few small tensors
-  c->lin = c->proj_level == 2 && c->hplan.lin_ok && packed_chain_on(c->w) && dbg(DBG_packed_gram, 1) != 0 && dbg(DBG_graw_v2, 1) != 0 &&
-           graw_batch_ok(m->Bp) && dbg(DBG_proj_small_alone, 0) == 0 && dbg(DBG_alpha_in_hoist, 1) != 0 && dbg(DBG_rnew_in_graw, 1) != 0 &&
+  // conditions of plan_chain's graw_single and rnew), a net with a product between the first and the pre-head one, few small tensors
+  c->lin = c->proj_level == 2 && c->hplan.lin_ok && graw_single_on(packed_chain_on(c->w), m->Bp) && rnew_keys_on() &&
            c->ba.nt <= 16 && proj_step_merged() && dbg(DBG_pstep_v2, 1) != 0 && dbg(DBG_lin_first, 1) != 0;
   // ... and on a four-layer net the update blocks ride in the head launch (k_headu, headu.inc) rather than in the pre-head one: the head's
   // prefetching instance must apply (<= 12 classes, last hidden width <= 512), and like lin it holds for the whole solve (slot parity)
