@@ -129,6 +129,16 @@ SYMBOLS = {
         c_int,
         [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p],
     ),
+    "bhg_logreg_solve_plan": (c_int, [c_int, c_int, c_int, c_int, c_char_p, c_size_t]),
+    "bhg_logreg_solve_ws_bytes": (c_size_t, [c_int, c_int]),
+    "bhg_logreg_cg_solve": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float, c_int, c_int, c_void_p],
+    ),
+    "bhg_logreg_neumann_solve": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float, c_int, c_int, c_void_p],
+    ),
     "bhg_mlp_partial_floats": (c_size_t, [POINTER(Mlp)]),
     "bhg_mlp_hvp": (c_int, [POINTER(Mlp), _PP, _PP, c_void_p]),
     "bhg_mlp_hvp_mode": (c_int, [POINTER(Mlp), _PP, _PP, c_int, c_void_p]),

@@ -350,6 +350,44 @@ class HipBackend:
             "bhg_quad_fd",
         )
 
+    # -- logistic regression: the whole cg / neumann solve in native launches (csrc/bhg_logreg_solve.hip) -------------------
+    def logreg_solve_workspace(self, n: int, d: int, device) -> torch.Tensor:
+        return torch.empty(int(self.lib.bhg_logreg_solve_ws_bytes(int(n), int(d))), dtype=torch.uint8, device=device)
+
+    def logreg_cg_solve(self, X, w, lam, rhs, out, coeff, ws, K: int, cg_alpha: float, out_scale: float, form: int = 0,
+                        strips: int = 0) -> None:
+        """out <- out_scale * x_K of K CG iterations on H = X^T diag(s) X + diag(lam) from x = 0, r = p = rhs (the reference's
+        iteration, ``cg_alpha`` quirk included); coeff (or None) <- w * out.  form: LOGREG_FORM_AUTO / _SINGLE / _STRIPS."""
+        n, d = X.shape
+        _native.check(
+            self.lib.bhg_logreg_cg_solve(X.data_ptr(), w.data_ptr(), lam.data_ptr(), rhs.data_ptr(), out.data_ptr(),
+                                         None if coeff is None else coeff.data_ptr(), ws.data_ptr(), n, d, int(K), float(cg_alpha),
+                                         float(out_scale), int(form), int(strips), _stream_ptr()),
+            "bhg_logreg_cg_solve",
+        )
+
+    def logreg_neumann_solve(self, X, w, lam, rhs, out, coeff, ws, K: int, alpha: float, out_scale: float, form: int = 0,
+                             strips: int = 0) -> None:
+        """out <- out_scale * p_K of K Neumann iterations v <- v - alpha H v, p <- p + v from v = p = rhs; coeff (or None) <- w * out."""
+        n, d = X.shape
+        _native.check(
+            self.lib.bhg_logreg_neumann_solve(X.data_ptr(), w.data_ptr(), lam.data_ptr(), rhs.data_ptr(), out.data_ptr(),
+                                              None if coeff is None else coeff.data_ptr(), ws.data_ptr(), n, d, int(K), float(alpha),
+                                              float(out_scale), int(form), int(strips), _stream_ptr()),
+            "bhg_logreg_neumann_solve",
+        )
+
+
+LOGREG_FORM_AUTO, LOGREG_FORM_SINGLE, LOGREG_FORM_STRIPS = 0, 1, 2
+
+
+def logreg_solve_plan(n: int, d: int, form: int = LOGREG_FORM_AUTO, strips: int = 0) -> str:
+    """The form the native logistic-regression solvers take for an n x d problem, as the library words it: "single: ...",
+    "strips G=...: ..." or "none" (bhg_logreg_solve_plan — host logic only: works on a box without a GPU).  A forced form the shape
+    does not admit raises."""
+    buf = ctypes.create_string_buffer(256)
+    _native.check(_native.load().bhg_logreg_solve_plan(int(n), int(d), int(form), int(strips), buf, 256), "bhg_logreg_solve_plan")
+    return buf.value.decode()
 
 
 _backend = None

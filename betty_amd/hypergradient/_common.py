@@ -194,6 +194,9 @@ class ForwardOverReverseHVP:
 # warning per problem, and nothing is touched.
 FD_HVP_STATS = {"solves": 0, "pairs": 0, "fallbacks": 0}
 FD_HVP_DEFAULT_RADIUS = 0.01
+# cg / neumann calls on a declared LogisticRegressionL2 that offered the provider's own solver: `fused` ran the whole K loop in native
+# launches (csrc/bhg_logreg_solve.hip), `loop` took K x (product + recurrence kernel) — K = 0, impl = "torch", d > 4096, ...
+LOGREG_SOLVE_STATS = {"fused": 0, "loop": 0}
 
 
 def finite_difference_wanted(curr) -> bool:

@@ -43,7 +43,7 @@ import warnings
 import torch
 import torch.nn.functional as F
 
-from ._common import _uses_ddp, is_fsdp, precision_of
+from ._common import LOGREG_SOLVE_STATS, _uses_ddp, finite_difference_wanted, is_fsdp, precision_of
 
 
 class StructureMismatchError(RuntimeError):
@@ -800,6 +800,12 @@ class LogisticRegressionL2(_QuadraticFD):
 
     darts / sama: the penalty is the only place lam enters, dL/dlam_j = w_j^2 / 2, so the central difference along v is
     (w-^2 - w+^2) / (4 eps) = -w_j v_j exactly (``finite_difference``, see _QuadraticFD for ``impl`` / ``closed_form_fd``).
+
+    cg / neumann: the provider's own solver (``fused_cg`` / ``fused_neumann``, csrc/bhg_logreg_solve.hip) runs the whole K loop in
+    native launches — one launch of one workgroup at BASELINE cfg 1 — and leaves the cotangent w * (-alpha x) of lam for
+    ``mixed_vjp``.  It is taken when K > 0, ``impl`` is hip, the library has a form for the shape (d <= 4096), the tensors are
+    contiguous 16-byte aligned fp32 and the product is the analytic one; everything else keeps K x (``hvp`` + recurrence kernel).
+    LOGREG_SOLVE_STATS (hypergradient/_common.py) counts both.
     """
 
     def __init__(self, curr, prev, weight: torch.nn.Parameter, lam_fn: Callable, batch=None, impl: Optional[str] = None,
@@ -823,18 +829,22 @@ class LogisticRegressionL2(_QuadraticFD):
         self.lam = self.lam_fn()  # keeps the graph to prev's parameters
         self.lam_d = self.lam.detach().to(torch.float32).contiguous()
         self.w = self.weight.detach().to(torch.float32).contiguous()
-        self.s = torch.empty(n, device=x.device)
-        self.tmp = torch.empty(int(self.lib.bhg_logreg_tmp_floats(n, d)), device=x.device)
-        self.out = torch.empty(d, device=x.device)
         self._stream = lambda: int(torch.cuda.current_stream().cuda_stream)
-        _native.check(self.lib.bhg_logreg_prepare(self.X.data_ptr(), self.w.data_ptr(), self.s.data_ptr(), n, d, self._stream()),
-                      "bhg_logreg_prepare")
         self._native = _native
+        self.s = None   # formed by the first product: a native solve forms s itself and never asks for one
+        self._coeff = None
         return self.hvp
 
     def hvp(self, direction_views):
         (p,) = direction_views
         p = p.detach().to(torch.float32).contiguous()
+        if self.s is None:
+            n, d, dev = self.n, self.d, self.X.device
+            self.s = torch.empty(n, device=dev)
+            self.tmp = torch.empty(int(self.lib.bhg_logreg_tmp_floats(n, d)), device=dev)
+            self.out = torch.empty(d, device=dev)
+            self._native.check(self.lib.bhg_logreg_prepare(self.X.data_ptr(), self.w.data_ptr(), self.s.data_ptr(), n, d, self._stream()),
+                               "bhg_logreg_prepare")
         self._native.check(
             self.lib.bhg_logreg_hvp(self.X.data_ptr(), self.s.data_ptr(), self.lam_d.data_ptr(), p.data_ptr(),
                                     self.out.data_ptr(), self.tmp.data_ptr(), self.n, self.d, self._stream()),
@@ -842,8 +852,63 @@ class LogisticRegressionL2(_QuadraticFD):
         )
         return [self.out.view(self.weight.shape)]
 
+    # ---- the provider's own solver: all K iterations in native launches (csrc/bhg_logreg_solve.hip) ----
+    _PLANS = {}   # (n, d) -> the library's plan line
+
+    def _fused_solve_ready(self, K: int, *state) -> bool:
+        from ..backend import get_backend, logreg_solve_plan  # noqa: PLC0415
+
+        if not (K > 0 and (self.impl or "hip") == "hip") or finite_difference_wanted(self.curr):
+            return False
+        if getattr(self, "X", None) is None or not hasattr(get_backend(), "logreg_cg_solve"):
+            return False
+        if self.lam_d.numel() != self.d or self.w.numel() != self.d or any(t.numel() < self.d for t in state):
+            return False
+        for t in (self.X, self.w, self.lam_d) + state:
+            if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.data_ptr() % 16 == 0):
+                return False
+        plan = self._PLANS.get((self.n, self.d))
+        if plan is None:
+            plan = self._PLANS[(self.n, self.d)] = logreg_solve_plan(self.n, self.d)
+        return not plan.startswith("none")
+
+    def _fused_solve(self, method: str, rhs, out, K: int, step: float) -> bool:
+        from ..backend import get_backend  # noqa: PLC0415
+
+        be = get_backend()
+        ws = be.logreg_solve_workspace(self.n, self.d, self.X.device)
+        coeff = torch.empty(self.d, device=self.X.device)
+        # out = -step * (x_K | p_K): what the generic loop leaves in the flat solution for mixed_vjp (InnerOperator.out_sign = -1 here)
+        getattr(be, method)(self.X, self.w, self.lam_d, rhs, out, coeff, ws, K, step, -step)
+        self._coeff = coeff
+        LOGREG_SOLVE_STATS["fused"] += 1
+        return True
+
+    def fused_cg_ready(self, layout, K: int) -> bool:
+        return layout.T == 1 and self._fused_solve_ready(K)
+
+    def fused_cg(self, layout, x, r, p, K: int, cg_alpha: float, rhs=None):
+        """x <- -cg_alpha * x_K and True, or False (nothing touched: the caller runs its loop).  r holds the right-hand side (cg_init)."""
+        if not (layout.T == 1 and self._fused_solve_ready(K, x, r)):
+            LOGREG_SOLVE_STATS["loop"] += 1
+            return False
+        return self._fused_solve("logreg_cg_solve", r, x, K, cg_alpha)
+
+    def fused_neumann_ready(self, layout, K: int) -> bool:
+        return layout.T == 1 and self._fused_solve_ready(K)
+
+    def fused_neumann(self, layout, v, p, K: int, alpha: float):
+        """p <- -alpha * p_K and True, or False.  v holds the right-hand side (neumann_init)."""
+        if not (layout.T == 1 and self._fused_solve_ready(K, v, p)):
+            LOGREG_SOLVE_STATS["loop"] += 1
+            return False
+        return self._fused_solve("logreg_neumann_solve", v, p, K, alpha)
+
     def mixed_vjp(self, neg_x_views, sync: bool):
-        coeff = (self.w * neg_x_views[0].reshape(-1)).reshape(self.lam.shape)  # d(g.(-x))/d lam
+        coeff, self._coeff = getattr(self, "_coeff", None), None
+        if coeff is None:   # (else a native solve has just left w * (-alpha x) beside its solution)
+            coeff = self.w * neg_x_views[0].reshape(-1)  # d(g.(-x))/d lam
+        coeff = coeff.reshape(self.lam.shape)
         upper = self.prev.trainable_parameters()
         if sync:
             torch.autograd.backward(self.lam, grad_tensors=coeff, inputs=upper)

@@ -239,6 +239,24 @@ size_t bhg_logreg_tmp_floats(int n, int d);
 int bhg_logreg_hvp(const float* X, const float* s, const float* lam, const float* p, float* out,
                    float* tmp, int n, int d, void* stream);
 
+/* The whole CG / Neumann solve on that structure in native launches (csrc/bhg_logreg_solve.hip): s is formed from (X, w) inside
+ * the solve, X is read once per product.  Two forms: `single` (one launch of one workgroup runs all K iterations; d <= 1024 and
+ * n * d <= 2^18) and `strips` (G workgroups own contiguous row strips; 3 launches per CG iteration, 2 per Neumann iteration;
+ * d <= 4096).  form: 0 = auto, 1 = single, 2 = strips — a forced form the shape does not admit is an error, not a fallback;
+ * strips: 0 = auto, else the strip count (<= 512).  Inputs are read-only; no host synchronisation, no float atomics; results are
+ * bitwise run-to-run deterministic and nothing is read from `ws` that the solve has not written.
+ *   CG      (cg.py:34-56 of the reference, its cg_alpha quirk included): out = out_scale * x_K
+ *   Neumann (neumann.py:59-66):                                           out = out_scale * p_K
+ * out_scale == 0 means no final scaling, as in the recurrence kernels.  coeff (nullable) receives w .* out, the cotangent of lam.
+ * bhg_logreg_solve_plan is host logic only: it writes one line into buf naming the form taken ("single: ...", "strips G=...: ...",
+ * "none") and its launches per iteration.  ws: bhg_logreg_solve_ws_bytes(n, d) bytes of device memory, 16-byte aligned.             */
+int bhg_logreg_solve_plan(int n, int d, int form, int strips, char* buf, size_t buf_bytes);
+size_t bhg_logreg_solve_ws_bytes(int n, int d);
+int bhg_logreg_cg_solve(const float* X, const float* w, const float* lam, const float* rhs, float* out, float* coeff, void* ws,
+                        int n, int d, int K, float cg_alpha, float out_scale, int form, int strips, void* stream);
+int bhg_logreg_neumann_solve(const float* X, const float* w, const float* lam, const float* rhs, float* out, float* coeff, void* ws,
+                             int n, int d, int K, float alpha, float out_scale, int form, int strips, void* stream);
+
 /* ReLU-MLP with per-sample-weighted cross-entropy (+ ridge) — SURVEY Appendix A.3; the inner
  * problem of examples/learning_to_reweight/main.py:117-127 (BASELINE cfg 2 / the metric's 10 M
  * parameter problem).  The caller computes the direction-independent quantities once per
