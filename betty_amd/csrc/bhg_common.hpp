@@ -145,6 +145,42 @@ __device__ __forceinline__ void st4(float* __restrict__ base, int e, int len, fl
   if (e + 2 < len) base[e + 2] = v.z;
 }
 
+// ---- rounding-pinned fp32 arithmetic ---------------------------------------------------
+// The recurrences follow the reference's rounding sequence: every product is rounded, then added or subtracted — never
+// contracted into an fma — and dot products accumulate in fp64 in a fixed order.  These are the only spellings of that rule:
+// the scalar forms pin one rounding each, the float4 forms apply them component by component.
+__device__ __forceinline__ float mul_rn(float a, float b) { return __fmul_rn(a, b); }
+__device__ __forceinline__ float add_rn(float a, float b) { return __fadd_rn(a, b); }
+__device__ __forceinline__ float sub_rn(float a, float b) { return __fsub_rn(a, b); }
+__device__ __forceinline__ float div_rn(float a, float b) { return __fdiv_rn(a, b); }
+// s * a
+__device__ __forceinline__ float4 scale4(float s, float4 a) {
+  return make_float4(mul_rn(s, a.x), mul_rn(s, a.y), mul_rn(s, a.z), mul_rn(s, a.w));
+}
+// a + b
+__device__ __forceinline__ float4 add4(float4 a, float4 b) {
+  return make_float4(add_rn(a.x, b.x), add_rn(a.y, b.y), add_rn(a.z, b.z), add_rn(a.w, b.w));
+}
+// a + s*b, the product rounded first
+__device__ __forceinline__ float4 add_scaled4(float4 a, float s, float4 b) {
+  return make_float4(add_rn(a.x, mul_rn(s, b.x)), add_rn(a.y, mul_rn(s, b.y)), add_rn(a.z, mul_rn(s, b.z)),
+                     add_rn(a.w, mul_rn(s, b.w)));
+}
+// a - s*b, the product rounded first
+__device__ __forceinline__ float4 sub_scaled4(float4 a, float s, float4 b) {
+  return make_float4(sub_rn(a.x, mul_rn(s, b.x)), sub_rn(a.y, mul_rn(s, b.y)), sub_rn(a.z, mul_rn(s, b.z)),
+                     sub_rn(a.w, mul_rn(s, b.w)));
+}
+// (a - b) / d: the difference rounded first, then a true fp32 division
+__device__ __forceinline__ float4 diff_over4(float4 a, float4 b, float d) {
+  return make_float4(div_rn(sub_rn(a.x, b.x), d), div_rn(sub_rn(a.y, b.y), d), div_rn(sub_rn(a.z, b.z), d),
+                     div_rn(sub_rn(a.w, b.w), d));
+}
+// a . b in fp64, in this association: ((x + y) + z) + w
+__device__ __forceinline__ double dot4(float4 a, float4 b) {
+  return (double)a.x * b.x + (double)a.y * b.y + (double)a.z * b.z + (double)a.w * b.w;
+}
+
 // ---- kernel arguments: one latency for all of them ------------------------------------------------------------------
 // A miss of the scalar cache on the kernarg segment costs ~1.4 us on this system (stamps of k_graw: a tile whose descriptor shares
 // the first lines of the argument struct reaches its first load 1.8 us after entry, one whose descriptor sits further back 4.6 us —

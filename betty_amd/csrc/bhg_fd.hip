@@ -27,9 +27,6 @@ constexpr int kFdMaxMT = 4;     // batch <= 512 rows: the accumulators of every 
 constexpr int kFdWgTarget = 512;
 constexpr int kFdMaxSplits = 32;
 
-__device__ __forceinline__ float fd_mul(float a, float b) { return __fmul_rn(a, b); }
-__device__ __forceinline__ float fd_add(float a, float b) { return __fadd_rn(a, b); }
-
 struct FdLayer {
   const float* hp;   // [M][K] activations at w+ (layer 0: the input)
   const float* hm;   // [M][K] activations at w- (layer 0: the same input)
@@ -45,9 +42,9 @@ struct FdLayer {
 
 // The three axpys of darts.py:37-63 on one element, in k_axpy_multi's roundings (a = mul * eps).
 __device__ __forceinline__ void fd_perturb(float w, float v, float a1, float a2, int restore, float& wp, float& wm, float& wf) {
-  wp = fd_add(w, fd_mul(a1, v));
-  wm = fd_add(wp, fd_mul(a2, v));
-  wf = restore ? fd_add(wm, fd_mul(a1, v)) : wm;
+  wp = add_rn(w, mul_rn(a1, v));
+  wm = add_rn(wp, mul_rn(a2, v));
+  wf = restore ? add_rn(wm, mul_rn(a1, v)) : wm;
 }
 
 // grid = (ceil(N / 32), splits), block = 256.  Wave w owns batch rows [32 w, 32 w + 32) of every 128-row M tile.
@@ -60,7 +57,7 @@ __global__ __launch_bounds__(kThreads) void k_fd_gemm(FdLayer a) {
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6, li = lane & 31, lk = lane >> 5;
   const int n0 = blockIdx.x * kFdTN, split = blockIdx.y;
   const float eps = *a.eps;
-  const float a1 = fd_mul(1.f, eps), a2 = fd_mul(-2.f, eps);
+  const float a1 = mul_rn(1.f, eps), a2 = mul_rn(-2.f, eps);
   const bool shared_a = a.hp == a.hm;
 
   // the biases of this column tile: the first split's workgroup owns them

@@ -32,18 +32,15 @@ struct QuadTab {
   float* o[kQuadT];         // result
 };
 
-__device__ __forceinline__ float q_mul(float a, float b) { return __fmul_rn(a, b); }
-__device__ __forceinline__ float q_add(float a, float b) { return __fadd_rn(a, b); }
-
 // One element: the weight the three axpys of darts.py:37-63 leave behind (k_axpy_multi's roundings), and the closed-form result.
 template <int MODE, bool ACC>
 __device__ __forceinline__ void quad_elem(float w, float v, float o_old, float a1, float a2, float scale, int restore, float& w_new,
                                           float& o_new) {
-  const float w1 = q_add(w, q_mul(a1, v));
-  const float w2 = q_add(w1, q_mul(a2, v));
-  w_new = restore ? q_add(w2, q_mul(a1, v)) : w2;
-  const float r = MODE == 0 ? q_mul(scale, v) : -q_mul(w, v);
-  o_new = ACC ? q_add(o_old, r) : r;
+  const float w1 = add_rn(w, mul_rn(a1, v));
+  const float w2 = add_rn(w1, mul_rn(a2, v));
+  w_new = restore ? add_rn(w2, mul_rn(a1, v)) : w2;
+  const float r = MODE == 0 ? mul_rn(scale, v) : -mul_rn(w, v);
+  o_new = ACC ? add_rn(o_old, r) : r;
 }
 
 // grid = grid_for(n_chunks) workgroups striding over the chunk table; block = 256.  Tensors [t0, t0 + kQuadT) of the layout are this
@@ -52,7 +49,7 @@ template <int MODE, bool ACC>
 __global__ __launch_bounds__(kThreads) void k_quad_fd(QuadTab tab, int t0, const bhg_chunk* __restrict__ chunks, int n_chunks,
                                                       const float* __restrict__ eps_dev, float scale, int restore) {
   const float eps = *eps_dev;
-  const float a1 = q_mul(1.f, eps), a2 = q_mul(-2.f, eps);
+  const float a1 = mul_rn(1.f, eps), a2 = mul_rn(-2.f, eps);
   for (int c = blockIdx.x; c < n_chunks; c += gridDim.x) {
     const bhg_chunk ck = chunks[c];
     const int t = ck.tensor - t0;

@@ -18,7 +18,7 @@ namespace {
 __global__ __launch_bounds__(kThreads) void k_fd_perturb(PtrTab w, const float* __restrict__ w0, PtrTab dir,
                                                          const bhg_chunk* __restrict__ chunks, int n_chunks,
                                                          const float* __restrict__ eps_dev, float sign) {
-  const float a = __fmul_rn(sign, *eps_dev);
+  const float a = mul_rn(sign, *eps_dev);
   for (int c = blockIdx.x; c < n_chunks; c += gridDim.x) {
     const bhg_chunk ck = chunks[c];
     float* d = tab_ptr(w, ck.tensor) + ck.src_off;
@@ -34,10 +34,7 @@ __global__ __launch_bounds__(kThreads) void k_fd_perturb(PtrTab w, const float* 
 #pragma unroll
     for (int i = 0; i < kVecPerThread; ++i) {
       const int e = 4 * (threadIdx.x + kThreads * i);
-      float4 o;
-      o.x = __fadd_rn(bv[i].x, __fmul_rn(a, sv[i].x)); o.y = __fadd_rn(bv[i].y, __fmul_rn(a, sv[i].y));
-      o.z = __fadd_rn(bv[i].z, __fmul_rn(a, sv[i].z)); o.w = __fadd_rn(bv[i].w, __fmul_rn(a, sv[i].w));
-      st4(d, e, ck.len, o);
+      st4(d, e, ck.len, add_scaled4(bv[i], a, sv[i]));
     }
   }
 }

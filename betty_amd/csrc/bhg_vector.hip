@@ -21,18 +21,6 @@
 namespace bhg {
 namespace {
 
-__device__ __forceinline__ float mul_rn(float a, float b) { return __fmul_rn(a, b); }
-__device__ __forceinline__ float add_rn(float a, float b) { return __fadd_rn(a, b); }
-__device__ __forceinline__ float sub_rn(float a, float b) { return __fsub_rn(a, b); }
-
-#define BHG_FOR4(stmt_x, stmt_y, stmt_z, stmt_w) \
-  do {                                           \
-    stmt_x;                                      \
-    stmt_y;                                      \
-    stmt_z;                                      \
-    stmt_w;                                      \
-  } while (0)
-
 // ---- pointer-table writer (T > kInlineT) -----------------------------------------------
 struct WriterArgs {
   const void* p[kWriterT];
@@ -54,11 +42,7 @@ __global__ __launch_bounds__(kThreads) void k_flatten(PtrTab tab, const bhg_chun
 #pragma unroll
     for (int i = 0; i < kVecPerThread; ++i) v[i] = ld4(src, 4 * (threadIdx.x + kThreads * i), ck.len);
 #pragma unroll
-    for (int i = 0; i < kVecPerThread; ++i) {
-      float4 o = v[i];
-      o.x = mul_rn(scale, o.x); o.y = mul_rn(scale, o.y); o.z = mul_rn(scale, o.z); o.w = mul_rn(scale, o.w);
-      st4(dst, 4 * (threadIdx.x + kThreads * i), ck.len, o);
-    }
+    for (int i = 0; i < kVecPerThread; ++i) st4(dst, 4 * (threadIdx.x + kThreads * i), ck.len, scale4(scale, v[i]));
   }
 }
 
@@ -73,11 +57,7 @@ __global__ __launch_bounds__(kThreads) void k_scatter(const float* __restrict__ 
 #pragma unroll
     for (int i = 0; i < kVecPerThread; ++i) v[i] = ld4(src, 4 * (threadIdx.x + kThreads * i), ck.len);
 #pragma unroll
-    for (int i = 0; i < kVecPerThread; ++i) {
-      float4 o = v[i];
-      o.x = mul_rn(scale, o.x); o.y = mul_rn(scale, o.y); o.z = mul_rn(scale, o.z); o.w = mul_rn(scale, o.w);
-      st4(dst, 4 * (threadIdx.x + kThreads * i), ck.len, o);
-    }
+    for (int i = 0; i < kVecPerThread; ++i) st4(dst, 4 * (threadIdx.x + kThreads * i), ck.len, scale4(scale, v[i]));
   }
 }
 
@@ -85,9 +65,7 @@ __global__ __launch_bounds__(kThreads) void k_scale_flat(float* __restrict__ fla
                                                          float scale) {
   // n4 = number of whole float4; tail handled by the last thread range
   for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < n4; i += (int64_t)gridDim.x * kThreads) {
-    float4 v = reinterpret_cast<float4*>(flat)[i];
-    v.x = mul_rn(scale, v.x); v.y = mul_rn(scale, v.y); v.z = mul_rn(scale, v.z); v.w = mul_rn(scale, v.w);
-    reinterpret_cast<float4*>(flat)[i] = v;
+    reinterpret_cast<float4*>(flat)[i] = scale4(scale, reinterpret_cast<float4*>(flat)[i]);
   }
   if (blockIdx.x == 0 && threadIdx.x < (n - 4 * n4)) {
     const int64_t j = 4 * n4 + threadIdx.x;
@@ -119,12 +97,41 @@ struct HvpGradPair {
   __device__ __forceinline__ float4 load(const Ctx& cx, const bhg_chunk& ck, int e) const {
     const float4 a = ld4(tab_ptr(gp, ck.tensor) + ck.src_off, e, ck.len);
     const float4 b = ld4(tab_ptr(gm, ck.tensor) + ck.src_off, e, ck.len);
-    float4 o;
-    o.x = __fdiv_rn(sub_rn(a.x, b.x), cx.d); o.y = __fdiv_rn(sub_rn(a.y, b.y), cx.d);
-    o.z = __fdiv_rn(sub_rn(a.z, b.z), cx.d); o.w = __fdiv_rn(sub_rn(a.w, b.w), cx.d);
-    return o;
+    return diff_over4(a, b, cx.d);
   }
 };
+
+// ---- the updates of the recurrences, each stated once ---------------------------------------------
+// Streaming kernels, the resident kernel's phases, its resident_stream lambdas and its streamed tails all call these.
+// H q = (raw HVP) + shift * q: the diagonal part of the Hessian is kept out of the producer (and never round-trips through HBM)
+__device__ __forceinline__ float4 shifted_product(float4 h, float shift, float4 q) {
+  if (shift != 0.f) h = add_scaled4(h, shift, q);
+  return h;
+}
+// contribution to den = (cg_alpha*Hp).p   (cg.py:42,44,46)
+__device__ __forceinline__ double php_term(float cg_alpha, float4 h, float4 q) { return dot4(scale4(cg_alpha, h), q); }
+// contribution to a squared norm (cg.py:45,51; darts.py:29)
+__device__ __forceinline__ double sqnorm4(float4 t) { return dot4(t, t); }
+// r' = r - alpha*Hp (cg.py:50) and its share of r'.r' (cg.py:51-52)
+__device__ __forceinline__ float4 resid_update(float4 r, float alpha, float4 h, double& acc) {
+  const float4 nr = sub_scaled4(r, alpha, h);
+  acc += sqnorm4(nr);
+  return nr;
+}
+// x += alpha*p (cg.py:49) [x <- out_scale*x on the last step]
+__device__ __forceinline__ float4 x_update(float4 x, float alpha, float4 p, float out_scale) {
+  float4 nx = add_scaled4(x, alpha, p);
+  if (out_scale != 0.f) nx = scale4(out_scale, nx);
+  return nx;
+}
+// p = r' + beta*p (cg.py:53)
+__device__ __forceinline__ float4 dir_update(float4 r, float beta, float4 p) { return add_scaled4(r, beta, p); }
+// v <- v - alpha*Hv ; p <- p + v ; [p <- out_scale * p]   (neumann.py:62-64, +66)
+__device__ __forceinline__ void neumann_update(float4& v, float4& p, float alpha, float4 h, float out_scale) {
+  v = sub_scaled4(v, alpha, h);
+  p = add4(v, p);
+  if (out_scale != 0.f) p = scale4(out_scale, p);
+}
 
 // ---- Neumann ----------------------------------------------------------------------------------
 // neumann.py:60  p = v (the reference aliases; we keep two flat buffers)
@@ -169,21 +176,9 @@ __global__ __launch_bounds__(kThreads) void k_neumann_step(Src src, const bhg_ch
 #pragma unroll
     for (int i = 0; i < kVecPerThread; ++i) {
       const int e = 4 * (threadIdx.x + kThreads * i);
-      if (shift != 0.f) {  // H v = (raw HVP) + shift * v  (diagonal part of the Hessian kept out of the producer)
-        h[i].x = add_rn(h[i].x, mul_rn(shift, a[i].x)); h[i].y = add_rn(h[i].y, mul_rn(shift, a[i].y));
-        h[i].z = add_rn(h[i].z, mul_rn(shift, a[i].z)); h[i].w = add_rn(h[i].w, mul_rn(shift, a[i].w));
-      }
-      float4 nv, np;
-      nv.x = sub_rn(a[i].x, mul_rn(alpha, h[i].x)); nv.y = sub_rn(a[i].y, mul_rn(alpha, h[i].y));
-      nv.z = sub_rn(a[i].z, mul_rn(alpha, h[i].z)); nv.w = sub_rn(a[i].w, mul_rn(alpha, h[i].w));
-      np.x = add_rn(nv.x, b[i].x); np.y = add_rn(nv.y, b[i].y);
-      np.z = add_rn(nv.z, b[i].z); np.w = add_rn(nv.w, b[i].w);
-      if (out_scale != 0.f) {
-        np.x = mul_rn(out_scale, np.x); np.y = mul_rn(out_scale, np.y);
-        np.z = mul_rn(out_scale, np.z); np.w = mul_rn(out_scale, np.w);
-      }
-      st4(vv, e, ck.len, nv);
-      st4(pp, e, ck.len, np);
+      neumann_update(a[i], b[i], alpha, shifted_product(h[i], shift, a[i]), out_scale);
+      st4(vv, e, ck.len, a[i]);
+      st4(pp, e, ck.len, b[i]);
     }
   }
 }
@@ -216,8 +211,7 @@ __global__ __launch_bounds__(kThreads) void k_cg_init(PtrTab tab, const bhg_chun
         st4(r + ck.flat_off, e, ck.len, t[i]);
         st4(p + ck.flat_off, e, ck.len, t[i]);
       }
-      acc += (double)t[i].x * t[i].x + (double)t[i].y * t[i].y + (double)t[i].z * t[i].z +
-             (double)t[i].w * t[i].w;
+      acc += sqnorm4(t[i]);
     }
   }
   const double s = block_sum(acc, red);
@@ -228,7 +222,54 @@ __global__ __launch_bounds__(kThreads) void k_cg_init(PtrTab tab, const bhg_chun
   }
 }
 
+// K2's and K3's pass over one chunk, for a workgroup of THREADS threads holding V float4 each (V * THREADS * 4 = kChunk):
+// the bodies of k_cg_resid / k_cg_dir <kVecPerThread, kThreads> and of the resident kernel's streamed tails
+// <kResV, kResThreads>.  Each issues all its loads first, then does the arithmetic and the stores.  (K1's pass: see k_cg_dot.)
+// K2's chunk: r' = r - alpha*Hp stored, its share of r'.r' added to acc.
+template <int V, int THREADS, typename Src>
+__device__ __forceinline__ void cg_resid_chunk(const Src& src, const typename Src::Ctx& cx, const bhg_chunk ck,
+                                               float* __restrict__ r, const float* __restrict__ p, float shift, float alpha,
+                                               double& acc) {
+  float* rrp = r + ck.flat_off;
+  float4 h[V], a[V];
+#pragma unroll
+  for (int i = 0; i < V; ++i) {
+    const int e = 4 * (threadIdx.x + THREADS * i);
+    h[i] = src.load(cx, ck, e);
+    a[i] = ld4(rrp, e, ck.len);
+    // (12+4)*N bytes in this case: the direction is re-read for the diagonal term.  The test here is what skips that load;
+    // shifted_product tests the shift again, which the compiler folds.
+    if (shift != 0.f) h[i] = shifted_product(h[i], shift, ld4(p + ck.flat_off, e, ck.len));
+  }
+#pragma unroll
+  for (int i = 0; i < V; ++i) st4(rrp, 4 * (threadIdx.x + THREADS * i), ck.len, resid_update(a[i], alpha, h[i], acc));
+}
+// K3's chunk: x += alpha*p [* out_scale] and p = r' + beta*p in one pass.
+template <int V, int THREADS>
+__device__ __forceinline__ void cg_dir_chunk(const bhg_chunk ck, float* __restrict__ x, const float* __restrict__ r,
+                                             float* __restrict__ p, float alpha, float beta, float out_scale) {
+  float4 a[V], q[V], xx[V];
+#pragma unroll
+  for (int i = 0; i < V; ++i) {
+    const int e = 4 * (threadIdx.x + THREADS * i);
+    a[i] = ld4(r + ck.flat_off, e, ck.len);
+    q[i] = ld4(p + ck.flat_off, e, ck.len);
+    xx[i] = ld4(x + ck.flat_off, e, ck.len);
+  }
+#pragma unroll
+  for (int i = 0; i < V; ++i) {
+    const int e = 4 * (threadIdx.x + THREADS * i);
+    const float4 nx = x_update(xx[i], alpha, q[i], out_scale), np = dir_update(a[i], beta, q[i]);
+    st4(x + ck.flat_off, e, ck.len, nx);
+    st4(p + ck.flat_off, e, ck.len, np);
+  }
+}
+
 // K1: den = (cg_alpha*Hp).p   (cg.py:42,44,46) — reads Hp, p: 8*N bytes.
+// Unlike K2's and K3's, this pass over a chunk is not a function shared with the resident kernel's first streamed tail: its
+// loop is written out here and there.  As a function of its own it compiles to other instructions in both places — branches
+// on the shift where there are 16 selects now, and half of the packed fp32 operations split.  The arithmetic goes through
+// shifted_product and php_term like everywhere else.
 template <typename Src>
 __global__ __launch_bounds__(kThreads) void k_cg_dot(Src src, const bhg_chunk* __restrict__ chunks,
                                                      int n_chunks, const float* __restrict__ p,
@@ -247,12 +288,8 @@ __global__ __launch_bounds__(kThreads) void k_cg_dot(Src src, const bhg_chunk* _
     }
 #pragma unroll
     for (int i = 0; i < kVecPerThread; ++i) {
-      if (shift != 0.f) {
-        h[i].x = add_rn(h[i].x, mul_rn(shift, q[i].x)); h[i].y = add_rn(h[i].y, mul_rn(shift, q[i].y));
-        h[i].z = add_rn(h[i].z, mul_rn(shift, q[i].z)); h[i].w = add_rn(h[i].w, mul_rn(shift, q[i].w));
-      }
-      acc += (double)mul_rn(cg_alpha, h[i].x) * q[i].x + (double)mul_rn(cg_alpha, h[i].y) * q[i].y +
-             (double)mul_rn(cg_alpha, h[i].z) * q[i].z + (double)mul_rn(cg_alpha, h[i].w) * q[i].w;
+      h[i] = shifted_product(h[i], shift, q[i]);
+      acc += php_term(cg_alpha, h[i], q[i]);
     }
   }
   const double s = block_sum(acc, red);
@@ -275,31 +312,8 @@ __global__ __launch_bounds__(kThreads) void k_cg_resid(Src src, const bhg_chunk*
   const float alpha = (float)rr / (float)den;  // fp32 divide of fp32 dots, as torch does
   const typename Src::Ctx cx = src.ctx();
   double acc = 0.0;
-  for (int c = blockIdx.x; c < n_chunks; c += gridDim.x) {
-    const bhg_chunk ck = chunks[c];
-    float* rrp = r + ck.flat_off;
-    float4 h[kVecPerThread], a[kVecPerThread];
-#pragma unroll
-    for (int i = 0; i < kVecPerThread; ++i) {
-      const int e = 4 * (threadIdx.x + kThreads * i);
-      h[i] = src.load(cx, ck, e);
-      a[i] = ld4(rrp, e, ck.len);
-      if (shift != 0.f) {  // (12+4)*N bytes in this case: the direction is re-read for the diagonal term
-        const float4 q = ld4(p + ck.flat_off, e, ck.len);
-        h[i].x = add_rn(h[i].x, mul_rn(shift, q.x)); h[i].y = add_rn(h[i].y, mul_rn(shift, q.y));
-        h[i].z = add_rn(h[i].z, mul_rn(shift, q.z)); h[i].w = add_rn(h[i].w, mul_rn(shift, q.w));
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < kVecPerThread; ++i) {
-      const int e = 4 * (threadIdx.x + kThreads * i);
-      float4 nr;
-      nr.x = sub_rn(a[i].x, mul_rn(alpha, h[i].x)); nr.y = sub_rn(a[i].y, mul_rn(alpha, h[i].y));
-      nr.z = sub_rn(a[i].z, mul_rn(alpha, h[i].z)); nr.w = sub_rn(a[i].w, mul_rn(alpha, h[i].w));
-      st4(rrp, e, ck.len, nr);
-      acc += (double)nr.x * nr.x + (double)nr.y * nr.y + (double)nr.z * nr.z + (double)nr.w * nr.w;
-    }
-  }
+  for (int c = blockIdx.x; c < n_chunks; c += gridDim.x)
+    cg_resid_chunk<kVecPerThread, kThreads>(src, cx, chunks[c], r, p, shift, alpha, acc);
   const double s = block_sum(acc, red);
   if (threadIdx.x == 0) {
     partR_new[blockIdx.x] = s;
@@ -325,32 +339,8 @@ __global__ __launch_bounds__(kThreads) void k_cg_dir(const bhg_chunk* __restrict
   const double rr_old = scal[S_RR_OLD];
   const float alpha = (float)scal[S_ALPHA];
   const float beta = (float)rr_new / (float)rr_old;
-  for (int c = blockIdx.x; c < n_chunks; c += gridDim.x) {
-    const bhg_chunk ck = chunks[c];
-    float4 a[kVecPerThread], q[kVecPerThread], xx[kVecPerThread];
-#pragma unroll
-    for (int i = 0; i < kVecPerThread; ++i) {
-      const int e = 4 * (threadIdx.x + kThreads * i);
-      a[i] = ld4(r + ck.flat_off, e, ck.len);
-      q[i] = ld4(p + ck.flat_off, e, ck.len);
-      xx[i] = ld4(x + ck.flat_off, e, ck.len);
-    }
-#pragma unroll
-    for (int i = 0; i < kVecPerThread; ++i) {
-      const int e = 4 * (threadIdx.x + kThreads * i);
-      float4 nx, np;
-      nx.x = add_rn(xx[i].x, mul_rn(alpha, q[i].x)); nx.y = add_rn(xx[i].y, mul_rn(alpha, q[i].y));
-      nx.z = add_rn(xx[i].z, mul_rn(alpha, q[i].z)); nx.w = add_rn(xx[i].w, mul_rn(alpha, q[i].w));
-      if (out_scale != 0.f) {
-        nx.x = mul_rn(out_scale, nx.x); nx.y = mul_rn(out_scale, nx.y);
-        nx.z = mul_rn(out_scale, nx.z); nx.w = mul_rn(out_scale, nx.w);
-      }
-      np.x = add_rn(a[i].x, mul_rn(beta, q[i].x)); np.y = add_rn(a[i].y, mul_rn(beta, q[i].y));
-      np.z = add_rn(a[i].z, mul_rn(beta, q[i].z)); np.w = add_rn(a[i].w, mul_rn(beta, q[i].w));
-      st4(x + ck.flat_off, e, ck.len, nx);
-      st4(p + ck.flat_off, e, ck.len, np);
-    }
-  }
+  for (int c = blockIdx.x; c < n_chunks; c += gridDim.x)
+    cg_dir_chunk<kVecPerThread, kThreads>(chunks[c], x, r, p, alpha, beta, out_scale);
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     scal[S_RR_NEW] = rr_new;
     scal[S_BETA] = (double)beta;
@@ -533,15 +523,11 @@ __global__ __launch_bounds__(kResThreads, 2) void k_cg_resident(
 #pragma unroll
     for (int j = 0; j < kResV; ++j) {
       const float4 qq = Q(i, j);
-      if (shift != 0.f) {  // H p = (raw HVP) + shift * p: the Hessian's diagonal part never round-trips through HBM
-        h[i][j].x = add_rn(h[i][j].x, mul_rn(shift, qq.x)); h[i][j].y = add_rn(h[i][j].y, mul_rn(shift, qq.y));
-        h[i][j].z = add_rn(h[i][j].z, mul_rn(shift, qq.z)); h[i][j].w = add_rn(h[i][j].w, mul_rn(shift, qq.w));
-      }
-      acc += (double)mul_rn(cg_alpha, h[i][j].x) * qq.x + (double)mul_rn(cg_alpha, h[i][j].y) * qq.y +
-             (double)mul_rn(cg_alpha, h[i][j].z) * qq.z + (double)mul_rn(cg_alpha, h[i][j].w) * qq.w;
+      h[i][j] = shifted_product(h[i][j], shift, qq);
+      acc += php_term(cg_alpha, h[i][j], qq);
     }
   }
-  if (HYBRID) {   // streamed chunks: (cg_alpha*Hp).p without keeping anything
+  if (HYBRID) {   // streamed chunks: (cg_alpha*Hp).p without keeping anything (k_cg_dot's loop, written out: see there)
     for (int c = NSLOT * G + blockIdx.x; c < n_chunks; c += G) {
       const bhg_chunk ck = chunks[c];
       float4 hv[kResV], qv[kResV];
@@ -553,12 +539,8 @@ __global__ __launch_bounds__(kResThreads, 2) void k_cg_resident(
       }
 #pragma unroll
       for (int j = 0; j < kResV; ++j) {
-        if (shift != 0.f) {
-          hv[j].x = add_rn(hv[j].x, mul_rn(shift, qv[j].x)); hv[j].y = add_rn(hv[j].y, mul_rn(shift, qv[j].y));
-          hv[j].z = add_rn(hv[j].z, mul_rn(shift, qv[j].z)); hv[j].w = add_rn(hv[j].w, mul_rn(shift, qv[j].w));
-        }
-        acc += (double)mul_rn(cg_alpha, hv[j].x) * qv[j].x + (double)mul_rn(cg_alpha, hv[j].y) * qv[j].y +
-               (double)mul_rn(cg_alpha, hv[j].z) * qv[j].z + (double)mul_rn(cg_alpha, hv[j].w) * qv[j].w;
+        hv[j] = shifted_product(hv[j], shift, qv[j]);
+        acc += php_term(cg_alpha, hv[j], qv[j]);
       }
     }
   }
@@ -570,53 +552,16 @@ __global__ __launch_bounds__(kResThreads, 2) void k_cg_resident(
   // ---- phase 2a: r' = r - a*Hp (kept in h, stored once) ; partial r'.r' ; ARRIVE
   acc = 0.0;
   resident_stream<NSLOT>(r, chunks, n_chunks, [&](int i, int j, float4 rv) {
-    float4 nr;
-    nr.x = sub_rn(rv.x, mul_rn(alpha, h[i][j].x)); nr.y = sub_rn(rv.y, mul_rn(alpha, h[i][j].y));
-    nr.z = sub_rn(rv.z, mul_rn(alpha, h[i][j].z)); nr.w = sub_rn(rv.w, mul_rn(alpha, h[i][j].w));
-    h[i][j] = nr;
-    acc += (double)nr.x * nr.x + (double)nr.y * nr.y + (double)nr.z * nr.z + (double)nr.w * nr.w;
-    return nr;
+    return h[i][j] = resid_update(rv, alpha, h[i][j], acc);
   });
-  if (HYBRID) {   // streamed chunks: r' = r - a*Hp with Hp (and p for the shift) read again
-    for (int c = NSLOT * G + blockIdx.x; c < n_chunks; c += G) {
-      const bhg_chunk ck = chunks[c];
-      float4 hv[kResV], rv[kResV];
-#pragma unroll
-      for (int j = 0; j < kResV; ++j) {
-        const int e = 4 * (threadIdx.x + kResThreads * j);
-        hv[j] = src.load(cx, ck, e);
-        rv[j] = ld4(r + ck.flat_off, e, ck.len);
-        if (shift != 0.f) {
-          const float4 qq = ld4(p + ck.flat_off, e, ck.len);
-          hv[j].x = add_rn(hv[j].x, mul_rn(shift, qq.x)); hv[j].y = add_rn(hv[j].y, mul_rn(shift, qq.y));
-          hv[j].z = add_rn(hv[j].z, mul_rn(shift, qq.z)); hv[j].w = add_rn(hv[j].w, mul_rn(shift, qq.w));
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < kResV; ++j) {
-        const int e = 4 * (threadIdx.x + kResThreads * j);
-        float4 nr;
-        nr.x = sub_rn(rv[j].x, mul_rn(alpha, hv[j].x)); nr.y = sub_rn(rv[j].y, mul_rn(alpha, hv[j].y));
-        nr.z = sub_rn(rv[j].z, mul_rn(alpha, hv[j].z)); nr.w = sub_rn(rv[j].w, mul_rn(alpha, hv[j].w));
-        st4(r + ck.flat_off, e, ck.len, nr);
-        acc += (double)nr.x * nr.x + (double)nr.y * nr.y + (double)nr.z * nr.z + (double)nr.w * nr.w;
-      }
-    }
-  }
+  if (HYBRID)   // streamed chunks: r' = r - a*Hp with Hp (and p for the shift) read again
+    for (int c = NSLOT * G + blockIdx.x; c < n_chunks; c += G)
+      cg_resid_chunk<kResV, kResThreads>(src, cx, chunks[c], r, p, shift, alpha, acc);
   grid_arrive(block_sum_res(acc, red), partR_new, barrier_words);
 
   // ---- phase 2b (hides the second barrier): x += a*p [x <- out_scale*x on the last step]
-  resident_stream<NSLOT>(x, chunks, n_chunks, [&](int i, int j, float4 xv) {
-    const float4 qq = Q(i, j);
-    float4 nx;
-    nx.x = add_rn(xv.x, mul_rn(alpha, qq.x)); nx.y = add_rn(xv.y, mul_rn(alpha, qq.y));
-    nx.z = add_rn(xv.z, mul_rn(alpha, qq.z)); nx.w = add_rn(xv.w, mul_rn(alpha, qq.w));
-    if (out_scale != 0.f) {
-      nx.x = mul_rn(out_scale, nx.x); nx.y = mul_rn(out_scale, nx.y);
-      nx.z = mul_rn(out_scale, nx.z); nx.w = mul_rn(out_scale, nx.w);
-    }
-    return nx;
-  });
+  resident_stream<NSLOT>(x, chunks, n_chunks,
+                         [&](int i, int j, float4 xv) { return x_update(xv, alpha, Q(i, j), out_scale); });
   const double rr_new = grid_wait_sum(partR_new, barrier_words, (unsigned)G * (2u * iter + 2u), red,
                                       barrier_words + 1, spin_limit);
   const float beta = (float)rr_new / (float)rr;
@@ -630,42 +575,13 @@ __global__ __launch_bounds__(kResThreads, 2) void k_cg_resident(
 #pragma unroll
       for (int j = 0; j < kResV; ++j) {
         const int e = 4 * (threadIdx.x + kResThreads * j);
-        const float4 qq = Q(i, j);
-        float4 np;
-        np.x = add_rn(h[i][j].x, mul_rn(beta, qq.x)); np.y = add_rn(h[i][j].y, mul_rn(beta, qq.y));
-        np.z = add_rn(h[i][j].z, mul_rn(beta, qq.z)); np.w = add_rn(h[i][j].w, mul_rn(beta, qq.w));
-        st4(p + ck.flat_off, e, ck.len, np);
+        st4(p + ck.flat_off, e, ck.len, dir_update(h[i][j], beta, Q(i, j)));
       }
     }
   }
-  if (HYBRID) {   // streamed chunks: x += a*p and p = r' + b*p in one pass (r', p, x read; x, p written), like k_cg_dir
-    for (int c = NSLOT * G + blockIdx.x; c < n_chunks; c += G) {
-      const bhg_chunk ck = chunks[c];
-      float4 rv[kResV], qv[kResV], xv[kResV];
-#pragma unroll
-      for (int j = 0; j < kResV; ++j) {
-        const int e = 4 * (threadIdx.x + kResThreads * j);
-        rv[j] = ld4(r + ck.flat_off, e, ck.len);
-        qv[j] = ld4(p + ck.flat_off, e, ck.len);
-        xv[j] = ld4(x + ck.flat_off, e, ck.len);
-      }
-#pragma unroll
-      for (int j = 0; j < kResV; ++j) {
-        const int e = 4 * (threadIdx.x + kResThreads * j);
-        float4 nx, np;
-        nx.x = add_rn(xv[j].x, mul_rn(alpha, qv[j].x)); nx.y = add_rn(xv[j].y, mul_rn(alpha, qv[j].y));
-        nx.z = add_rn(xv[j].z, mul_rn(alpha, qv[j].z)); nx.w = add_rn(xv[j].w, mul_rn(alpha, qv[j].w));
-        if (out_scale != 0.f) {
-          nx.x = mul_rn(out_scale, nx.x); nx.y = mul_rn(out_scale, nx.y);
-          nx.z = mul_rn(out_scale, nx.z); nx.w = mul_rn(out_scale, nx.w);
-        }
-        np.x = add_rn(rv[j].x, mul_rn(beta, qv[j].x)); np.y = add_rn(rv[j].y, mul_rn(beta, qv[j].y));
-        np.z = add_rn(rv[j].z, mul_rn(beta, qv[j].z)); np.w = add_rn(rv[j].w, mul_rn(beta, qv[j].w));
-        st4(x + ck.flat_off, e, ck.len, nx);
-        st4(p + ck.flat_off, e, ck.len, np);
-      }
-    }
-  }
+  if (HYBRID)   // streamed chunks: x += a*p and p = r' + b*p in one pass (r', p, x read; x, p written), like k_cg_dir
+    for (int c = NSLOT * G + blockIdx.x; c < n_chunks; c += G)
+      cg_dir_chunk<kResV, kResThreads>(chunks[c], x, r, p, alpha, beta, out_scale);
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     scal[S_RR_OLD] = rr;
     scal[S_PHP] = den;
@@ -688,9 +604,7 @@ __global__ __launch_bounds__(kThreads) void k_sqnorm(PtrTab tab, const bhg_chunk
 #pragma unroll
     for (int i = 0; i < kVecPerThread; ++i) t[i] = ld4(src, 4 * (threadIdx.x + kThreads * i), ck.len);
 #pragma unroll
-    for (int i = 0; i < kVecPerThread; ++i)
-      acc += (double)t[i].x * t[i].x + (double)t[i].y * t[i].y + (double)t[i].z * t[i].z +
-             (double)t[i].w * t[i].w;
+    for (int i = 0; i < kVecPerThread; ++i) acc += sqnorm4(t[i]);
   }
   const double s = block_sum(acc, red);
   if (threadIdx.x == 0) part[blockIdx.x] = s;
@@ -731,10 +645,7 @@ __global__ __launch_bounds__(kThreads) void k_axpy_multi(PtrTab dst, PtrTab src,
 #pragma unroll
     for (int i = 0; i < kVecPerThread; ++i) {
       const int e = 4 * (threadIdx.x + kThreads * i);
-      float4 o;
-      o.x = add_rn(dv[i].x, mul_rn(a, sv[i].x)); o.y = add_rn(dv[i].y, mul_rn(a, sv[i].y));
-      o.z = add_rn(dv[i].z, mul_rn(a, sv[i].z)); o.w = add_rn(dv[i].w, mul_rn(a, sv[i].w));
-      st4(d, e, ck.len, o);
+      st4(d, e, ck.len, add_scaled4(dv[i], a, sv[i]));
     }
   }
 }
@@ -783,6 +694,24 @@ __global__ __launch_bounds__(kThreads) void k_sama_adam(PtrTab tv, PtrTab tg, Pt
 }
 
 inline int grid_for(int n_chunks) { return n_chunks < kMaxBlocks ? (n_chunks > 0 ? n_chunks : 1) : kMaxBlocks; }
+
+// The CG part of the workspace (layout: bhg_common.hpp), carved once.
+struct CgWs {
+  double* scal;
+  double* partP;
+  unsigned* barrier;
+  explicit CgWs(void* ws)
+      : scal(at<double>(ws, kWsScal)), partP(at<double>(ws, kWsPartP)), barrier(at<unsigned>(ws, kWsBarrier)),
+        partR(at<double>(ws, kWsPartR)) {}
+  // The producer of r.r for iteration `iter` (k_cg_init for 0) wrote partR[iter & 1]; the iteration writes the other.
+  double* partR_old(int iter) const { return partR + (size_t)(iter & 1) * kMaxBlocks; }
+  double* partR_new(int iter) const { return partR + (size_t)((iter + 1) & 1) * kMaxBlocks; }
+
+ private:
+  double* partR;
+  template <typename T>
+  static T* at(void* ws, size_t off) { return reinterpret_cast<T*>(static_cast<char*>(ws) + off); }
+};
 
 // Per-device caches (a process may drive several GPUs): index = current HIP device, -1 = not probed yet.
 constexpr int kMaxDevices = 64;
@@ -991,10 +920,9 @@ int bhg_cg_init_masked(const void* const* vec, int T, const bhg_chunk* chunks_de
   hipStream_t st = static_cast<hipStream_t>(stream);
   PtrTab tab;
   if (int rc = make_table(&tab, vec, T, ws, 0, st)) return rc;
-  char* w = static_cast<char*>(ws);
+  const CgWs w(ws);
   hipLaunchKernelGGL(k_cg_init, dim3(grid_for(n_chunks)), dim3(kThreads), 0, st, tab, chunks_dev, n_chunks, x,
-                     r, p, reinterpret_cast<double*>(w + kWsPartR),
-                     reinterpret_cast<unsigned*>(w + kWsBarrier), reinterpret_cast<double*>(w + kWsScal), keep_mask);
+                     r, p, w.partR_old(0), w.barrier, w.scal, keep_mask);
   BHG_HIP_CHECK(hipGetLastError());
   return BHG_OK;
 }
@@ -1055,18 +983,15 @@ int bhg_cg_resident_ok(void) {
   int ok = 0;
   do {
     if (hipMemset(ws, 0, bytes) != hipSuccess) break;
-    char* w = static_cast<char*>(ws);
-    double* partR = reinterpret_cast<double*>(w + kWsPartR);
+    const CgWs w(ws);
     HvpTensors tab;
     memset(&tab, 0, sizeof(tab));
     hipLaunchKernelGGL((k_cg_resident<kResMax, 0, false>), dim3(G), dim3(kResThreads), 0, nullptr, tab, (const bhg_chunk*)nullptr, 0,
                        (float*)nullptr, (float*)nullptr, (float*)nullptr, 1.0f, 0, 0.0f, 0.0f,
-                       (const double*)partR, partR + kMaxBlocks, reinterpret_cast<double*>(w + kWsPartP),
-                       reinterpret_cast<unsigned*>(w + kWsBarrier), reinterpret_cast<double*>(w + kWsScal),
-                       1u << 16);
+                       (const double*)w.partR_old(0), w.partR_new(0), w.partP, w.barrier, w.scal, 1u << 16);
     if (hipGetLastError() != hipSuccess) break;
     unsigned words[2] = {0, 1};
-    if (hipMemcpy(words, w + kWsBarrier, sizeof(words), hipMemcpyDeviceToHost) != hipSuccess) break;
+    if (hipMemcpy(words, w.barrier, sizeof(words), hipMemcpyDeviceToHost) != hipSuccess) break;
     ok = (words[1] == 0 && words[0] == 2u * (unsigned)G) ? 1 : 0;
   } while (0);
   (void)hipFree(ws);
@@ -1093,16 +1018,21 @@ const unsigned* bhg_cg_timeout_flag_dev(const void* ws) {
 
 // One CG iteration on the product source `src` (validated by the caller): the streaming trio or one resident launch.
 extern "C++" {
+// One launch of an instance of the resident kernel, one workgroup per CU; its dynamic LDS follows from NLDS (the parked
+// direction slices).  `ea` / `eb`: the timing events, or NULL.
+template <int NSLOT, int NLDS, bool HYBRID, typename Src>
+static void launch_resident(const Src& src, const bhg_chunk* chunks_dev, int n_chunks, float* x, float* r, float* p, float cg_alpha,
+                            int iter, float out_scale, float hvp_shift, const CgWs& w, hipStream_t st, hipEvent_t ea, hipEvent_t eb) {
+  constexpr size_t lds_bytes = (size_t)NLDS * kResV * kResThreads * sizeof(float4);
+  hipExtLaunchKernelGGL((k_cg_resident<NSLOT, NLDS, HYBRID, Src>), dim3(num_cus()), dim3(kResThreads), lds_bytes, st, ea, eb, 0, src,
+                        chunks_dev, n_chunks, x, r, p, cg_alpha, iter, out_scale, hvp_shift, (const double*)w.partR_old(iter),
+                        w.partR_new(iter), w.partP, w.barrier, w.scal, spin_limit());
+}
+
 template <typename Src>
 static int cg_step_launch(const Src& src, const bhg_chunk* chunks_dev, int n_chunks, float* x, float* r, float* p, float cg_alpha,
                           int iter, float out_scale, float hvp_shift, int variant, void* ws, hipStream_t st) {
-  char* w = static_cast<char*>(ws);
-  double* scal = reinterpret_cast<double*>(w + kWsScal);
-  double* partP = reinterpret_cast<double*>(w + kWsPartP);
-  double* partR = reinterpret_cast<double*>(w + kWsPartR);
-  // The producer of r.r for iteration `iter` wrote partR[iter & 1]; this iteration writes the other.
-  double* partR_old = partR + (size_t)(iter & 1) * kMaxBlocks;
-  double* partR_new = partR + (size_t)((iter + 1) & 1) * kMaxBlocks;
+  const CgWs w(ws);
   // How many partials the previous producer wrote travels in scal[S_NPART0 + parity], and a streamed
   // iteration credits the resident kernel's arrival counter (k_cg_dir), so the stream and resident
   // variants may be mixed between iterations of one solve.
@@ -1113,33 +1043,24 @@ static int cg_step_launch(const Src& src, const bhg_chunk* chunks_dev, int n_chu
     // start event rides on the first kernel, stop event on the last: the span is the whole
     // iteration's recurrence including the two inter-kernel boundaries.
     hipExtLaunchKernelGGL(k_cg_dot<Src>, dim3(n_stream), dim3(kThreads), 0, st, timed ? ea : nullptr, nullptr, 0, src,
-                          chunks_dev, n_chunks, (const float*)p, cg_alpha, hvp_shift, partP);
+                          chunks_dev, n_chunks, (const float*)p, cg_alpha, hvp_shift, w.partP);
     hipLaunchKernelGGL(k_cg_resid<Src>, dim3(n_stream), dim3(kThreads), 0, st, src, chunks_dev, n_chunks, r,
-                       (const float*)p, hvp_shift, (const double*)partP, (const double*)partR_old, partR_new, n_stream, iter, scal);
+                       (const float*)p, hvp_shift, (const double*)w.partP, (const double*)w.partR_old(iter), w.partR_new(iter),
+                       n_stream, iter, w.scal);
     hipExtLaunchKernelGGL(k_cg_dir, dim3(n_stream), dim3(kThreads), 0, st, nullptr, timed ? eb : nullptr, 0,
-                          chunks_dev, n_chunks, x, (const float*)r, p, (const double*)partR_new, n_stream,
-                          out_scale, scal, reinterpret_cast<unsigned*>(w + kWsBarrier), 2u * (unsigned)num_cus());
+                          chunks_dev, n_chunks, x, (const float*)r, p, (const double*)w.partR_new(iter), n_stream,
+                          out_scale, w.scal, w.barrier, 2u * (unsigned)num_cus());
   } else {
     const int G = num_cus();
-    if (n_chunks <= G * kResMax) {   // register-only instance: fastest while it fits (11.5 M elements)
-      hipExtLaunchKernelGGL((k_cg_resident<kResMax, 0, false, Src>), dim3(G), dim3(kResThreads), 0, st, timed ? ea : nullptr,
-                            timed ? eb : nullptr, 0, src, chunks_dev, n_chunks, x, r, p, cg_alpha, iter, out_scale,
-                            hvp_shift, (const double*)partR_old, partR_new, partP,
-                            reinterpret_cast<unsigned*>(w + kWsBarrier), scal, spin_limit());
-    } else {
-      constexpr size_t lds = (size_t)kResLds * kResV * kResThreads * sizeof(float4);
+    hipEvent_t const e0 = timed ? ea : nullptr, e1 = timed ? eb : nullptr;
+    if (n_chunks > G * kResMax)
       BHG_REQUIRE(resident_lds_instances_ok(), "this device does not grant the resident kernel's 144 KiB of dynamic LDS");
-      if (n_chunks <= G * kResMaxLds)   // LDS-assisted instance: 9 direction slices per workgroup parked in LDS (15.7 M elements)
-        hipExtLaunchKernelGGL((k_cg_resident<kResMaxLds, kResLds, false, Src>), dim3(G), dim3(kResThreads), lds, st, timed ? ea : nullptr,
-                              timed ? eb : nullptr, 0, src, chunks_dev, n_chunks, x, r, p, cg_alpha, iter, out_scale,
-                              hvp_shift, (const double*)partR_old, partR_new, partP,
-                              reinterpret_cast<unsigned*>(w + kWsBarrier), scal, spin_limit());
-      else                              // hybrid instance: 14 resident slots per workgroup, the rest streamed in the same launch
-        hipExtLaunchKernelGGL((k_cg_resident<kResHyb, kResLds, true, Src>), dim3(G), dim3(kResThreads), lds, st, timed ? ea : nullptr,
-                              timed ? eb : nullptr, 0, src, chunks_dev, n_chunks, x, r, p, cg_alpha, iter, out_scale,
-                              hvp_shift, (const double*)partR_old, partR_new, partP,
-                              reinterpret_cast<unsigned*>(w + kWsBarrier), scal, spin_limit());
-    }
+    if (n_chunks <= G * kResMax)           // register-only instance: fastest while it fits (11.5 M elements)
+      launch_resident<kResMax, 0, false>(src, chunks_dev, n_chunks, x, r, p, cg_alpha, iter, out_scale, hvp_shift, w, st, e0, e1);
+    else if (n_chunks <= G * kResMaxLds)   // LDS-assisted instance: 9 direction slices per workgroup parked in LDS (15.7 M elements)
+      launch_resident<kResMaxLds, kResLds, false>(src, chunks_dev, n_chunks, x, r, p, cg_alpha, iter, out_scale, hvp_shift, w, st, e0, e1);
+    else                                   // hybrid instance: 14 resident slots per workgroup, the rest streamed in the same launch
+      launch_resident<kResHyb, kResLds, true>(src, chunks_dev, n_chunks, x, r, p, cg_alpha, iter, out_scale, hvp_shift, w, st, e0, e1);
   }
   BHG_HIP_CHECK(hipGetLastError());
   return BHG_OK;
@@ -1205,17 +1126,11 @@ int bhg_cg_phase(int phase, const void* const* hvp, int T, const bhg_chunk* chun
   if (n_chunks == 0) return BHG_OK;
   BHG_REQUIRE(x && r && p, "state vector is NULL");
   hipStream_t st = static_cast<hipStream_t>(stream);
-  char* w = static_cast<char*>(ws);
-  double* scal = reinterpret_cast<double*>(w + kWsScal);
-  double* partP = reinterpret_cast<double*>(w + kWsPartP);
-  double* partR = reinterpret_cast<double*>(w + kWsPartR);
-  double* partR_old = partR + (size_t)(iter & 1) * kMaxBlocks;
-  double* partR_new = partR + (size_t)((iter + 1) & 1) * kMaxBlocks;
+  const CgWs w(ws);
   const int n_stream = grid_for(n_chunks);
   if (phase == 2) {
     hipLaunchKernelGGL(k_cg_dir, dim3(n_stream), dim3(kThreads), 0, st, chunks_dev, n_chunks, x, (const float*)r, p,
-                       (const double*)partR_new, n_stream, out_scale, scal, reinterpret_cast<unsigned*>(w + kWsBarrier),
-                       2u * (unsigned)num_cus());
+                       (const double*)w.partR_new(iter), n_stream, out_scale, w.scal, w.barrier, 2u * (unsigned)num_cus());
     BHG_HIP_CHECK(hipGetLastError());
     return BHG_OK;
   }
@@ -1223,20 +1138,20 @@ int bhg_cg_phase(int phase, const void* const* hvp, int T, const bhg_chunk* chun
   if (int rc = make_table(&tab.tab, hvp, T, ws, 0, st)) return rc;
   if (phase == 0)
     hipLaunchKernelGGL(k_cg_dot<HvpTensors>, dim3(n_stream), dim3(kThreads), 0, st, tab, chunks_dev, n_chunks, (const float*)p, cg_alpha,
-                       hvp_shift, partP);
+                       hvp_shift, w.partP);
   else
     hipLaunchKernelGGL(k_cg_resid<HvpTensors>, dim3(n_stream), dim3(kThreads), 0, st, tab, chunks_dev, n_chunks, r, (const float*)p,
-                       hvp_shift, (const double*)partP, (const double*)partR_old, partR_new, n_stream, iter, scal);
+                       hvp_shift, (const double*)w.partP, (const double*)w.partR_old(iter), w.partR_new(iter), n_stream, iter,
+                       w.scal);
   BHG_HIP_CHECK(hipGetLastError());
   return BHG_OK;
 }
 
 double* bhg_cg_partials_dev(void* ws, int which, int iter) {
-  char* w = static_cast<char*>(ws);
-  if (which == 0) return reinterpret_cast<double*>(w + kWsPartP);
-  double* partR = reinterpret_cast<double*>(w + kWsPartR);
-  if (which == 1) return partR + (size_t)((iter + 1) & 1) * kMaxBlocks;
-  return partR;   // which == 2: the r.r partials bhg_cg_init wrote (consumed by iteration 0)
+  const CgWs w(ws);
+  if (which == 0) return w.partP;
+  if (which == 1) return w.partR_new(iter);
+  return w.partR_old(0);   // which == 2: the r.r partials bhg_cg_init wrote (consumed by iteration 0)
 }
 
 int bhg_cg_partials_count(void) { return kMaxBlocks; }

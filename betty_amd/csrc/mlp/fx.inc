@@ -102,7 +102,7 @@ __device__ __forceinline__ void fx_small_body(const FxSmallArgs& a, const int sb
   if (grp == 0) {   // (one wave: the five inner products of the block's 64 outputs with the narrow state, fixed order)
     double q0 = 0.0, q1 = 0.0, q2 = 0.0, q3 = 0.0, q4 = 0.0;
     if (out_idx >= 0) {
-      const float v = fz_mul(a.invG, (redf[0][col] + redf[1][col]) + (redf[2][col] + redf[3][col]));
+      const float v = mul_rn(a.invG, (redf[0][col] + redf[1][col]) + (redf[2][col] + redf[3][col]));
       a.rawn[out_idx] = v;
       const double hv = (double)v + (double)a.shift * (double)pv;
       q0 = (double)pv * (double)v; q1 = (double)pv * (double)pv; q2 = (double)rv * (double)rv; q3 = (double)rv * hv; q4 = hv * hv;
@@ -327,9 +327,9 @@ __global__ __launch_bounds__(256) void k_fx_step(FxStepArgs a) {
   }
   auto narrow = [&](const float rv, const float pv, const float wv, float& rnew, float& pnew) {
     float hv = wv;
-    if (h.shift != 0.f) hv = fz_add(hv, fz_mul(h.shift, pv));
-    rnew = fz_add(h.neumann ? pv : rv, -fz_mul(alpha, hv));
-    pnew = h.neumann ? rnew : fz_add(rnew, fz_mul(beta, pv));
+    if (h.shift != 0.f) hv = add_rn(hv, mul_rn(h.shift, pv));
+    rnew = add_rn(h.neumann ? pv : rv, -mul_rn(alpha, hv));
+    pnew = h.neumann ? rnew : add_rn(rnew, mul_rn(beta, pv));
   };
   if (is_narrow) {
     if (ne < h.Nn) {
@@ -346,10 +346,10 @@ __global__ __launch_bounds__(256) void k_fx_step(FxStepArgs a) {
     if (m[u] < h.B) {
 #define BHG_FX1(c)                                                          \
       {                                                                     \
-        float hv = fz_mul(h.invG, w0[u].c);                                 \
-        if (h.shift != 0.f) hv = fz_add(hv, fz_mul(h.shift, p0[u].c));      \
-        gr.c = fz_add(h.neumann ? p0[u].c : r0[u].c, -fz_mul(alpha, hv));   \
-        gp.c = h.neumann ? gr.c : fz_add(gr.c, fz_mul(beta, p0[u].c));      \
+        float hv = mul_rn(h.invG, w0[u].c);                                 \
+        if (h.shift != 0.f) hv = add_rn(hv, mul_rn(h.shift, p0[u].c));      \
+        gr.c = add_rn(h.neumann ? p0[u].c : r0[u].c, -mul_rn(alpha, hv));   \
+        gp.c = h.neumann ? gr.c : add_rn(gr.c, mul_rn(beta, p0[u].c));      \
       }
       BHG_FX1(x) BHG_FX1(y) BHG_FX1(z) BHG_FX1(w)
 #undef BHG_FX1

@@ -174,8 +174,8 @@ void BHG_GRAW_NAME(GrawArgs g) {
 #pragma unroll
           for (int u = 0; u < 4; ++u) {
             float hv = v[u];
-            if (shift_t != 0.f) hv = fz_add(hv, fz_mul(shift_t, e_p[j][u]));
-            gr[u] = fz_sub(e_r[j][u], fz_mul(alpha_t, hv));
+            if (shift_t != 0.f) hv = add_rn(hv, mul_rn(shift_t, e_p[j][u]));
+            gr[u] = sub_rn(e_r[j][u], mul_rn(alpha_t, hv));
           }
           *reinterpret_cast<f32x4*>(const_cast<float*>(q.Gr) + (int64_t)m * q.N + n0 + c4) = gr;
           if (em) {
@@ -184,8 +184,8 @@ void BHG_GRAW_NAME(GrawArgs g) {
             for (int u = 0; u < 4; ++u) {
               const int c = c4 + u;
               float hb = (sCol[c] + sCol[CT + c]) + (sCol[2 * CT + c] + sCol[3 * CT + c]);
-              if (shift_t != 0.f) hb = fz_add(hb, fz_mul(shift_t, pb0v[u]));
-              const float rbn = fz_sub(rb0v[u], fz_mul(alpha_t, hb));
+              if (shift_t != 0.f) hb = add_rn(hb, mul_rn(shift_t, pb0v[u]));
+              const float rbn = sub_rn(rb0v[u], mul_rn(alpha_t, hb));
               o[u] = (gr[u] + rbn) * e_m0[j][u];
             }
             *reinterpret_cast<f32x4*>(g.rh0p + ((int64_t)((n0 + c4) >> 4) * g.Bp + m) * 16 + ((n0 + c4) & 15)) = o;
@@ -385,8 +385,8 @@ void BHG_GRAW_NAME(GrawArgs g) {
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
           float hv = v[u];
-          if (shift_t != 0.f) hv = fz_add(hv, fz_mul(shift_t, e_p[j][u]));
-          gr[u] = fz_sub(e_r[j][u], fz_mul(alpha_t, hv));
+          if (shift_t != 0.f) hv = add_rn(hv, mul_rn(shift_t, e_p[j][u]));
+          gr[u] = sub_rn(e_r[j][u], mul_rn(alpha_t, hv));
         }
         *reinterpret_cast<f32x4*>(const_cast<float*>(q.Gr) + (int64_t)m * q.N + n0 + c4) = gr;
         if (em) {
@@ -395,8 +395,8 @@ void BHG_GRAW_NAME(GrawArgs g) {
           for (int u = 0; u < 4; ++u) {
             const int c = c4 + u;
             float hb = (sCol[c] + sCol[CT + c]) + (sCol[2 * CT + c] + sCol[3 * CT + c]);
-            if (shift_t != 0.f) hb = fz_add(hb, fz_mul(shift_t, pb0v[u]));
-            const float rbn = fz_sub(rb0v[u], fz_mul(alpha_t, hb));
+            if (shift_t != 0.f) hb = add_rn(hb, mul_rn(shift_t, pb0v[u]));
+            const float rbn = sub_rn(rb0v[u], mul_rn(alpha_t, hb));
             o[u] = (gr[u] + rbn) * e_m0[j][u];
           }
           *reinterpret_cast<f32x4*>(g.rh0p + ((int64_t)((n0 + c4) >> 4) * g.Bp + m) * 16 + ((n0 + c4) & 15)) = o;

@@ -87,8 +87,8 @@
         // which run as another block class of this launch and write Gf(p') into the OTHER slot (k_headu)
         if (lazy_addend2) {
           const float4 a2 = ld16(lazy_addend2 + (int64_t)b * K + k);
-          ad.x = fz_add(ad.x, fz_mul(lazy_beta, a2.x)); ad.y = fz_add(ad.y, fz_mul(lazy_beta, a2.y));
-          ad.z = fz_add(ad.z, fz_mul(lazy_beta, a2.z)); ad.w = fz_add(ad.w, fz_mul(lazy_beta, a2.w));
+          ad.x = add_rn(ad.x, mul_rn(lazy_beta, a2.x)); ad.y = add_rn(ad.y, mul_rn(lazy_beta, a2.y));
+          ad.z = add_rn(ad.z, mul_rn(lazy_beta, a2.z)); ad.w = add_rn(ad.w, mul_rn(lazy_beta, a2.w));
         }
 #endif
         v.x += ad.x; v.y += ad.y; v.z += ad.z; v.w += ad.w;

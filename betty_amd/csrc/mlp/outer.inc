@@ -34,35 +34,32 @@ struct FuseArgs {
                      // here (same roundings as k_cg_pdir) and written back, so no kernel of its own updates it (cg.py:53)
 };
 struct FuseAcc { double rr, rp, pp; };
-__device__ __forceinline__ float fz_mul(float a, float b) { return __fmul_rn(a, b); }
-__device__ __forceinline__ float fz_add(float a, float b) { return __fadd_rn(a, b); }
-__device__ __forceinline__ float fz_sub(float a, float b) { return __fsub_rn(a, b); }
 // one element: hv = raw HVP value, dv = direction (CG lazy: previous direction), av / bv = the two state values;
 // results back in av / bv, the direction actually used back in dv.
 template <int MODE>
 __device__ __forceinline__ void fuse_elem(const FuseArgs& f, float alpha, float beta, float hv, float& dv, float& av,
                                           float& bv, FuseAcc& acc, float alpha_prev = 0.f) {
   const float d_old = dv;
-  if (MODE == FUSE_CG && f.lazy) dv = fz_add(av, fz_mul(beta, dv));
-  if (f.shift != 0.f) hv = fz_add(hv, fz_mul(f.shift, dv));
+  if (MODE == FUSE_CG && f.lazy) dv = add_rn(av, mul_rn(beta, dv));
+  if (f.shift != 0.f) hv = add_rn(hv, mul_rn(f.shift, dv));
   if (MODE == FUSE_CG) {
-    const float nr = fz_sub(av, fz_mul(alpha, hv));
+    const float nr = sub_rn(av, mul_rn(alpha, hv));
     float nx = bv;
-    if (f.x_mode == 2) nx = fz_add(nx, fz_mul(alpha_prev, d_old));
-    if (f.x_mode != 1) nx = fz_add(nx, fz_mul(alpha, dv));
-    if (f.apply_out) nx = fz_mul(f.out_scale, nx);
+    if (f.x_mode == 2) nx = add_rn(nx, mul_rn(alpha_prev, d_old));
+    if (f.x_mode != 1) nx = add_rn(nx, mul_rn(alpha, dv));
+    if (f.apply_out) nx = mul_rn(f.out_scale, nx);
     acc.rr += (double)nr * nr;
     acc.rp += (double)nr * dv;
     acc.pp += (double)dv * dv;
     av = nr; bv = nx;
   } else {
-    const float nv = fz_sub(dv, fz_mul(alpha, hv));
+    const float nv = sub_rn(dv, mul_rn(alpha, hv));
     // x_mode for Neumann: 1 = leave the accumulator p alone this iteration, 2 = catch up: p = (p + v_in) + v' — v_in is
     // last iteration's v' (the direction just read), so these are the very roundings of two separate p += v' updates
     float np = bv;
-    if (f.x_mode == 2) np = fz_add(np, dv);
-    if (f.x_mode != 1) np = fz_add(np, nv);
-    if (f.apply_out) np = fz_mul(f.out_scale, np);
+    if (f.x_mode == 2) np = add_rn(np, dv);
+    if (f.x_mode != 1) np = add_rn(np, nv);
+    if (f.apply_out) np = mul_rn(f.out_scale, np);
     av = nv; bv = np;
   }
 }

@@ -182,8 +182,8 @@ __global__ __launch_bounds__(256) void k_hoist_reduce(HoistRedArgs ra) {
     }
     if (!ra.first) {   // the two roundings of p = r + (beta * p_old), applied to the products instead of the operands
       const float beta = (float)ra.scal[S_BETA];
-      v.x = fz_add(v.x, fz_mul(beta, gp.x)); v.y = fz_add(v.y, fz_mul(beta, gp.y));
-      v.z = fz_add(v.z, fz_mul(beta, gp.z)); v.w = fz_add(v.w, fz_mul(beta, gp.w));
+      v.x = add_rn(v.x, mul_rn(beta, gp.x)); v.y = add_rn(v.y, mul_rn(beta, gp.y));
+      v.z = add_rn(v.z, mul_rn(beta, gp.z)); v.w = add_rn(v.w, mul_rn(beta, gp.w));
     }
     *reinterpret_cast<float4*>(pr.G + idx * 4) = v;
     if (pr.G2) *reinterpret_cast<float4*>(pr.G2 + idx * 4) = v;
@@ -365,7 +365,7 @@ __device__ __forceinline__ float proj_scalars_finish(const SA& a, const ProjScal
                                 __HIP_MEMORY_SCOPE_AGENT);
   // cg.py:53 for the small slices (biases, head weight): p = r' + beta p
   if (eoff >= 0) {
-    const float np = fz_add(rv, fz_mul(s_beta, pv));
+    const float np = add_rn(rv, mul_rn(s_beta, pv));
     if (R.alt_wr) R.alt_wr[eidx] = np; else if (alt0) p0_wr[eidx] = np; else a.p_small[eoff] = np;
   }
   return s_beta;
@@ -480,8 +480,8 @@ __device__ __forceinline__ void proj_update_one(const ProjProb& pr, const ProjCo
       float4 bv = make_float4(0.f, 0.f, 0.f, 0.f), mv = make_float4(1.f, 1.f, 1.f, 1.f);
       if (pr.out) {
         if (own_b0) {
-          bv.x = fz_add(rb[u].x, fz_mul(beta, pb[u].x)); bv.y = fz_add(rb[u].y, fz_mul(beta, pb[u].y));
-          bv.z = fz_add(rb[u].z, fz_mul(beta, pb[u].z)); bv.w = fz_add(rb[u].w, fz_mul(beta, pb[u].w));
+          bv.x = add_rn(rb[u].x, mul_rn(beta, pb[u].x)); bv.y = add_rn(rb[u].y, mul_rn(beta, pb[u].y));
+          bv.z = add_rn(rb[u].z, mul_rn(beta, pb[u].z)); bv.w = add_rn(rb[u].w, mul_rn(beta, pb[u].w));
         } else if (pr.bias) {
           bv = bq[u];
         }
@@ -491,9 +491,9 @@ __device__ __forceinline__ void proj_update_one(const ProjProb& pr, const ProjCo
 #define BHG_PROJ1(c)                                                                  \
       {                                                                               \
         float hv = wv.c;                                                              \
-        if (pa.shift != 0.f) hv = fz_add(hv, fz_mul(pa.shift, p0[u].c));              \
-        gr.c = pr.Graw ? fz_sub(r0[u].c, fz_mul(alpha, hv)) : r0[u].c;                \
-        gp.c = pa.scal ? fz_add(gr.c, fz_mul(beta, p0[u].c)) : gr.c;                  \
+        if (pa.shift != 0.f) hv = add_rn(hv, mul_rn(pa.shift, p0[u].c));              \
+        gr.c = pr.Graw ? sub_rn(r0[u].c, mul_rn(alpha, hv)) : r0[u].c;                \
+        gp.c = pa.scal ? add_rn(gr.c, mul_rn(beta, p0[u].c)) : gr.c;                  \
       }
       BHG_PROJ1(x) BHG_PROJ1(y) BHG_PROJ1(z) BHG_PROJ1(w)
 #undef BHG_PROJ1

@@ -48,8 +48,8 @@ __global__ __launch_bounds__(kThreads) void k_cg_pdir(const bhg_chunk* __restric
     for (int i = 0; i < kVecPerThread; ++i) {
       const int e = 4 * (threadIdx.x + kThreads * i);
       float4 np;
-      np.x = fz_add(a[i].x, fz_mul(beta, q[i].x)); np.y = fz_add(a[i].y, fz_mul(beta, q[i].y));
-      np.z = fz_add(a[i].z, fz_mul(beta, q[i].z)); np.w = fz_add(a[i].w, fz_mul(beta, q[i].w));
+      np.x = add_rn(a[i].x, mul_rn(beta, q[i].x)); np.y = add_rn(a[i].y, mul_rn(beta, q[i].y));
+      np.z = add_rn(a[i].z, mul_rn(beta, q[i].z)); np.w = add_rn(a[i].w, mul_rn(beta, q[i].w));
       st4(p + ck.flat_off, e, ck.len, np);
       acc += (double)np.x * np.x + (double)np.y * np.y + (double)np.z * np.z + (double)np.w * np.w;
     }
@@ -126,6 +126,6 @@ __device__ __forceinline__ void beta_body(const BetaArgs& a, const int bx) {
     }
   }
   __syncthreads();
-  if (eoff >= 0) a.p[eoff] = fz_add(rv, fz_mul(s_beta, pv));
+  if (eoff >= 0) a.p[eoff] = add_rn(rv, mul_rn(s_beta, pv));
 }
 __global__ __launch_bounds__(kThreads) void k_cg_beta(BetaArgs a) { beta_body(a, blockIdx.x); }

@@ -242,12 +242,12 @@ __device__ __forceinline__ void wskp_tile(const WskpProb& q, const int m0, const
       float sum = 0.f;
 #pragma unroll
       for (int w = 0; w < kWskpWaves; ++w) sum += sPf[w * (TR * TCP) + row * TCP + col];
-      const float z = fz_add(sum, fz_mul(beta_lin, e_zold[u]));
+      const float z = add_rn(sum, mul_rn(beta_lin, e_zold[u]));
       if (q.znew) q.znew[idx] = m < q.B ? z : 0.f;
-      v = fz_add(v, fz_mul(beta_lin, e_add2[u]));   // the rounding of the recurrence G(p') = G(r') + beta G(p)
+      v = add_rn(v, mul_rn(beta_lin, e_add2[u]));   // the rounding of the recurrence G(p') = G(r') + beta G(p)
       v += z;
       if (!q.raw) {
-        if (q.bias) v += fz_add(e_bias[u], fz_mul(beta_lin, e_bias2[u]));
+        if (q.bias) v += add_rn(e_bias[u], mul_rn(beta_lin, e_bias2[u]));
         if (q.mask) v *= e_mask[u];
       }
     } else {
