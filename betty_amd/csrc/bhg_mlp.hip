@@ -26,6 +26,7 @@
 
 
 #include "bhg_common.hpp"
+#include "bhg_mlp_headj.hpp"   // the head launch in its head_j form: device code in bhg_mlp_headj.hip
 
 #ifdef BHG_STAMPS
 namespace bhg { __device__ unsigned long long* d_stamps = nullptr; }
@@ -593,8 +594,17 @@ struct FusedWs {
   float* dpk[BHG_MLP_MAX_LAYERS];   // delta_l  [d_{l+1} / 16][Bp][16],  l = 1 .. L-2
   float* Rhp[BHG_MLP_MAX_LAYERS];   // Rh_l     [d_{l+1} / 16][Bp][16],  l = 0 .. L-3   (written by the producer of Rh_l)
   float* Rdp[BHG_MLP_MAX_LAYERS];   // Rd_l     [d_{l+1} / 16][Bp][16],  l = 1 .. L-2   (written by the producer of Rd_l)
+  // head_j (bhg_mlp_headj.hpp): J = W_3 diag(mask_2) W_2 per sample, [round32(Bp C)][d_2], built once per solve from the packed
+  // operand hj_Ap [d_3 / 16][round32(B C)][16]; nT2j: T2h partials of the head launch's tiles, appended to partT2 (0: the form cannot apply)
+  float* hj_J; float* hj_Ap; int nT2j;
   size_t bytes;
 };
+// The shapes the head_j form takes — where lin_head applies (cg_ctx_init adds the solver's own conditions): L = 4, <= 12 classes, last
+// hidden width <= 512, a padded batch of 128 rows.
+inline bool headj_shape_ok(const bhg_mlp* m, const HoistPlan& hp) {
+  return hp.ok && hp.lin_ok && m->L == 4 && m->dims[m->L] <= 12 && m->dims[m->L - 1] <= 512 && m->Bp == 128;
+}
+inline int headj_rows(int rows_valid, int C) { return (rows_valid * C + 31) & ~31; }
 void carve_fused_ws(const bhg_mlp* m, void* base, FusedWs* w) {
   memset(w, 0, sizeof(*w));
   const bool head = use_head(m);
@@ -611,11 +621,13 @@ void carve_fused_ws(const bhg_mlp* m, void* base, FusedWs* w) {
   int nt2 = 0;
   for (int l = 1; l + 1 < m->L; ++l) { w->t2_off[l] = nt2; nt2 += reduce_blocks(m->Bp * m->dims[l], m->dims[l]); }
   w->nT2 = nt2;
-  w->partT2 = static_cast<double*>(take(sizeof(double) * (nt2 > 0 ? nt2 : 1)));
-  w->rz = static_cast<float*>(take(sizeof(float) * (size_t)m->Bp * m->dims[m->L]));
-  w->rzx = static_cast<double*>(take(sizeof(double) * (size_t)m->Bp * m->dims[m->L]));
   HoistPlan hp;
   hoist_plan(m, &hp);
+  const bool hj = headj_shape_ok(m, hp);
+  w->nT2j = hj ? headj_tiles(m->Bp, m->dims[m->L - 1], 1) : 0;   // (the most any tile shape needs)
+  w->partT2 = static_cast<double*>(take(sizeof(double) * (nt2 + w->nT2j > 0 ? nt2 + w->nT2j : 1)));
+  w->rz = static_cast<float*>(take(sizeof(float) * (size_t)m->Bp * m->dims[m->L]));
+  w->rzx = static_cast<double*>(take(sizeof(double) * (size_t)m->Bp * m->dims[m->L]));
   w->hoist = static_cast<float*>(take(sizeof(float) * (hp.ok ? hp.floats : 1)));
   w->part_dot = static_cast<double*>(take(sizeof(double) * 2 * (hp.ok ? hp.dot_blocks : 1)));
   w->part_raw = static_cast<double*>(take(sizeof(double) * (hp.ok ? hp.raw_blocks : 1)));
@@ -637,6 +649,11 @@ void carve_fused_ws(const bhg_mlp* m, void* base, FusedWs* w) {
         w->Rdp[l] = static_cast<float*>(take(sizeof(float) * Bp * m->dims[l + 1]));
       }
     }
+  }
+  if (hj) {
+    const size_t rj = (size_t)headj_rows(m->Bp, m->dims[m->L]);
+    w->hj_J = static_cast<float*>(take(sizeof(float) * rj * m->dims[m->L - 2]));
+    w->hj_Ap = static_cast<float*>(take(sizeof(float) * rj * m->dims[m->L - 1]));
   }
   w->bytes = off;
 }
@@ -676,6 +693,22 @@ int pack_operands(const bhg_mlp* m, const FusedWs& w, hipStream_t st, bool weigh
   BHG_REQUIRE(ok, "too many layers for one packing launch");
   g.blk0[g.n] = blk;
   hipLaunchKernelGGL(k_pack, dim3(blk), dim3(256), 0, st, g);
+  BHG_HIP_CHECK(hipGetLastError());
+  return BHG_OK;
+}
+
+// head_j: J = A W_2 once per solve — A[b C + c][k] = W_3[c][k] mask_2[b][k] packed by k_headj_pack, then the backward product through
+// W_2 (the chain's own k_wskpc on Wb[L-2]) with round32(B C) rows instead of the padded batch; row-major output, rows >= B C zero.
+int build_head_j(const bhg_mlp* m, const FusedWs& w, hipStream_t st) {
+  const int L = m->L, C = m->dims[L], K = m->dims[L - 1], N = m->dims[L - 2], RA = headj_rows(m->B, C);
+  BHG_REQUIRE(w.nT2j > 0 && w.hj_J && w.hj_Ap && w.Wb[L - 2], "the head_j form was planned for a net it cannot take");
+  if (int rc = launch_headj_pack(m->W[L - 1], m->mask[L - 2], w.hj_Ap, m->B, C, K, RA, st)) return rc;
+  WskpBuilder wb;
+  WskpProb q{};
+  q.Ap = w.hj_Ap; q.Bq = w.Wb[L - 2]; q.RA = RA; q.RB = N; q.K = K; q.B = m->B * C; q.nsplit = 1;
+  q.out = w.hj_J;
+  wb.add(q);
+  wb.launch(st);
   BHG_HIP_CHECK(hipGetLastError());
   return BHG_OK;
 }
@@ -931,6 +964,12 @@ int hoist_forward(const bhg_mlp* m, const void* const* dir, const ChainMode& cm,
         if (sp > cap) sp = cap;
         if (sp > K / 64) sp = K / 64;
         if (sp < 1) sp = 1;
+        if (pl.head_j && cs->lin_update_pending) {   // head_j: no pre-head launch — its tiles ride in the head launch (hoist_head)
+          cs->head_fuse = {nullptr, 0, Bp * N, c, m->mask[l], m->Rh[l], hbase + hp->gr_off[hp->gf[l]]};
+          cs->fuse_head = true;
+          cs->head_j = true;
+          continue;
+        }
         q.nsplit = sp; q.raw = 1; q.out = m->partial;
         // (lin_head, past the first iteration: the head forms Gf(p') = Gf(r') + beta Gf(p) itself — k_headu, see there)
         cs->head_fuse = {m->partial, sp, Bp * N, c, m->mask[l], m->Rh[l], (pl.lin_head && !cm.first) ? hbase + hp->gr_off[hp->gf[l]] : Gf};
@@ -991,7 +1030,29 @@ int hoist_forward(const bhg_mlp* m, const void* const* dir, const ChainMode& cm,
 // The head launch of the hoisted form: Rd_{L-1} and Rd_{L-2}, the pre-head product's slabs combined on the way (ChainState.head_fuse)
 int hoist_head(const bhg_mlp* m, const void* const* dir, const ChainMode& cm, const ChainPlan& pl, hipStream_t st, ChainState* cs) {
   const int L = m->L, Bp = m->Bp, B = m->B;
-  if (cs->lin_update_pending) {   // the head launch with the update blocks behind the head's rows (k_headu)
+  if (cs->lin_update_pending && cs->head_j) {   // head_j: head rows through J, the pre-head tiles, the update blocks (k_headj)
+    const int l = L - 1, K = m->dims[l], N = m->dims[l + 1];
+    BHG_REQUIRE(cs->fuse_head && pl.cg && pl.packed && cm.ws->nT2j > 0 && !cm.rzx_acc, "k_headj was planned for a head it cannot run");
+    HeadjLaunch a{};
+    a.h = m->h[l]; a.W = m->W[l]; a.V = static_cast<const float*>(dir[2 * l]); a.cb = static_cast<const float*>(dir[2 * l + 1]);
+    a.prob = m->prob; a.sd = m->sd; a.rd = m->Rd[l];
+    a.K = K; a.C = N; a.B = B; a.rows = Bp;
+    a.delta_top = (const float*)m->delta[l]; a.mask_prev = (const float*)m->mask[l - 1]; a.rd_prev = m->Rd[l - 1]; a.rd_prev_p = cm.ws->Rdp[l - 1];
+    a.partT1 = cm.ws->partT1; a.rz_out = cm.ws->rz;
+    a.bias2 = cs->head_fuse.bias; a.mask2 = cs->head_fuse.mask; a.addend = cs->head_fuse.addend;
+    a.addend2 = pl.gp2(cm.kpar ^ 1); a.gran = cm.ws->gran;
+    a.J = cm.ws->hj_J; a.Rh1 = m->Rh[l - 2]; a.K1 = m->dims[l - 1];
+    a.Rh1p = cm.ws->Rhp[l - 2]; a.W2p = cm.ws->Wf[l - 1]; a.rh_out = m->Rh[l - 1];
+    // T2h partials, one per tile: where the head rows' went (partT2h, B slots summed) when they fit — the step length's one-round-trip
+    // form takes a bounded number of T2 partials (alpha_begin) — else behind the layers' own in partT2
+    a.tile_shape = dbg(DBG_head_j_tile, kHeadjTile);
+    const int nt = headj_tiles(Bp, K, a.tile_shape);
+    if (nt <= B) { a.partT2 = cm.ws->partT2h; a.t2n = B; cs->head_j_nt = 0; }
+    else { a.partT2 = cm.ws->partT2 + cm.ws->nT2; a.t2n = nt; cs->head_j_nt = nt; }
+    a.ps = &cs->lin_ps; a.ps_bytes = sizeof(cs->lin_ps); a.nu = cs->lin_ps.h.update_blocks;
+    if (int rc = launch_headj(a, st)) return rc;
+    cs->lin_update_pending = false;
+  } else if (cs->lin_update_pending) {   // the head launch with the update blocks behind the head's rows (k_headu)
     const int l = L - 1, K = m->dims[l], N = m->dims[l + 1];
     BHG_REQUIRE(cs->fuse_head && pl.cg && pl.packed && N <= 12 && K <= 512, "k_headu was planned for a head it cannot run");
     HeaduArgs ha{};
@@ -1576,6 +1637,10 @@ int run_chain(const bhg_mlp* m, const void* const* dir, const ChainMode& cm, hip
   if (pl.do_chain && !pl.hp) chain_forward(m, dir, cm, pl, st, &cs);
   ChainOutputs od;
   describe_outputs(m, dir, cm, pl, &od);
+  if (cs.head_j && cs.head_j_nt > 0) {   // T2h came from the head launch's tiles as fp64 partials behind the layers' own (a plain fp64 sum either way)
+    od.aa.partT2h = nullptr;
+    od.aa.nT2 = cm.ws->nT2 + cs.head_j_nt;
+  }
   if (pl.do_chain && !pl.hp)
     if (int rc = chain_backward(m, dir, cm, pl, st)) return rc;
 
@@ -1696,6 +1761,16 @@ void* bhg_mlp_timeout_flag_dev(const bhg_mlp* m, void* fws) {
   return w.gran + 1;
 }
 
+const float* bhg_mlp_head_j_dev(const bhg_mlp* m, void* fws, int* rows, int* cols) {
+  if (!m || m->L < 1 || m->L > BHG_MLP_MAX_LAYERS || m->Bp <= 0 || !fws) return nullptr;
+  FusedWs w;
+  carve_fused_ws(m, fws, &w);
+  if (w.nT2j == 0) return nullptr;
+  if (rows) *rows = headj_rows(m->B, m->dims[m->L]);
+  if (cols) *cols = m->dims[m->L - 2];
+  return w.hj_J;
+}
+
 size_t bhg_mlp_fused_ws_bytes(const bhg_mlp* m) {
   if (!m || m->L < 1 || m->L > BHG_MLP_MAX_LAYERS || m->Bp <= 0) return 0;
   FusedWs w;
@@ -1718,7 +1793,7 @@ struct CgCtx {
   const bhg_mlp* m; float* x; float* r; float* p; const int64_t* starts; const bhg_chunk* chunks_dev; int n_chunks, K;
   float cg_alpha, shift;
   FusedWs w; double* scal; const double* partR0; int n_init, pgrid, bgrid;
-  bool lazy, hoist, lin, lin_head; int proj_level;
+  bool lazy, hoist, lin, lin_head, head_j; int proj_level;
   const void* const* rhs;
   BetaArgs ba; HoistPlan hplan;
   const void* dir[2 * BHG_MLP_MAX_LAYERS];
@@ -1767,6 +1842,9 @@ static void cg_ctx_init(CgCtx* c, const bhg_mlp* m, float* x, float* r, float* p
   // prefetching instance must apply (<= 12 classes, last hidden width <= 512), and like lin it holds for the whole solve (slot parity)
   c->lin_head = c->lin && m->L == 4 && dbg(DBG_lin_update_next, 1) != 0 && dbg(DBG_lin_update_in_head, 1) != 0 && dbg(DBG_lin_nub, 0) == 0 &&
                 m->dims[m->L] <= 12 && m->dims[m->L - 1] <= 512 && dbg(DBG_head_no_prefetch, 0) == 0;
+  // ... whose rows can take the pre-head product through J = W_3 diag(mask_2) W_2, built once per solve: the pre-head launch leaves the
+  // dependency chain, its tiles ride in the head launch (k_headj, bhg_mlp_headj.hip).  Debug key head_j = 0: today's six launches.
+  c->head_j = c->lin_head && c->w.nT2j > 0 && dbg(DBG_head_j, 1) != 0;
 }
 // gphase 0: the whole iteration (one rank) | 1: up to this rank's p.H_data p | 2: from the step length on (see ChainMode)
 static int cg_iteration(CgCtx* c, int k, int gphase, double* php, double inv_world, hipStream_t st) {
@@ -1816,6 +1894,7 @@ static int cg_iteration(CgCtx* c, int k, int gphase, double* php, double inv_wor
   if (c->lin) c->dir[3] = k == 0 ? static_cast<const void*>(c->p + c->starts[3]) : static_cast<const void*>(w.pb1[k & 1]);
   cm.lin = c->lin ? 1 : 0;
   cm.lin_head = c->lin_head ? 1 : 0;
+  cm.head_j = c->head_j ? 1 : 0;
   cm.rhs = c->rhs;
   if (int rc = run_chain(m, c->dir, cm, st)) return rc;
   if (timed) BHG_HIP_CHECK(hipEventRecord(tb, st));
@@ -1868,6 +1947,8 @@ int bhg_mlp_cg_solve_rhs(const bhg_mlp* m, float* x, float* r, float* p, const i
   c.rhs = rhs;
   if (c.hoist && packed_chain_on(c.w) && !m->prepacked)   // (prepacked: bhg_mlp_forward_packed / _backward_packed left the packed operands)
     if (int rc = pack_operands(m, c.w, st)) return rc;
+  if (c.head_j && K >= 2)   // (the projected iterations 1 .. K-1 read J)
+    if (int rc = build_head_j(m, c.w, st)) return rc;
   for (int k = 0; k < K; ++k)
     if (int rc = cg_iteration(&c, k, 0, nullptr, 1.0, st)) return rc;
   BHG_HIP_CHECK(hipGetLastError());
@@ -2376,7 +2457,7 @@ int bhg_mlp_plan_describe(const bhg_mlp* m, int algo, int keep_solution, char* b
   HoistPlan hp;
   hoist_plan(m, &hp);
   const char* form = "unfused";
-  int hoist = 0, proj_level = 0, lin = 0, lin_head = 0, upd_first = 0;
+  int hoist = 0, proj_level = 0, lin = 0, lin_head = 0, upd_first = 0, head_j = 0;
   const char* closing = "k_outer_all";
   if (fused) {
     // the flat layout of [W_1, b_1, ...] (what the callers pass as `starts`), fake state pointers: nothing is dereferenced
@@ -2389,7 +2470,7 @@ int bhg_mlp_plan_describe(const bhg_mlp* m, int algo, int keep_solution, char* b
     if (algo == 0) {
       static CgCtx c;   // (large: off the stack)
       cg_ctx_init(&c, m, keep_solution ? fake : nullptr, fake, fake, starts, nullptr, (int)nch, 2, 1.f, 0.f, fake, fake, false);
-      hoist = c.hoist ? 1 : 0; proj_level = c.proj_level; lin = c.lin ? 1 : 0; lin_head = c.lin_head ? 1 : 0;
+      hoist = c.hoist ? 1 : 0; proj_level = c.proj_level; lin = c.lin ? 1 : 0; lin_head = c.lin_head ? 1 : 0; head_j = c.head_j ? 1 : 0;
       upd_first = (c.lin && L > 4) ? 1 : 0;
       form = !c.lazy ? "classic-eager" : (!c.hoist ? "classic" : (c.proj_level == 0 ? "hoisted" : (c.proj_level == 1 ? "projected-keep-state" :
              (c.lin ? (c.lin_head ? "six-launch (k_wskpl .. k_headu .. k_graw)" : "six-launch-class (k_wskpl first, recurrences beside the chain)") :
@@ -2410,14 +2491,14 @@ int bhg_mlp_plan_describe(const bhg_mlp* m, int algo, int keep_solution, char* b
   const int n = snprintf(buf, buf_bytes,
                          "algo=%s keep_solution=%d fused=%d form=\"%s\" hoist=%d proj_level=%d lin=%d lin_head=%d upd_first=%d closing=%s "
                          "plan_ok=%d proj_ok=%d lin_ok=%d hoist_products=%d hoist_wgs=%d gram_floats=%zu fused_ws_bytes=%zu narrow_head=%d packed_prepare=%d "
-                         "global_form=%s fx_slab_bytes=%zu fx_ws_bytes_world8=%zu",
+                         "global_form=%s fx_slab_bytes=%zu fx_ws_bytes_world8=%zu head_j=%d",
                          algo == 0 ? "cg" : "neumann", keep_solution ? 1 : 0, fused ? 1 : 0, form, hoist, proj_level, lin, lin_head, upd_first, closing,
                          hp.ok ? 1 : 0, hp.proj_ok ? 1 : 0, hp.lin_ok ? 1 : 0, hp.n, hp.ok ? hp.blk0[hp.n] : 0, gram,
                          fused ? bhg_mlp_fused_ws_bytes(m) : (size_t)0, narrow_head(m) ? 1 : 0, bhg_mlp_supports_packed_prepare(m),
                          // Config(type="cg_global"): the form of the global-batch solve (round 6: factor exchange whenever the projected plan is
                          // taken and the caller does not ask for x; else the one-pass form; without a fused solver the sharded form)
                          (algo == 0 && !keep_solution && bhg_mlp_fx_supported(m, 1)) ? "factor-exchange" : (fused ? "one-pass" : "sharded"),
-                         sizeof(float) * bhg_mlp_fx_slab_floats(m), bhg_mlp_fx_ws_bytes(m, 8));
+                         sizeof(float) * bhg_mlp_fx_slab_floats(m), bhg_mlp_fx_ws_bytes(m, 8), head_j);
   BHG_REQUIRE(n > 0 && (size_t)n < buf_bytes, "output buffer too small");
   return BHG_OK;
 }

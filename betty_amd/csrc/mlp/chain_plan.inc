@@ -36,6 +36,7 @@ struct ChainMode {
   int nk;                       // projected Neumann: iteration index (the row-major Rh_0 lives in two slots by its parity, see vnew)
   const void* const* rhs;       // fully projected CG, first iteration: the right-hand side's own tensors (bhg_mlp_cg_solve_rhs) or NULL
   int lin_head;                 // lin on a four-layer net: the update blocks ride in the HEAD launch (k_headu), the pre-head launch is the plain product
+  int head_j;                   // lin_head with the head rows reading J (k_headj): no pre-head launch, its tiles ride in the head launch
 };
 
 // What one pass of the chain decides before its first launch (plan_chain).  The stages of run_chain read it; none of them changes it.
@@ -78,6 +79,7 @@ struct ChainPlan {
   // the whole solve: every iteration's first product, every k_graw (Rh_0(r') for the next one) and cg_iteration (the second bias's
   // direction in slots) follow it.  lin_head: see ChainMode
   bool lin, lin_head;
+  bool head_j;                  // see ChainMode; applies to the iterations whose head launch carries the update blocks (all but the first)
 
   float* rh0_slot(int k) const { return (k & 1) ? hoist + hp->rh0alt_off : rh0; }                   // Rh_0(v_k), row-major (vnew)
   float* gp1(int par) const { return hoist + (par ? hp->gp1alt_off : hp->g_off[hp->gf[1]]); }       // Gf_1(p): two slots (lin)
@@ -96,6 +98,8 @@ struct ChainState {
   int lin_nu = 0, lin_U = 4;
   bool lin_update_pending = false;    // the update blocks ride in the launch after the first product (k_wskpu) or in the head launch (k_headu)
   bool sd_in_chain = false;           // first iteration: S_l, D_l rode in the first chain launch as well
+  bool head_j = false;                // this pass skipped the pre-head launch: the head launch is k_headj, T2h arrives as tile partials
+  int head_j_nt = 0;                  // ... behind the layers' own in partT2 (0: in partT2h's slots)
 };
 
 int plan_chain(const bhg_mlp* m, const ChainMode& cm, ChainPlan* p) {
@@ -140,6 +144,7 @@ int plan_chain(const bhg_mlp* m, const ChainMode& cm, ChainPlan* p) {
   BHG_REQUIRE(!p->lin || (p->rnew && hp && hp->lin_ok && cm.beta && cm.beta->nt <= 16 && proj_step_merged() && L >= 4),
               "the linear first product was planned for a solve that cannot run it");
   p->lin_head = p->lin && cm.lin_head != 0;
+  p->head_j = p->lin_head && cm.head_j != 0;
   return BHG_OK;
 }
 

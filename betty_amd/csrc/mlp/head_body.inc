@@ -2,6 +2,8 @@
 // arguments must be named in the __global__ function itself).  Expects the parameter names of k_head_forward in scope, and
 //   BHG_HEAD_B      this workgroup's sample row            BHG_HEAD_ROWS   rows of the launch (the padded batch)
 //   BHG_HEAD_LAZY   1: `lazy_addend2` / `lazy_beta` in scope — the hoisted addend is Gf(r') + beta Gf(p) formed here (k_headu)
+//   BHG_HEAD_J      defined (k_headj, bhg_mlp_headj.hip): the pre-head product reaches the classes through J_b — `hj_J`, `hj_Rh1`, `hj_K1`
+//                   in scope; no slabs are combined, Rh_{L-2} is neither formed nor stored here (the launch's tiles do that)
   // rd_prev_p != NULL: a packed copy of rd_prev ([K / 16][rows][16], wskp.inc) for the first product of the backward chain
 #if !BHG_HEAD_LAZY
   kernarg_warm<256>();   // (28 arguments: fetched in one round trip instead of group by group)
@@ -29,8 +31,10 @@
         *reinterpret_cast<float4*>(rd_prev + (int64_t)b * K + k) = make_float4(0.f, 0.f, 0.f, 0.f);
         if (rd_prev_p) *reinterpret_cast<float4*>(rd_prev_p + ((int64_t)(k >> 4) * BHG_HEAD_ROWS + b) * 16 + (k & 15)) = make_float4(0.f, 0.f, 0.f, 0.f);
       }
+#ifndef BHG_HEAD_J
     if (FUSED)
       for (int k = 4 * t; k < K; k += 1024) *reinterpret_cast<float4*>(fz.rh_out + (int64_t)b * K + k) = make_float4(0.f, 0.f, 0.f, 0.f);
+#endif
     return;
   }
   const float* hb = h + (int64_t)b * K;
@@ -65,12 +69,33 @@
     pf_sd = sd[b];
     pf_dt = delta_top[(int64_t)b * C + tc];
   }
+#ifdef BHG_HEAD_J
+  // J_b[c] . Rh_1[b] over K1 = d_{L-2}: lanes stride the rows like the dot products below, HJT trips of 256 k in flight; the first
+  // batch is requested here, with the operands above
+  constexpr int HJT = 3;
+  const float* hj_rrow = hj_Rh1 + (int64_t)b * hj_K1;
+  const float* hj_jrow[JMAX];
+#pragma unroll
+  for (int j = 0; j < JMAX; ++j) hj_jrow[j] = hj_J + ((int64_t)b * C + min(wave + 4 * j, C - 1)) * hj_K1;
+  float4 hj_r[HJT], hj_j[HJT][JMAX];
+#pragma unroll
+  for (int tr = 0; tr < HJT; ++tr) {
+    const int k = 4 * lane + 256 * tr;
+    const int kc = k < hj_K1 ? k : 0;
+    hj_r[tr] = ld16(hj_rrow + kc);
+#pragma unroll
+    for (int j = 0; j < JMAX; ++j) hj_j[tr][j] = ld16(hj_jrow[j] + kc);
+  }
+#endif
   if (FUSED) {
     for (int k = 4 * t; k < K; k += 1024) {
+#ifndef BHG_HEAD_J
       const float* p0 = fz.part + (int64_t)b * K + k;
+#endif
       const float4 bv = ld16(fz.bias + k);
       const float4 mv = ld16(fz.mask + (int64_t)b * K + k);
       float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+#ifndef BHG_HEAD_J
       constexpr int NB = PF ? 16 : 8;                 // slabs in flight together; the summation order is s = 0, 1, ... either way
       for (int s0 = 0; s0 < fz.splits; s0 += NB) {    // (as k_reduce_mask)
         float4 tt[NB];
@@ -80,6 +105,7 @@
         for (int u = 0; u < NB; ++u)
           if (s0 + u < fz.splits) { v.x += tt[u].x; v.y += tt[u].y; v.z += tt[u].z; v.w += tt[u].w; }
       }
+#endif
       if (fz.addend) {
         float4 ad = ld16(fz.addend + (int64_t)b * K + k);
 #if BHG_HEAD_LAZY
@@ -95,10 +121,40 @@
       }
       v.x = (v.x + bv.x) * mv.x; v.y = (v.y + bv.y) * mv.y; v.z = (v.z + bv.z) * mv.z; v.w = (v.w + bv.w) * mv.w;
       *reinterpret_cast<float4*>(srow + k) = v;
+#ifndef BHG_HEAD_J
       *reinterpret_cast<float4*>(fz.rh_out + (int64_t)b * K + k) = v;
+#endif
     }
     __syncthreads();
   }
+#ifdef BHG_HEAD_J
+  // (srow holds mask (addend + c) — the part of Rh_{L-2} that does not come through W_{L-2}; the rest of it reaches rz through J)
+  for (int k0 = 0; k0 < hj_K1; k0 += 256 * HJT) {
+    if (k0 > 0) {
+#pragma unroll
+      for (int tr = 0; tr < HJT; ++tr) {
+        const int k = k0 + 4 * lane + 256 * tr;
+        const int kc = k < hj_K1 ? k : 0;
+        hj_r[tr] = ld16(hj_rrow + kc);
+#pragma unroll
+        for (int j = 0; j < JMAX; ++j) hj_j[tr][j] = ld16(hj_jrow[j] + kc);
+      }
+    }
+#pragma unroll
+    for (int tr = 0; tr < HJT; ++tr) {
+      if (k0 + 4 * lane + 256 * tr < hj_K1) {
+        const float4 rv = hj_r[tr];
+#pragma unroll
+        for (int j = 0; j < JMAX; ++j) {
+          float a = acc[j];
+          const float4 jv = hj_j[tr][j];
+          a = fmaf(rv.x, jv.x, a); a = fmaf(rv.y, jv.y, a); a = fmaf(rv.z, jv.z, a); a = fmaf(rv.w, jv.w, a);
+          acc[j] = a;
+        }
+      }
+    }
+  }
+#endif
   const float* rhb = HAS_RH ? (FUSED ? srow : Rh + (int64_t)b * K) : nullptr;
   // PF: operands of the fused R-backward (k = 4 t, all C <= 12 classes), requested while the dot products run
   float4 pf_mk, pf_W[12], pf_V[12];

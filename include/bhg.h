@@ -470,6 +470,13 @@ int bhg_mlp_backward_packed(const bhg_mlp* m, const int64_t* labels, void* fws, 
  * barrier (bhg_cg_timeout_flag_dev).  The caller reads and clears it (HipBackend.check_health).  NULL on a bad descriptor.          */
 void* bhg_mlp_timeout_flag_dev(const bhg_mlp* m, void* fws);
 
+/* Fully projected CG on a four-layer net with a narrow head (plan key head_j = 1, bhg_mlp_plan_describe): the solve builds, once,
+ *   J[b C + c][n] = sum_k W_3[c][k] mask_2[b][k] W_2[k][n]          (C = dims[4] classes, n < dims[2]; csrc/bhg_mlp_headj.hpp)
+ * inside `fws`, and the head launch of every later iteration reads the pre-head product through it.  Device address of J after a solve
+ * of >= 2 iterations: row-major, *rows = B C rounded up to 32 (rows >= B C are zero), *cols = dims[2].  NULL where the form does not
+ * apply.  For tests; reads nothing on the device.                                                                                    */
+const float* bhg_mlp_head_j_dev(const bhg_mlp* m, void* fws, int* rows, int* cols);
+
 /* ---- closed-form meta-weight-net (round 5; csrc/bhg_mwn.hip) --------------------------------------------------------------------
  * The UPPER problem of data reweighting (examples/learning_to_reweight/model.py:98-111 `MLP(hidden_size, num_layers = 1)`, called at
  * main.py:123-125):  s_i = sigmoid(w2 . relu(w1 * ce_i + b1) + b2),  ce: [B] detached per-sample losses, w1, b1, w2: [H], b2: [1].
@@ -487,8 +494,8 @@ int bhg_mwn_backward(const float* ce, const float* coeff, int B, const float* w1
 
 /* Host only (no launch, no device access): the form bhg_mlp_cg_solve (algo 0) / bhg_mlp_neumann_solve (algo 1) will take for this
  * descriptor, with (keep_solution != 0) or without a materialised solution / accumulator vector — the decision of hoist_plan and of the
- * solvers' set-up code, printed as `key=value` pairs into `buf` (form, hoist, proj_level, lin, lin_head, closing launch, workspace
- * sizes).  Only L, B, Bp and dims of the descriptor are read.  For tests of the shape -> form map and for diagnostics; the reference has
+ * solvers' set-up code, printed as `key=value` pairs into `buf` (form, hoist, proj_level, lin, lin_head, head_j, closing launch,
+ * workspace sizes).  Only L, B, Bp and dims of the descriptor are read.  For tests of the shape -> form map and for diagnostics; the reference has
  * no counterpart (its cg / neumann have one form: betty/hypergradient/cg.py:8-70, neumann.py:8-66).                                  */
 int bhg_mlp_plan_describe(const bhg_mlp* m, int algo, int keep_solution, char* buf, size_t buf_bytes);
 

@@ -79,6 +79,10 @@ def demangle(n):
 # (.sgpr_spill_count > 0, .vgpr_spill_count == 0) and their code contains no scratch / stack instruction.  Everything else with a
 # non-zero .private_segment_fixed_size fails the build (an allow-list per kernel, not a global relaxation).
 FRAME_ALLOWED = ("k_wskpl<", "k_wskpu<", "k_headu<")
+# k_headj (csrc/bhg_mlp_headj.hip) carries k_headu's update blocks (pstep_body) and declares the same 68-byte frame; in its unit the
+# compiler finds registers for those SGPRs after the frame was laid out (.sgpr_spill_count == 0), so the frame is dead.  Allowed on the
+# same evidence: no scratch / stack instruction in the kernel's code.
+FRAME_ALLOWED_UNSPILLED = ("k_headj<",)
 
 
 def check(build_dir):
@@ -93,7 +97,8 @@ def check(build_dir):
                 if d.get(".vgpr_spill_count", 0):
                     bad.append((name, d))
                 elif d.get(".private_segment_fixed_size", 0):
-                    explained = d.get(".sgpr_spill_count", 0) > 0 and short(name).startswith(FRAME_ALLOWED)
+                    explained = (d.get(".sgpr_spill_count", 0) > 0 and short(name).startswith(FRAME_ALLOWED)) or \
+                                short(name).startswith(FRAME_ALLOWED_UNSPILLED)
                     n = scratch_ops(o, tmp, name) if explained else None
                     if not explained or n != 0:   # (n == -1: the kernel's symbol was not found in the disassembly — refuse, do not guess)
                         d["scratch_instructions"] = n
