@@ -22,7 +22,6 @@
 // helpers, the plan of the hoisted / projected forms (hoist_plan), the workspace carve-up, run_chain (one HVP chain with its
 // outputs stored or consumed), and the C entry points bhg_mlp_* of include/bhg.h.
 #include <stdlib.h>
-#include <vector>
 
 
 #include "bhg_common.hpp"
@@ -599,7 +598,7 @@ struct FusedWs {
   float* hj_J; float* hj_Ap; int nT2j;
   size_t bytes;
 };
-// The shapes the head_j form takes — where lin_head applies (cg_ctx_init adds the solver's own conditions): L = 4, <= 12 classes, last
+// The shapes the head_j form takes — where lin_head applies (plan_solve adds the solver's own conditions): L = 4, <= 12 classes, last
 // hidden width <= 512, a padded batch of 128 rows.
 inline bool headj_shape_ok(const bhg_mlp* m, const HoistPlan& hp) {
   return hp.ok && hp.lin_ok && m->L == 4 && m->dims[m->L] <= 12 && m->dims[m->L - 1] <= 512 && m->Bp == 128;
@@ -666,7 +665,6 @@ bool rnew_keys_on() { return dbg(DBG_proj_small_alone, 0) == 0 && dbg(DBG_alpha_
 
 // Packed copies of the constants of a solve (wskp.inc): the chain's weights in both orientations, h_l and delta_l for the Gram
 // products.  One launch, once per solve: 3 x 15 M floats moved at cfg 2, ~1 % of a CG-20 solve.
-bool packed_chain_on(const FusedWs& w) { return w.Wf[1] != nullptr && dbg(DBG_packed_chain, 1) != 0; }
 // weights_only: the chain's weights and the input batch h_0 — what bhg_mlp_forward_packed packs before the net's own forward pass,
 // whose epilogues leave h_l and delta_l packed themselves
 int pack_operands(const bhg_mlp* m, const FusedWs& w, hipStream_t st, bool weights_only = false) {
@@ -713,6 +711,7 @@ int build_head_j(const bhg_mlp* m, const FusedWs& w, hipStream_t st) {
   return BHG_OK;
 }
 
+#include "mlp/solve_plan.inc"   // host only: the form of a whole solve, decided once (SolvePlan, plan_solve)
 #include "mlp/chain_plan.inc"   // host only: what one pass of run_chain is told (ChainMode), decides before its first launch (ChainPlan, plan_chain) and
                                 // hands from stage to stage (ChainState)
 
@@ -744,7 +743,7 @@ int hoist_products(const bhg_mlp* m, const void* const* dir, const ChainMode& cm
   }
   ha.blk0[hp->n] = hp->blk0[hp->n];
   ha.n = hp->n; ha.Bp = Bp; ha.gemm_blocks = hp->blk0[hp->n];
-  const bool proj = cm.proj != 0;
+  const bool proj = pl.proj != 0;
   int rblk = 0;
   for (int i = 0; i < hp->n; ++i) { ra.blk0[i] = rblk; rblk += (Bp * (hp->N[i] / 4) + 255) / 256; }
   ra.blk0[hp->n] = rblk;
@@ -777,7 +776,7 @@ int hoist_products(const bhg_mlp* m, const void* const* dir, const ChainMode& cm
     }
     pa.blk0[hp->n] = rblk;
     pa.n = hp->n; pa.Bp = Bp; pa.B = B; pa.kpar_prev = cm.kpar ^ 1; pa.shift = cm.shift; pa.scal = pl.cg ? cm.scal : nullptr; pa.alpha = cm.alpha;
-    if (pl.cg && cm.proj >= 2 && proj_step_merged()) {   // + the scalars and the small slices' direction update of the LAST iteration
+    if (pl.cg && pl.proj >= 2 && proj_step_merged()) {   // + the scalars and the small slices' direction update of the LAST iteration
       ProjStepArgs g{};
       g.pa = pa;
       ProjScalArgs& sa = g.sa;
@@ -1260,7 +1259,7 @@ void describe_outputs(const bhg_mlp* m, const void* const* dir, const ChainMode&
   ba.blk0[L] = bias_blk;
   od->bias_blk = bias_blk;
   // fully projected CG (k_proj_step): the first bias's slice of the direction lives in the slot dir[1] names
-  if (pl.cg && cm.proj >= 2 && pl.hp && proj_step_merged()) ba.d0 = static_cast<const float*>(dir[1]);
+  if (pl.cg && pl.proj >= 2 && pl.hp && proj_step_merged()) ba.d0 = static_cast<const float*>(dir[1]);
   if (pl.lin) ba.d1 = static_cast<const float*>(dir[3]);
   FuseArgs& bias_fz = od->bias_fz;
   bias_fz = pl.fbase;
@@ -1378,7 +1377,7 @@ int close_graw(const bhg_mlp* m, const void* const* dir, const ChainMode& cm, co
   if (alpha_in_gram) { g.do_alpha = 1; g.alpha = od.aa; }
   if (blk + (alpha_in_gram ? 1 : 0) > 0) launch_wsk_group(g, blk + (alpha_in_gram ? 1 : 0), st);
 #endif
-  const bool full = pl.cg && cm.proj >= 2;   // fully projected CG: r.raw, p.raw, raw.raw from batch-sized arrays (k_pstep)
+  const bool full = pl.cg && pl.proj >= 2;   // fully projected CG: r.raw, p.raw, raw.raw from batch-sized arrays (k_pstep)
   SmallOutArgs so{};
   int small_blocks = 0;
   if (small_in_graw) {   // the small slices' outputs (head weight, biases) with their CG epilogue: block classes of the closing launch
@@ -1512,7 +1511,7 @@ int close_outputs(const bhg_mlp* m, const void* const* dir, const ChainMode& cm,
   const HoistPlan* hp = pl.hp;
   // one launch for all outputs when every MFMA layer is all-interior
   // (fully projected CG: the MFMA layers' slices of r and p are not materialised — only the small slices' blocks launch)
-  const bool proj_full = hp && ((pl.cg && cm.proj >= 2) || (!pl.cg && cm.proj));   // no N-sized state: only the small slices' blocks
+  const bool proj_full = hp && ((pl.cg && pl.proj >= 2) || (!pl.cg && pl.proj));   // no N-sized state: only the small slices' blocks
   const int n_mfma = proj_full ? 0 : (pl.head ? L - 1 : L);
   OuterAllArgs oa{};
   bool all_fast = !pl.no_outer_all && n_mfma <= kOuterAllMax && pl.head;
@@ -1600,11 +1599,11 @@ int chain_close(const bhg_mlp* m, const void* const* dir, const ChainMode& cm, c
   // (projected Neumann: EVERY iteration — the closing pass needs G(raw) of the last one)
   const bool alpha_alone = dbg(DBG_proj_alpha_alone, 0) != 0 || pl.gram_in_chain;   // A/B (packed Gram products: no Gram launch to ride in)
   const bool small_alone = dbg(DBG_proj_small_alone, 0) != 0;   // A/B
-  const bool small_in_graw = pl.proj_iter && (cm.proj >= 2 || !pl.cg) && !small_alone;
+  const bool small_in_graw = pl.proj_iter && (pl.proj >= 2 || !pl.cg) && !small_alone;
   // fully projected CG with the Gram products in the chain launches: nothing is left between the chain and the G(raw) launch but
   // the step length — and its only readers inside that launch are the small slices' blocks, which recompute it from the same
   // partials (alpha_compute, bit-identical in every block); the first of them publishes it and completes Rz(x)
-  const bool alpha_in_hoist = pl.cg && pl.proj_iter && cm.proj >= 2 && small_in_graw && pl.gram_in_chain && cm.gphase == 0 &&
+  const bool alpha_in_hoist = pl.cg && pl.proj_iter && pl.proj >= 2 && small_in_graw && pl.gram_in_chain && cm.gphase == 0 &&
                               dbg(DBG_alpha_in_hoist, 1) != 0;
   const bool alpha_in_gram = pl.cg && pl.proj_iter && !alpha_alone;
   if (pl.cg && !alpha_in_gram && !alpha_in_hoist) hipLaunchKernelGGL(k_cg_alpha, dim3(1), dim3(kThreads), 0, st, od.aa);
@@ -1689,7 +1688,7 @@ using namespace bhg;
 extern "C" {
 
 size_t bhg_mlp_partial_floats(const bhg_mlp* m) {
-  if (!m || m->L < 1 || m->L > BHG_MLP_MAX_LAYERS) return 0;
+  if (!mlp_desc_ok(m)) return 0;
   size_t mx = 0;
   for (int l = 0; l < m->L; ++l) {
     // R-forward of layer l (N = dims[l+1], K = dims[l]) and R-backward into layer l (N = dims[l], K = dims[l+1])
@@ -1750,19 +1749,19 @@ int bhg_mlp_neumann_mixed_coeff(const bhg_mlp* m, const void* const* v_last, con
 
 int bhg_mlp_supports_fused_solve(const bhg_mlp* m) {
   const bool off = dbg(DBG_mlp_no_fused_solve, 0) != 0;   // A/B switch: callers fall back to HVP + recurrence kernel
-  return !off && m && m->L >= 1 && m->L <= BHG_MLP_MAX_LAYERS && m->Bp > 0 && m->Bp % kTM == 0 && use_head(m);
+  return !off && mlp_desc_tiled(m) && use_head(m);
 }
 
 // The time-out word of the in-launch beta exchange (poll_beta, wskp.inc): non-zero after a solve whose pollers gave up.
 void* bhg_mlp_timeout_flag_dev(const bhg_mlp* m, void* fws) {
-  if (!m || !fws || m->L < 1 || m->L > BHG_MLP_MAX_LAYERS || m->Bp <= 0) return nullptr;
+  if (!mlp_desc_ok(m) || !fws) return nullptr;
   FusedWs w;
   carve_fused_ws(m, fws, &w);
   return w.gran + 1;
 }
 
 const float* bhg_mlp_head_j_dev(const bhg_mlp* m, void* fws, int* rows, int* cols) {
-  if (!m || m->L < 1 || m->L > BHG_MLP_MAX_LAYERS || m->Bp <= 0 || !fws) return nullptr;
+  if (!mlp_desc_ok(m) || !fws) return nullptr;
   FusedWs w;
   carve_fused_ws(m, fws, &w);
   if (w.nT2j == 0) return nullptr;
@@ -1772,7 +1771,7 @@ const float* bhg_mlp_head_j_dev(const bhg_mlp* m, void* fws, int* rows, int* col
 }
 
 size_t bhg_mlp_fused_ws_bytes(const bhg_mlp* m) {
-  if (!m || m->L < 1 || m->L > BHG_MLP_MAX_LAYERS || m->Bp <= 0) return 0;
+  if (!mlp_desc_ok(m)) return 0;
   FusedWs w;
   carve_fused_ws(m, nullptr, &w);
   return w.bytes;
@@ -1793,12 +1792,11 @@ struct CgCtx {
   const bhg_mlp* m; float* x; float* r; float* p; const int64_t* starts; const bhg_chunk* chunks_dev; int n_chunks, K;
   float cg_alpha, shift;
   FusedWs w; double* scal; const double* partR0; int n_init, pgrid, bgrid;
-  bool lazy, hoist, lin, lin_head, head_j; int proj_level;
   const void* const* rhs;
-  BetaArgs ba; HoistPlan hplan;
+  BetaArgs ba; SolvePlan plan;
   const void* dir[2 * BHG_MLP_MAX_LAYERS];
 };
-// global: the global-batch solver (bhg_mlp_cg_global_phase) — lazy direction, N-sized residual (it is what the ranks exchange)
+// Pointer set-up only: the form of the solve is plan_solve's (global: see there)
 static void cg_ctx_init(CgCtx* c, const bhg_mlp* m, float* x, float* r, float* p, const int64_t* starts, const bhg_chunk* chunks_dev,
                         int n_chunks, int K, float cg_alpha, float hvp_shift, void* ws, void* fws, bool global) {
   c->m = m; c->x = x; c->r = r; c->p = p; c->starts = starts; c->chunks_dev = chunks_dev; c->n_chunks = n_chunks; c->K = K;
@@ -1810,9 +1808,7 @@ static void cg_ctx_init(CgCtx* c, const bhg_mlp* m, float* x, float* r, float* p
   c->n_init = n_chunks < kMaxBlocks ? n_chunks : kMaxBlocks;
   for (int i = 0; i < 2 * m->L; ++i) c->dir[i] = p + starts[i];
   c->pgrid = n_chunks < kMaxBlocks ? n_chunks : kMaxBlocks;
-  // Direction update between two iterations: lazy (default; see k_cg_beta) or the 12*N-byte k_cg_pdir pass (A/B switch)
-  const bool eager = dbg(DBG_cg_eager_p, 0) != 0;
-  c->lazy = global || !eager;
+  plan_solve(m, 0, x != nullptr, global, &c->plan);
   BetaArgs& ba = c->ba;
   ba = BetaArgs{};
   int small_total = 0;
@@ -1827,31 +1823,14 @@ static void cg_ctx_init(CgCtx* c, const bhg_mlp* m, float* x, float* r, float* p
     }
   }
   c->bgrid = small_total > 0 ? (small_total + kThreads - 1) / kThreads : 1;   // one element of the small slices per thread
-  c->hplan.ok = false;
-  if (c->lazy && hoist_mode() != 0) hoist_plan(m, &c->hplan);
-  c->hoist = c->lazy && c->hplan.ok;
-  // projection level: 1 = G(r) by recurrence, the N-sized r / p still updated by k_outer_all (needed when the caller wants x);
-  // 2 = fully projected (default without a solution vector): no N-sized state after the first iteration
-  // (BHG_MLP_PROJ: 0 off | 1 default | 9 level 1 even without a solution vector — the A/B arm of level 2)
-  c->proj_level = (!c->hoist || !c->hplan.proj_ok || proj_mode() == 0 || global) ? 0 : ((proj_mode() == 9 || x) ? 1 : 2);
-  // the chain's first product by linearity (k_wskpl): fully projected CG closing with k_graw that applies the residual step (the
-  // conditions of plan_chain's graw_single and rnew), a net with a product between the first and the pre-head one, few small tensors
-  c->lin = c->proj_level == 2 && c->hplan.lin_ok && graw_single_on(packed_chain_on(c->w), m->Bp) && rnew_keys_on() &&
-           c->ba.nt <= 16 && proj_step_merged() && dbg(DBG_pstep_v2, 1) != 0 && dbg(DBG_lin_first, 1) != 0;
-  // ... and on a four-layer net the update blocks ride in the head launch (k_headu, headu.inc) rather than in the pre-head one: the head's
-  // prefetching instance must apply (<= 12 classes, last hidden width <= 512), and like lin it holds for the whole solve (slot parity)
-  c->lin_head = c->lin && m->L == 4 && dbg(DBG_lin_update_next, 1) != 0 && dbg(DBG_lin_update_in_head, 1) != 0 && dbg(DBG_lin_nub, 0) == 0 &&
-                m->dims[m->L] <= 12 && m->dims[m->L - 1] <= 512 && dbg(DBG_head_no_prefetch, 0) == 0;
-  // ... whose rows can take the pre-head product through J = W_3 diag(mask_2) W_2, built once per solve: the pre-head launch leaves the
-  // dependency chain, its tiles ride in the head launch (k_headj, bhg_mlp_headj.hip).  Debug key head_j = 0: today's six launches.
-  c->head_j = c->lin_head && c->w.nT2j > 0 && dbg(DBG_head_j, 1) != 0;
 }
 // gphase 0: the whole iteration (one rank) | 1: up to this rank's p.H_data p | 2: from the step length on (see ChainMode)
 static int cg_iteration(CgCtx* c, int k, int gphase, double* php, double inv_world, hipStream_t st) {
   const bhg_mlp* m = c->m;
   FusedWs& w = c->w;
   const int K = c->K;
-  const bool lazy = c->lazy, hoist = c->hoist;
+  const SolvePlan& sp = c->plan;
+  const bool lazy = sp.lazy, hoist = sp.hoist;
   hipEvent_t ta, tb, tc, td;
   const bool timed = gphase == 0 && span_begin(BHG_TIMING_MLP_HVP, &ta, &tb);
   const bool timed_it = gphase == 0 && span_begin(BHG_TIMING_MLP_CG_ITER, &tc, &td);
@@ -1859,7 +1838,7 @@ static int cg_iteration(CgCtx* c, int k, int gphase, double* php, double inv_wor
   if (lazy && k > 0 && gphase != 2) {   // beta, p.p of the coming direction, direction update of the small slices
     c->ba.part = w.partRR[k & 1];
     // hoisted, not projected: inside k_hoist; fully projected: k_proj_scalars (end of the last iteration) + k_proj_update
-    if (!hoist || c->proj_level == 1) hipLaunchKernelGGL(k_cg_beta, dim3(c->bgrid), dim3(kThreads), 0, st, c->ba);
+    if (!hoist || sp.proj_level == 1) hipLaunchKernelGGL(k_cg_beta, dim3(c->bgrid), dim3(kThreads), 0, st, c->ba);
   }
   if (timed) BHG_HIP_CHECK(hipEventRecord(ta, st));
   ChainMode cm{};
@@ -1884,17 +1863,13 @@ static int cg_iteration(CgCtx* c, int k, int gphase, double* php, double inv_wor
   cm.skip_outputs = (!c->x && k == K - 1) ? 1 : 0;
   cm.first = k == 0;
   cm.kpar = k & 1;
-  cm.hoist = hoist ? &c->hplan : nullptr;
+  cm.sp = &sp;
   cm.beta = &c->ba; cm.beta_blocks = c->bgrid;
-  cm.proj = c->proj_level;
   cm.gphase = gphase; cm.php = php; cm.inv_world = inv_world;
   cm.second = k == 1;
-  if (c->proj_level == 2 && proj_step_merged())   // the first bias's direction: flat p in iteration 0, then the slot of the parity
+  if (sp.proj_level == 2 && proj_step_merged())   // the first bias's direction: flat p in iteration 0, then the slot of the parity
     c->dir[1] = k == 0 ? static_cast<const void*>(c->p + c->starts[1]) : static_cast<const void*>(w.pb0[k & 1]);
-  if (c->lin) c->dir[3] = k == 0 ? static_cast<const void*>(c->p + c->starts[3]) : static_cast<const void*>(w.pb1[k & 1]);
-  cm.lin = c->lin ? 1 : 0;
-  cm.lin_head = c->lin_head ? 1 : 0;
-  cm.head_j = c->head_j ? 1 : 0;
+  if (sp.lin) c->dir[3] = k == 0 ? static_cast<const void*>(c->p + c->starts[3]) : static_cast<const void*>(w.pb1[k & 1]);
   cm.rhs = c->rhs;
   if (int rc = run_chain(m, c->dir, cm, st)) return rc;
   if (timed) BHG_HIP_CHECK(hipEventRecord(tb, st));
@@ -1914,13 +1889,10 @@ int bhg_mlp_cg_solve(const bhg_mlp* m, float* x, float* r, float* p, const int64
 }
 
 unsigned long long bhg_mlp_cg_state_mask(const bhg_mlp* m, int has_x) {
-  if (!m || m->L < 1 || m->L > BHG_MLP_MAX_LAYERS || 2 * m->L > 64 || has_x || !bhg_mlp_supports_fused_solve(m)) return ~0ull;
-  // cg_ctx_init's decision with x == NULL (nothing in it depends on the state pointers)
-  HoistPlan hp;
-  hp.ok = false;
-  if (dbg(DBG_cg_eager_p, 0) == 0 && hoist_mode() != 0) hoist_plan(m, &hp);
-  const bool level2 = hp.ok && hp.proj_ok && proj_mode() != 0 && proj_mode() != 9;
-  if (!level2 || dbg(DBG_cg_rhs_direct, 1) == 0) return ~0ull;
+  if (!mlp_desc_ok(m) || 2 * m->L > 64 || !bhg_mlp_supports_fused_solve(m)) return ~0ull;
+  SolvePlan sp;
+  plan_solve(m, 0, has_x != 0, false, &sp);
+  if (sp.proj_level != 2 || dbg(DBG_cg_rhs_direct, 1) == 0) return ~0ull;
   unsigned long long mask = 0ull;
   for (int l = 0; l < m->L; ++l) mask |= 1ull << (2 * l + 1);   // biases
   mask |= 1ull << (2 * (m->L - 1));                              // the narrow head weight (use_head holds: the fused solve needs it)
@@ -1941,13 +1913,13 @@ int bhg_mlp_cg_solve_rhs(const bhg_mlp* m, float* x, float* r, float* p, const i
   hipStream_t st = static_cast<hipStream_t>(stream);
   CgCtx c;
   cg_ctx_init(&c, m, x, r, p, starts, chunks_dev, n_chunks, K, cg_alpha, hvp_shift, ws, fws, false);
-  BHG_REQUIRE(!rhs || c.proj_level == 2, "rhs names the right-hand side for the FULLY PROJECTED solver only (see bhg_mlp_cg_state_mask)");
+  BHG_REQUIRE(!rhs || c.plan.proj_level == 2, "rhs names the right-hand side for the FULLY PROJECTED solver only (see bhg_mlp_cg_state_mask)");
   if (rhs)
     for (int l = 0; l + 1 < m->L; ++l) BHG_REQUIRE(rhs[2 * l] && ((uintptr_t)rhs[2 * l] & 15) == 0, "rhs tensors must be 16-byte aligned device pointers");
   c.rhs = rhs;
-  if (c.hoist && packed_chain_on(c.w) && !m->prepacked)   // (prepacked: bhg_mlp_forward_packed / _backward_packed left the packed operands)
+  if (c.plan.hoist && c.plan.packed && !m->prepacked)   // (prepacked: bhg_mlp_forward_packed / _backward_packed left the packed operands)
     if (int rc = pack_operands(m, c.w, st)) return rc;
-  if (c.head_j && K >= 2)   // (the projected iterations 1 .. K-1 read J)
+  if (c.plan.head_j && K >= 2)   // (the projected iterations 1 .. K-1 read J)
     if (int rc = build_head_j(m, c.w, st)) return rc;
   for (int k = 0; k < K; ++k)
     if (int rc = cg_iteration(&c, k, 0, nullptr, 1.0, st)) return rc;
@@ -1989,7 +1961,7 @@ int bhg_mlp_cg_global_phase(const bhg_mlp* m, float* x, float* r, float* p, cons
     BHG_HIP_CHECK(hipGetLastError());
     return BHG_OK;
   }
-  if (k == 0 && phase == BHG_CG_GLOBAL_CHAIN && c.hoist && packed_chain_on(c.w) && !m->prepacked)
+  if (k == 0 && phase == BHG_CG_GLOBAL_CHAIN && c.plan.hoist && c.plan.packed && !m->prepacked)
     if (int rc = pack_operands(m, c.w, st)) return rc;
   if (int rc = cg_iteration(&c, k, phase == BHG_CG_GLOBAL_CHAIN ? 1 : 2, php, 1.0 / (double)world, st)) return rc;
   BHG_HIP_CHECK(hipGetLastError());
@@ -1997,33 +1969,22 @@ int bhg_mlp_cg_global_phase(const bhg_mlp* m, float* x, float* r, float* p, cons
 }
 
 // ---- global-batch CG, FACTOR-EXCHANGE form (mlp/fx.inc; include/bhg.h) ---------------------------------------------------------------------
-int bhg_mlp_fx_supported(const bhg_mlp* m, int world) {
-  if (!m || m->L < 1 || m->L > BHG_MLP_MAX_LAYERS || m->Bp <= 0 || m->Bp % kTM != 0 || !bhg_mlp_supports_fused_solve(m)) return 0;
-  FxPlan fp;
-  fx_plan(m, world, &fp);
-  return fp.ok && dbg(DBG_packed_chain, 1) != 0 ? 1 : 0;
+// the plan of the form where the network takes it (what every size query below and fx_phase ask first)
+static bool fx_plan_if_supported(const bhg_mlp* m, int world, FxPlan* fp) {
+  if (!mlp_desc_tiled(m) || !bhg_mlp_supports_fused_solve(m)) return false;
+  fx_plan(m, world, fp);
+  return fp->ok && dbg(DBG_packed_chain, 1) != 0;
 }
+int bhg_mlp_fx_supported(const bhg_mlp* m, int world) { FxPlan fp; return fx_plan_if_supported(m, world, &fp) ? 1 : 0; }
 size_t bhg_mlp_fx_ws_bytes(const bhg_mlp* m, int world) {
-  if (!bhg_mlp_fx_supported(m, world)) return 0;
-  FxPlan fp; fx_plan(m, world, &fp);
+  FxPlan fp;
+  if (!fx_plan_if_supported(m, world, &fp)) return 0;
   FxWs x; fx_carve(m, fp, nullptr, &x);
   return x.bytes;
 }
-size_t bhg_mlp_fx_const_floats(const bhg_mlp* m) {
-  if (!bhg_mlp_fx_supported(m, 1)) return 0;
-  FxPlan fp; fx_plan(m, 1, &fp);
-  return fp.const_floats;
-}
-size_t bhg_mlp_fx_slab_floats(const bhg_mlp* m) {
-  if (!bhg_mlp_fx_supported(m, 1)) return 0;
-  FxPlan fp; fx_plan(m, 1, &fp);
-  return fp.slab_floats;
-}
-size_t bhg_mlp_fx_scal_doubles(const bhg_mlp* m) {
-  if (!bhg_mlp_fx_supported(m, 1)) return 0;
-  FxPlan fp; fx_plan(m, 1, &fp);
-  return fp.scal_doubles;
-}
+size_t bhg_mlp_fx_const_floats(const bhg_mlp* m) { FxPlan fp; return fx_plan_if_supported(m, 1, &fp) ? fp.const_floats : 0; }
+size_t bhg_mlp_fx_slab_floats(const bhg_mlp* m) { FxPlan fp; return fx_plan_if_supported(m, 1, &fp) ? fp.slab_floats : 0; }
+size_t bhg_mlp_fx_scal_doubles(const bhg_mlp* m) { FxPlan fp; return fx_plan_if_supported(m, 1, &fp) ? fp.scal_doubles : 0; }
 // algo 0: CG (cg.py:34-56; k = 0 .. K-1, END at k = K-1) | 1: Neumann (neumann.py:59-66; CHAIN for k = 0 .. K — the last one is the closing half
 // pass, forward chain + head only: Rz(v_K) — GRAM for k = 0 .. K-1, END at k = K)
 static int fx_phase(int algo, const bhg_mlp* m, const void* const* rhs, int k, int K, int phase, int world, int rank, float* const_all,
@@ -2094,21 +2055,17 @@ int bhg_mlp_neumann_solve(const bhg_mlp* m, float* v0, float* v1, float* p, cons
   hipStream_t st = static_cast<hipStream_t>(stream);
   FusedWs w;
   carve_fused_ws(m, fws, &w);
-  // Hoisting alone (direction products on the N-sized v every iteration, BHG_MLP_HOIST=2) neither gains nor loses for Neumann
-  // (656 vs 656 steps/s at cfg 2: no step length, no lazy direction, no beta launch to save) and is an A/B arm only.  The
-  // PROJECTED form (default without an accumulator vector) is the Neumann twin of the fully projected CG solver:
+  // The PROJECTED form (plan_solve: the default without an accumulator vector) is the Neumann twin of the fully projected CG solver:
   //     G(v_{k+1}) = G(v_k) - alpha (G(raw_k) + shift G(v_k)),   G(raw) from B x B Gram matrices (see k_proj_update)
   // — no scalars at all, nothing N-sized after the first iteration; the small slices (biases, head weight) keep their
   // explicit epilogues.  The mixed coefficient needs Rz(sum_k v_k): the head kernel sums Rz(v_k), k < K, as before, and a
   // closing half pass (update + forward chain + head) adds Rz(v_K) — instead of bhg_mlp_neumann_mixed_coeff's R-forward over
   // the N-sized v_K, which no longer exists.
-  HoistPlan hplan;
-  hplan.ok = false;
-  const bool want_proj = !p && K > 0 && proj_mode() != 0 && hoist_mode() != 0;
-  if (hoist_mode() == 2 || want_proj) hoist_plan(m, &hplan);
-  const bool proj = want_proj && hplan.ok && hplan.proj_ok && use_head(m);
+  SolvePlan sp;
+  plan_solve(m, 1, p != nullptr, false, &sp);
+  const bool proj = sp.proj_level && K > 0;
   if (projected_out) *projected_out = proj ? 1 : 0;   // the caller hands it to bhg_mlp_neumann_mixed_coeff (no hidden per-workspace state)
-  if (hplan.ok && K > 0 && packed_chain_on(w) && !m->prepacked)
+  if (sp.hoist && K > 0 && sp.packed && !m->prepacked)
     if (int rc = pack_operands(m, w, st)) return rc;
   for (int k = 0; k < K; ++k) {
     float* vin = (k & 1) ? v1 : v0;
@@ -2129,8 +2086,7 @@ int bhg_mlp_neumann_solve(const bhg_mlp* m, float* v0, float* v1, float* p, cons
     cm.first = k == 0;
     if (!p) { cm.x_mode = 1; cm.rzx_acc = w.rzx; }
     cm.ws = &w;
-    cm.hoist = hplan.ok ? &hplan : nullptr;   // every direction product in one grouped launch (k_hoist), as in the CG solver
-    cm.proj = proj ? 1 : 0;
+    cm.sp = &sp;   // (hoist: every direction product in one grouped launch (k_hoist), as in the CG solver)
     cm.nk = k;
     if (int rc = run_chain(m, dir, cm, st)) return rc;
     if (timed) BHG_HIP_CHECK(hipEventRecord(tb, st));
@@ -2144,7 +2100,7 @@ int bhg_mlp_neumann_solve(const bhg_mlp* m, float* v0, float* v1, float* p, cons
     cm.fa = (K & 1) ? v0 : v1; cm.fb = nullptr; cm.fd = vin; cm.starts = starts;
     cm.alpha = alpha; cm.shift = hvp_shift;
     cm.x_mode = 1; cm.rzx_acc = w.rzx; cm.first = 0;
-    cm.ws = &w; cm.hoist = &hplan; cm.proj = 1; cm.stop_after_head = 1; cm.nk = K;
+    cm.ws = &w; cm.sp = &sp; cm.stop_after_head = 1; cm.nk = K;
     if (int rc = run_chain(m, dir, cm, st)) return rc;
   }
   return BHG_OK;
@@ -2177,7 +2133,7 @@ static int check_head_problem(const bhg_mlp* m) {
 static bool narrow_head(const bhg_mlp* m) { return m->dims[m->L] <= kSmallC && (m->dims[m->L - 1] & 3) == 0; }
 
 int bhg_mlp_supports_native_prepare(const bhg_mlp* m) {
-  return m && m->L >= 1 && m->L <= BHG_MLP_MAX_LAYERS && m->Bp > 0 && m->Bp % kTM == 0;
+  return mlp_desc_tiled(m);
 }
 
 }  // extern "C"
@@ -2444,8 +2400,8 @@ int bhg_mlp_mixed_coeff(const bhg_mlp* m, const void* const* dir, const int64_t*
 
 // ---- the plan, described without running it (round 6; host only: no launch, no device access) -----------------------------------------
 // Which form bhg_mlp_cg_solve (algo 0) / bhg_mlp_neumann_solve (algo 1) takes for this descriptor is decided by host logic alone —
-// hoist_plan (shapes, cost model), cg_ctx_init (projection level, the linear first product, the head launch with the recurrences) —
-// before the first launch.  This entry point evaluates exactly that logic on the shapes and prints the decision, so that the map
+// hoist_plan (shapes, cost model), plan_solve (projection level, the linear first product, the head launch with the recurrences) —
+// before the first launch.  This entry point calls exactly that logic on the shapes and prints the decision, so that the map
 // "shape -> form" has a unit test of its own that runs on a CPU-only box (tests/test_plan_selection.py); the GPU suite ties the
 // description to the launch counters (bhg_mlp_hoist_launches / _proj_iterations / _lin_launches) on the same shapes.
 int bhg_mlp_plan_describe(const bhg_mlp* m, int algo, int keep_solution, char* buf, size_t buf_bytes) {
@@ -2453,38 +2409,21 @@ int bhg_mlp_plan_describe(const bhg_mlp* m, int algo, int keep_solution, char* b
   BHG_REQUIRE(buf && buf_bytes >= 64, "output buffer too small");
   BHG_REQUIRE(algo == 0 || algo == 1, "algo: 0 = cg, 1 = neumann");
   const int L = m->L;
-  const bool fused = bhg_mlp_supports_fused_solve(m) != 0;
-  HoistPlan hp;
-  hoist_plan(m, &hp);
+  SolvePlan sp;
+  plan_solve(m, algo, keep_solution != 0, false, &sp);
+  const bool fused = sp.fused;
+  const int hoist = sp.hoist ? 1 : 0, proj_level = sp.proj_level, lin = sp.lin ? 1 : 0, lin_head = sp.lin_head ? 1 : 0;
+  const int upd_first = sp.upd_first ? 1 : 0, head_j = sp.head_j ? 1 : 0;
+  const char* closing = sp.closing;
   const char* form = "unfused";
-  int hoist = 0, proj_level = 0, lin = 0, lin_head = 0, upd_first = 0, head_j = 0;
-  const char* closing = "k_outer_all";
-  if (fused) {
-    // the flat layout of [W_1, b_1, ...] (what the callers pass as `starts`), fake state pointers: nothing is dereferenced
-    int64_t numel[2 * BHG_MLP_MAX_LAYERS], starts[2 * BHG_MLP_MAX_LAYERS];
-    for (int l = 0; l < L; ++l) { numel[2 * l] = (int64_t)m->dims[l] * m->dims[l + 1]; numel[2 * l + 1] = m->dims[l + 1]; }
-    const int64_t nch = bhg_layout_num_chunks(numel, 2 * L);
-    std::vector<bhg_chunk> chunks((size_t)(nch > 0 ? nch : 1));
-    if (int rc = bhg_layout_build(numel, 2 * L, starts, chunks.data())) return rc;
-    float* const fake = reinterpret_cast<float*>((uintptr_t)1 << 30);
-    if (algo == 0) {
-      static CgCtx c;   // (large: off the stack)
-      cg_ctx_init(&c, m, keep_solution ? fake : nullptr, fake, fake, starts, nullptr, (int)nch, 2, 1.f, 0.f, fake, fake, false);
-      hoist = c.hoist ? 1 : 0; proj_level = c.proj_level; lin = c.lin ? 1 : 0; lin_head = c.lin_head ? 1 : 0; head_j = c.head_j ? 1 : 0;
-      upd_first = (c.lin && L > 4) ? 1 : 0;
-      form = !c.lazy ? "classic-eager" : (!c.hoist ? "classic" : (c.proj_level == 0 ? "hoisted" : (c.proj_level == 1 ? "projected-keep-state" :
-             (c.lin ? (c.lin_head ? "six-launch (k_wskpl .. k_headu .. k_graw)" : "six-launch-class (k_wskpl first, recurrences beside the chain)") :
-              "fully-projected (k_pstep launch)"))));
-      if (c.proj_level >= 1) closing = graw_batch_ok(m->Bp) ? (m->Bp == 128 ? "k_graw" : "k_grawk") : "k_hoist+k_proj_update";
-    } else {
-      const bool want_proj = !keep_solution && proj_mode() != 0 && hoist_mode() != 0;
-      const bool proj = want_proj && hp.ok && hp.proj_ok && use_head(m);
-      hoist = (hp.ok && (hoist_mode() == 2 || want_proj)) ? 1 : 0;
-      proj_level = proj ? 1 : 0;
-      form = proj ? "projected-neumann (update inside k_graw)" : (hoist ? "hoisted" : "classic");
-      if (proj) closing = graw_batch_ok(m->Bp) ? (m->Bp == 128 ? "k_graw" : "k_grawk") : "k_hoist+k_proj_update";
-    }
-  }
+  if (fused && algo == 0)
+    form = !sp.lazy ? "classic-eager" : (!sp.hoist ? "classic" : (proj_level == 0 ? "hoisted" : (proj_level == 1 ? "projected-keep-state" :
+           (sp.lin ? (sp.lin_head ? "six-launch (k_wskpl .. k_headu .. k_graw)" : "six-launch-class (k_wskpl first, recurrences beside the chain)") :
+            "fully-projected (k_pstep launch)"))));
+  else if (fused)
+    form = proj_level ? "projected-neumann (update inside k_graw)" : (sp.hoist ? "hoisted" : "classic");
+  HoistPlan hp;   // the shape facts below are those of the descriptor, whatever the solve asks for
+  hoist_plan(m, &hp);
   size_t gram = 0;
   if (hp.ok && hp.proj_ok)
     for (int l = 0; l + 1 < L; ++l) gram += (size_t)m->Bp * m->Bp * (l >= 1 ? (2 + 2 * kGramSplitMax + 6) : 2);

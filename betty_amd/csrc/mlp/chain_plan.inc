@@ -1,5 +1,5 @@
 // Host side of run_chain (bhg_mlp.hip), no device code: the mode a caller asks for, the plan derived from it before the first launch,
-// and the state one stage leaves for a later one.  Included inside namespace bhg, after HoistPlan / FusedWs / SideState.
+// and the state one stage leaves for a later one.  Included inside namespace bhg, after SolvePlan / FusedWs / SideState.
 
 // What one pass of the HVP chain does with its weight-shaped outputs.
 struct ChainMode {
@@ -23,20 +23,16 @@ struct ChainMode {
   double* rzx_acc;              // FUSE_NEUMANN without an accumulator vector: sum_k Rz(v_k) lands here (head kernel)
   int skip_outputs;             // FUSE_CG: stop after the step length (see bhg_mlp_cg_solve)
   int gemm_mode;                // FUSE_NONE: BHG_MLP_WSK-style mode asked for by the caller (bhg_mlp_hvp_mode)
-  const HoistPlan* hoist;       // FUSE_CG + lazy: run the hoisted form of the chain (k_hoist); NULL = the classic chain
+  const SolvePlan* sp;          // fused: the form of the whole solve (plan_solve decides; every pass of a solve is handed the same one)
   const BetaArgs* beta; int beta_blocks;   // hoisted form: k_cg_beta's work rides in k_hoist's launch (iterations > 0)
-  int proj;                     // hoisted: direction products from batch-sized recurrences (k_proj_update); CG: 1 / 2, Neumann: 1
   int stop_after_head;          // projected Neumann: the closing pass that only adds Rz(v_K) to the accumulated Rz sums
   // global-batch CG (bhg_mlp_cg_global_phase): the iteration is cut where the ranks must talk.
   //   gphase 1: the R-chain only; this rank's share of p.H_data p -> php[0] (k_php_local)
   //   gphase 2: step length from the all-reduced php[0] * inv_world, then the outputs with their epilogues
   int gphase; double* php; double inv_world;
   int second;                   // fully projected CG: iteration 1 (the scalars k_proj_step completes are those of the FIRST iteration)
-  int lin;                      // fully projected CG: the chain's first product by linearity, update launch inside it (k_wskpl; cg_ctx_init decides)
   int nk;                       // projected Neumann: iteration index (the row-major Rh_0 lives in two slots by its parity, see vnew)
   const void* const* rhs;       // fully projected CG, first iteration: the right-hand side's own tensors (bhg_mlp_cg_solve_rhs) or NULL
-  int lin_head;                 // lin on a four-layer net: the update blocks ride in the HEAD launch (k_headu), the pre-head launch is the plain product
-  int head_j;                   // lin_head with the head rows reading J (k_headj): no pre-head launch, its tiles ride in the head launch
 };
 
 // What one pass of the chain decides before its first launch (plan_chain).  The stages of run_chain read it; none of them changes it.
@@ -61,25 +57,13 @@ struct ChainPlan {
   bool do_chain;                // (global-batch CG, second phase: the chain ran in the first)
   // projected CG, not the last iteration (projected Neumann: EVERY iteration): the iteration ends with the G(raw) products
   bool proj_iter;
-  // round 4: the chain through the constant weights on PACKED operands (wskp.inc), the per-iteration Gram products T_l / E_l as
-  // extra workgroups of the chain launch that consumes the same packed activation (debug keys packed_chain / packed_gram: A/B)
-  bool packed, gram_in_chain;
-  // graw_single: what the NEXT iteration's recurrences are told about the layout of G(raw) (one slab per product, not one per pair;
-  // see graw_single_on); graw2: this iteration closes with k_graw
-  bool graw_single, graw2;
-  // rnew: k_graw applies r' = r - alpha Hp to G(r) itself (GrawArgs.rnew) — like graw_single, what the NEXT iteration's recurrences
-  // are told (G(r) is up to date, there is no G(raw)); the conditions are those of the step length computed inside k_graw
-  bool rnew;
-  // vnew (round 5): the projected Neumann solver's k_graw applies v' = v - alpha (raw + shift v) to G(v) itself and leaves Rh_0(v') packed
-  // and row-major — neumann.py:63 has no scalars to wait for — so the update launch at the top of the next iteration (k_proj_update) is
-  // gone: SIX launches per iteration instead of seven.  Like rnew a property of the whole solve.  The row-major Rh_0 alternates between
-  // m->Rh[0] and a second slot (iteration parity): the Gb_1 tiles of the launch that writes Rh_0(v') still read Rh_0(v).
-  bool vnew;
-  // lin: the chain's first product by linearity with the update launch riding in it (k_wskpl, wskpl.inc) — like rnew a property of
-  // the whole solve: every iteration's first product, every k_graw (Rh_0(r') for the next one) and cg_iteration (the second bias's
-  // direction in slots) follow it.  lin_head: see ChainMode
-  bool lin, lin_head;
-  bool head_j;                  // see ChainMode; applies to the iterations whose head launch carries the update blocks (all but the first)
+  // the per-iteration Gram products T_l / E_l as extra workgroups of the chain launch that consumes the same packed activation
+  // (debug key packed_gram: A/B); graw2: this pass closes with k_graw
+  bool gram_in_chain, graw2;
+  // Properties of the WHOLE solve, copied from SolvePlan (described there) for the stages to read; all zero where this pass runs the
+  // classic chain.  proj: SolvePlan.proj_level
+  int proj;
+  bool packed, graw_single, rnew, vnew, lin, lin_head, head_j;
 
   float* rh0_slot(int k) const { return (k & 1) ? hoist + hp->rh0alt_off : rh0; }                   // Rh_0(v_k), row-major (vnew)
   float* gp1(int par) const { return hoist + (par ? hp->gp1alt_off : hp->g_off[hp->gf[1]]); }       // Gf_1(p): two slots (lin)
@@ -129,22 +113,16 @@ int plan_chain(const bhg_mlp* m, const ChainMode& cm, ChainPlan* p) {
   for (int l = 0; l < L; ++l) { p->part_base_w[l] = base; base += outer_blocks(m, l, p->head); }
   p->part_base_bias = base;
 
-  const HoistPlan* hp = p->hp = ((cg && cm.lazy) || (cm.mode == FUSE_NEUMANN && p->single)) ? cm.hoist : nullptr;
+  const SolvePlan* sp = cm.sp;
+  const HoistPlan* hp = p->hp = (sp && sp->hoist && (cg || p->single)) ? &sp->hp : nullptr;
   p->hoist = hp ? cm.ws->hoist : nullptr;
   p->rh0 = m->Rh[0];
   p->do_chain = cm.gphase != 2;
-  p->proj_iter = hp && cm.proj && (cg ? (!cm.apply_out && !cm.skip_outputs) : true);
-  p->packed = hp && packed_chain_on(*cm.ws);
+  if (hp) { p->proj = sp->proj_level; p->packed = sp->packed; p->graw_single = sp->graw_single; p->rnew = sp->rnew; p->vnew = sp->vnew; }
+  if (hp) { p->lin = sp->lin; p->lin_head = sp->lin_head; p->head_j = sp->head_j; }
+  p->proj_iter = hp && p->proj && (cg ? (!cm.apply_out && !cm.skip_outputs) : true);
   p->gram_in_chain = p->packed && p->proj_iter && !cm.stop_after_head && dbg(DBG_packed_gram, 1) != 0;
-  p->graw_single = graw_single_on(p->packed, m->Bp);
   p->graw2 = p->gram_in_chain && p->graw_single;
-  p->rnew = p->graw_single && cg && cm.proj >= 2 && cm.gphase == 0 && rnew_keys_on();
-  p->vnew = cm.mode == FUSE_NEUMANN && hp && cm.proj && p->graw_single && L >= 3 && dbg(DBG_neumann_vnew, 1) != 0;
-  p->lin = cm.lin != 0;
-  BHG_REQUIRE(!p->lin || (p->rnew && hp && hp->lin_ok && cm.beta && cm.beta->nt <= 16 && proj_step_merged() && L >= 4),
-              "the linear first product was planned for a solve that cannot run it");
-  p->lin_head = p->lin && cm.lin_head != 0;
-  p->head_j = p->lin_head && cm.head_j != 0;
   return BHG_OK;
 }
 

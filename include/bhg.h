@@ -493,8 +493,8 @@ int bhg_mwn_backward(const float* ce, const float* coeff, int B, const float* w1
                      int H, float scale, float* gw1, float* gb1, float* gw2, float* gb2, void* stream);
 
 /* Host only (no launch, no device access): the form bhg_mlp_cg_solve (algo 0) / bhg_mlp_neumann_solve (algo 1) will take for this
- * descriptor, with (keep_solution != 0) or without a materialised solution / accumulator vector — the decision of hoist_plan and of the
- * solvers' set-up code, printed as `key=value` pairs into `buf` (form, hoist, proj_level, lin, lin_head, head_j, closing launch,
+ * descriptor, with (keep_solution != 0) or without a materialised solution / accumulator vector — the decision of hoist_plan and of
+ * plan_solve (csrc/mlp/solve_plan.inc: the one place that decides; the solvers and bhg_mlp_cg_state_mask read the same plan), printed as `key=value` pairs into `buf` (form, hoist, proj_level, lin, lin_head, head_j, closing launch,
  * workspace sizes).  Only L, B, Bp and dims of the descriptor are read.  For tests of the shape -> form map and for diagnostics; the reference has
  * no counterpart (its cg / neumann have one form: betty/hypergradient/cg.py:8-70, neumann.py:8-66).                                  */
 int bhg_mlp_plan_describe(const bhg_mlp* m, int algo, int keep_solution, char* buf, size_t buf_bytes);

@@ -1155,7 +1155,7 @@ def test_hoisted_and_projected_chain_match_classic_chain(algo, dims, B, K, bhg_d
 @pytest.mark.parametrize("dims", [[256, 256, 192, 640, 10], [256, 256, 128, 64, 24], [256, 256, 192, 640, 24]], ids=lambda v: str(v))
 def test_four_layer_nets_outside_the_head_launch_form(dims):
     """PRODUCT build, no key set: four-layer nets whose head k_headu does not take — a last hidden layer wider than 512, more than
-    12 classes — keep their update blocks in the pre-head launch (k_wskpu; `lin_head` in cg_ctx_init).  Against the un-fused loop,
+    12 classes — keep their update blocks in the pre-head launch (k_wskpu; `lin_head` in plan_solve).  Against the un-fused loop,
     bit-reproducible."""
     assert not _native.is_ab()
     lib = _native.load()

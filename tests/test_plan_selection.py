@@ -1,7 +1,7 @@
 """The map "shape -> solver form" (the plan logic had no unit test of its own beyond launch counters).
 
-``bhg_mlp_plan_describe`` (include/bhg.h) evaluates the host logic that picks the form — hoist_plan's shape rules and cost model, the
-solvers' set-up code (projection level, the chain's first product by linearity, the head launch with the recurrences, the closing
+``bhg_mlp_plan_describe`` (include/bhg.h) evaluates the host logic that picks the form — hoist_plan's shape rules and cost model,
+plan_solve (csrc/mlp/solve_plan.inc: projection level, the chain's first product by linearity, the head launch with the recurrences, the closing
 launch) — WITHOUT launching anything, so this file runs on the CPU box.  The GPU half ties the description to what the library then
 does: the launch counters of a real solve on the same shapes."""
 import pytest
@@ -69,6 +69,107 @@ def test_shape_to_form(dims, B, cg_free, cg_x, neu_free, neu_acc, closing):
         assert d["fx_slab_bytes"] >= 4 * Bp * (sum(dims[1:]) + sum(dims[1:-1])) and d["fx_ws_bytes_world8"] > 0
     else:
         assert d["fx_slab_bytes"] == 0 and d["fx_ws_bytes_world8"] == 0
+
+
+# ---- every debug key the plan reads: arm -> form, as literals (taken from the library before plan_solve existed) ------------------------
+# (form, proj_level, lin, lin_head, head_j, closing) of the solution-free CG plan and of the solution-free Neumann plan
+G, GK, HP = "k_graw", "k_grawk", "k_hoist+k_proj_update"
+
+
+def _six(closing, head_j=0):
+    return (SIX, 2, 1, 1, head_j, closing)
+
+
+def _six_class(closing):
+    return (SIX_CLASS, 2, 1, 0, 0, closing)
+
+
+def _pstep(closing):
+    return (PSTEP, 2, 0, 0, 0, closing)
+
+
+def _keep(closing):
+    return ("projected-keep-state", 1, 0, 0, 0, closing)
+
+
+def _neu(closing):
+    return (NEU, 1, 0, 0, 0, closing)
+
+
+def _off(form):
+    return (form, 0, 0, 0, 0, "k_outer_all")
+
+
+ARM_SHAPES = [([3072, 2048, 1536, 384, 10], 100), ([256, 384, 128, 10], 100), ([256, 256, 256, 256, 128, 10], 100), ([512, 256, 256, 64, 10], 200)]
+ARM_DEFAULT = [(_six(G, 1), _neu(G)), (_pstep(G), _neu(G)), (_six_class(G), _neu(G)), (_six(GK), _neu(GK))]   # (head_j: a padded batch of 128 only)
+_ALL_PSTEP = [(_pstep(G), _neu(G)), None, (_pstep(G), _neu(G)), (_pstep(GK), _neu(GK))]           # both six-launch forms fall back to the k_pstep launch
+_HEAD_OUT = [(_six_class(G), _neu(G)), None, None, (_six_class(GK), _neu(GK))]                     # the update blocks leave the head launch
+# one row per arm: the four shapes in order, None = as the default arm
+ARM_FORMS = {
+    None: [None] * 4,
+    ("mlp_proj", 0): [(_off("hoisted"), _off("classic"))] * 4,
+    ("mlp_proj", 9): [(_keep(G), _neu(G))] * 3 + [(_keep(GK), _neu(GK))],
+    ("mlp_hoist", 0): [(_off("classic"), _off("classic"))] * 4,
+    ("mlp_hoist", 2): [None] * 4,
+    ("cg_eager_p", 1): [(_off("classic-eager"), _neu(G))] * 3 + [(_off("classic-eager"), _neu(GK))],   # Neumann stays projected
+    ("lin_first", 0): _ALL_PSTEP,
+    ("lin_update_next", 0): _HEAD_OUT,
+    ("lin_update_in_head", 0): _HEAD_OUT,
+    ("lin_nub", 1): _HEAD_OUT,
+    ("head_no_prefetch", 1): _HEAD_OUT,
+    ("head_j", 0): [(_six(G, 0), _neu(G)), None, None, None],
+    ("packed_chain", 0): _ALL_PSTEP,
+    ("packed_gram", 0): _ALL_PSTEP,
+    ("graw_v2", 0): _ALL_PSTEP,
+    ("graw_kloop", 0): [None, None, None, (_pstep(HP), _neu(HP))],
+    ("rnew_in_graw", 0): _ALL_PSTEP,
+    ("alpha_in_hoist", 0): _ALL_PSTEP,
+    ("proj_small_alone", 1): _ALL_PSTEP,
+    ("proj_step_alone", 1): _ALL_PSTEP,
+    ("pstep_v2", 0): _ALL_PSTEP,
+    ("lin_deep", 0): [None, None, (_pstep(G), _neu(G)), None],
+    ("neumann_vnew", 0): [None] * 4,
+    ("cg_rhs_direct", 0): [None] * 4,
+    ("mlp_no_head", 1): [(_off("unfused"), _off("unfused"))] * 4,
+    ("mlp_no_fused_solve", 1): [(_off("unfused"), _off("unfused"))] * 4,
+    ("proj_max_ratio", 50): [None] + [(_off("hoisted"), _off("hoisted"))] * 3,
+}
+
+
+def _plan_tuple(d):
+    return (d["form"], d["proj_level"], d["lin"], d["lin_head"], d["head_j"], d["closing"])
+
+
+@pytest.mark.parametrize("arm", list(ARM_FORMS), ids=lambda a: "default" if a is None else f"{a[0]}={a[1]}")
+def test_arm_to_form(arm, bhg_debug):
+    if arm is not None:
+        bhg_debug.setenv(*arm)
+    for (dims, B), want, dflt in zip(ARM_SHAPES, ARM_FORMS[arm], ARM_DEFAULT):
+        got = (_plan_tuple(_native.plan_describe(dims, B, "cg")), _plan_tuple(_native.plan_describe(dims, B, "neumann")))
+        assert got == (want or dflt), (arm, dims, B)
+
+
+def _state_mask(dims, B, has_x):
+    d = _native.Mlp()
+    d.L, d.B, d.Bp = len(dims) - 1, int(B), (int(B) + 127) // 128 * 128
+    for i, v in enumerate(dims):
+        d.dims[i] = int(v)
+    import ctypes
+
+    return int(_native.load().bhg_mlp_cg_state_mask(ctypes.byref(d), has_x))
+
+
+@pytest.mark.parametrize("dims,B", [(c[0], c[1]) for c in CASES], ids=lambda v: str(v))
+def test_state_mask_follows_the_plan(dims, B):
+    """The tensors bhg_mlp_cg_solve_rhs reads from the flat state: all of them unless the solution-free CG plan is fully projected —
+    then exactly the biases and the head weight (bit 2 (L - 1))."""
+    L = len(dims) - 1
+    ones = (1 << 64) - 1
+    want = ones
+    if _native.plan_describe(dims, B, "cg")["proj_level"] == 2:
+        want = sum(1 << (2 * l + 1) for l in range(L)) | 1 << (2 * (L - 1))
+    assert _state_mask(dims, B, 0) == want
+    assert _state_mask(dims, B, 1) == ones
 
 
 def test_wide_head_has_no_fused_solver_and_the_twin_rounds_widths_up():
