@@ -139,6 +139,18 @@ SYMBOLS = {
         c_int,
         [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float, c_int, c_int, c_void_p],
     ),
+    "bhg_softreg_solve_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, c_char_p, c_size_t]),
+    "bhg_softreg_solve_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "bhg_softreg_cg_solve": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_float, c_int, c_int,
+         c_void_p],
+    ),
+    "bhg_softreg_neumann_solve": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_float, c_int, c_int,
+         c_void_p],
+    ),
     "bhg_mlp_partial_floats": (c_size_t, [POINTER(Mlp)]),
     "bhg_mlp_hvp": (c_int, [POINTER(Mlp), _PP, _PP, c_void_p]),
     "bhg_mlp_hvp_mode": (c_int, [POINTER(Mlp), _PP, _PP, c_int, c_void_p]),

@@ -377,6 +377,34 @@ class HipBackend:
             "bhg_logreg_neumann_solve",
         )
 
+    # -- softmax regression with per-weight L2: the multi-class sibling (csrc/bhg_softreg_solve.hip) ---------------------------
+    def softreg_solve_workspace(self, n: int, d: int, C: int, device) -> torch.Tensor:
+        return torch.empty(int(self.lib.bhg_softreg_solve_ws_bytes(int(n), int(d), int(C))), dtype=torch.uint8, device=device)
+
+    def softreg_cg_solve(self, X, W, lam, rhs, out, coeff, ws, K: int, cg_alpha: float, out_scale: float, form: int = 0,
+                         strips: int = 0) -> None:
+        """out <- out_scale * x_K of K CG iterations on H V = U^T X + lam * V (U from P = softmax(X W^T) and Z = X V^T) from x = 0,
+        r = p = rhs (the reference's iteration, ``cg_alpha`` quirk included); coeff (or None) <- W * out.  W, lam: [C, d]; rhs, out,
+        coeff: C * d floats, W's row-major order.  form: SOFTREG_FORM_AUTO / _SINGLE / _STRIPS."""
+        n, d = X.shape
+        _native.check(
+            self.lib.bhg_softreg_cg_solve(X.data_ptr(), W.data_ptr(), lam.data_ptr(), rhs.data_ptr(), out.data_ptr(),
+                                          None if coeff is None else coeff.data_ptr(), ws.data_ptr(), n, d, int(W.shape[0]), int(K),
+                                          float(cg_alpha), float(out_scale), int(form), int(strips), _stream_ptr()),
+            "bhg_softreg_cg_solve",
+        )
+
+    def softreg_neumann_solve(self, X, W, lam, rhs, out, coeff, ws, K: int, alpha: float, out_scale: float, form: int = 0,
+                              strips: int = 0) -> None:
+        """out <- out_scale * p_K of K Neumann iterations v <- v - alpha H v, p <- p + v from v = p = rhs; coeff (or None) <- W * out."""
+        n, d = X.shape
+        _native.check(
+            self.lib.bhg_softreg_neumann_solve(X.data_ptr(), W.data_ptr(), lam.data_ptr(), rhs.data_ptr(), out.data_ptr(),
+                                               None if coeff is None else coeff.data_ptr(), ws.data_ptr(), n, d, int(W.shape[0]), int(K),
+                                               float(alpha), float(out_scale), int(form), int(strips), _stream_ptr()),
+            "bhg_softreg_neumann_solve",
+        )
+
 
 LOGREG_FORM_AUTO, LOGREG_FORM_SINGLE, LOGREG_FORM_STRIPS = 0, 1, 2
 
@@ -387,6 +415,18 @@ def logreg_solve_plan(n: int, d: int, form: int = LOGREG_FORM_AUTO, strips: int 
     does not admit raises."""
     buf = ctypes.create_string_buffer(256)
     _native.check(_native.load().bhg_logreg_solve_plan(int(n), int(d), int(form), int(strips), buf, 256), "bhg_logreg_solve_plan")
+    return buf.value.decode()
+
+
+SOFTREG_FORM_AUTO, SOFTREG_FORM_SINGLE, SOFTREG_FORM_STRIPS = 0, 1, 2
+
+
+def softreg_solve_plan(n: int, d: int, C: int, form: int = SOFTREG_FORM_AUTO, strips: int = 0) -> str:
+    """The form the native softmax-regression solvers take for n rows, d features and C classes, as the library words it:
+    "single: ...", "strips G=...: ..." or "none" (bhg_softreg_solve_plan — host logic only: works on a box without a GPU).  A forced
+    form the shape does not admit raises."""
+    buf = ctypes.create_string_buffer(256)
+    _native.check(_native.load().bhg_softreg_solve_plan(int(n), int(d), int(C), int(form), int(strips), buf, 256), "bhg_softreg_solve_plan")
     return buf.value.decode()
 
 

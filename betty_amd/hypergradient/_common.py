@@ -197,6 +197,9 @@ FD_HVP_DEFAULT_RADIUS = 0.01
 # cg / neumann calls on a declared LogisticRegressionL2 that offered the provider's own solver: `fused` ran the whole K loop in native
 # launches (csrc/bhg_logreg_solve.hip), `loop` took K x (product + recurrence kernel) — K = 0, impl = "torch", d > 4096, ...
 LOGREG_SOLVE_STATS = {"fused": 0, "loop": 0}
+# the same for a declared SoftmaxRegressionL2 (csrc/bhg_softreg_solve.hip): `loop` — K = 0, impl = "torch", a shape outside the family
+# (C > 16, d > 4096, C d > 32768), unaligned / non-contiguous / non-fp32 tensors, hypergradient_hvp = "finite_difference"
+SOFTREG_SOLVE_STATS = {"fused": 0, "loop": 0}
 
 
 def finite_difference_wanted(curr) -> bool:

@@ -43,7 +43,7 @@ import warnings
 import torch
 import torch.nn.functional as F
 
-from ._common import LOGREG_SOLVE_STATS, _uses_ddp, finite_difference_wanted, is_fsdp, precision_of
+from ._common import LOGREG_SOLVE_STATS, SOFTREG_SOLVE_STATS, _uses_ddp, finite_difference_wanted, is_fsdp, precision_of
 
 
 class StructureMismatchError(RuntimeError):
@@ -786,7 +786,76 @@ class _QuadraticFD:
                 o.add_(r) if accumulate else o.copy_(r)
 
 
-class LogisticRegressionL2(_QuadraticFD):
+class _PerWeightL2(_QuadraticFD):
+    """What LogisticRegressionL2 and SoftmaxRegressionL2 share: the upper parameters enter through ``1/2 sum lam * w^2`` with one
+    coefficient per weight, so the cotangent of the lam tensor is ``w * u`` for cg / neumann and ``-(w * v)`` for darts / sama, and
+    ``lam``'s own graph carries it to ``prev``'s parameters; and the front of the provider's own solver (``fused_cg`` /
+    ``fused_neumann``).  A subclass sets ``_SOLVE_STATS`` / ``_SOLVERS`` and has ``_fused_solve_ready(K, *state)`` and
+    ``_fused_solve(method, rhs, out, K, step)``; after ``prepare()`` it holds ``self.w`` (the flat weights) and ``self.lam``."""
+
+    _SOLVE_STATS: dict = {}
+    _SOLVERS = ("", "")   # the backend's cg / neumann solve methods
+
+    def _lam_tensor(self):
+        """lam with its graph to prev's parameters, one coefficient per weight."""
+        return self.lam_fn()
+
+    def fused_cg_ready(self, layout, K: int) -> bool:
+        return layout.T == 1 and self._fused_solve_ready(K)
+
+    def fused_cg(self, layout, x, r, p, K: int, cg_alpha: float, rhs=None):
+        """x <- -cg_alpha * x_K and True, or False (nothing touched: the caller runs its loop).  r holds the right-hand side (cg_init)."""
+        if not (layout.T == 1 and self._fused_solve_ready(K, x, r)):
+            self._SOLVE_STATS["loop"] += 1
+            return False
+        return self._fused_solve(self._SOLVERS[0], r, x, K, cg_alpha)
+
+    def fused_neumann_ready(self, layout, K: int) -> bool:
+        return layout.T == 1 and self._fused_solve_ready(K)
+
+    def fused_neumann(self, layout, v, p, K: int, alpha: float):
+        """p <- -alpha * p_K and True, or False.  v holds the right-hand side (neumann_init)."""
+        if not (layout.T == 1 and self._fused_solve_ready(K, v, p)):
+            self._SOLVE_STATS["loop"] += 1
+            return False
+        return self._fused_solve(self._SOLVERS[1], v, p, K, alpha)
+
+    def mixed_vjp(self, neg_x_views, sync: bool):
+        coeff, self._coeff = getattr(self, "_coeff", None), None
+        if coeff is None:   # (else a native solve has just left w * (-alpha x) beside its solution)
+            coeff = self.w.reshape(-1) * neg_x_views[0].reshape(-1)  # d(g.(-x))/d lam
+        coeff = coeff.reshape(self.lam.shape)
+        upper = self.prev.trainable_parameters()
+        if sync:
+            torch.autograd.backward(self.lam, grad_tensors=coeff, inputs=upper)
+            return None
+        return list(torch.autograd.grad(self.lam, upper, grad_outputs=coeff))
+
+    def finite_difference(self, layout, vector, eps32, eps64, sync: bool, restore: bool = True):
+        """darts.py:37-67 / sama.py:29-59 in closed form: the kernel leaves the perturbed-and-restored weights and the cotangent
+        -(w * v) of the lam tensor (one element per weight), ``lam``'s own graph carries it to ``prev``'s parameters as in
+        ``mixed_vjp``.  None of ``prepare()``'s state is needed.  NotImplemented (nothing touched) when the closed form does not cover
+        the call."""
+        vector = list(vector)
+        if self._quad_fd_blocker(layout, vector) is not None:
+            return NotImplemented
+        upper = list(self.prev.trainable_parameters())
+        lam = self._lam_tensor()   # keeps the graph to prev's parameters
+        if not torch.is_tensor(lam) or lam.dtype != torch.float32 or lam.numel() != self.weight.numel() or lam.device != self.weight.device:
+            return NotImplemented
+        leaves = _graph_leaves(lam)
+        if not upper or any(id(p) not in leaves for p in upper):
+            return NotImplemented   # an upper parameter lam does not depend on: the opaque path knows what the reference does with it
+        coeff = torch.empty_like(self.weight.data)
+        self._quad_fd_launch(layout, vector, [coeff], eps32, 0.0, 1, bool(restore), False)
+        coeff = coeff.reshape(lam.shape)
+        if sync:
+            torch.autograd.backward(lam, grad_tensors=coeff, inputs=upper)
+            return None
+        return list(torch.autograd.grad(lam, upper, grad_outputs=coeff))
+
+
+class LogisticRegressionL2(_PerWeightL2):
     """Logistic regression with a per-weight L2 penalty (the inner problem
     of examples/logistic_regression_hpo/logistic_regression_implicit.py:80-91 and
     test/test_regression.py:47-59):
@@ -854,6 +923,7 @@ class LogisticRegressionL2(_QuadraticFD):
 
     # ---- the provider's own solver: all K iterations in native launches (csrc/bhg_logreg_solve.hip) ----
     _PLANS = {}   # (n, d) -> the library's plan line
+    _SOLVE_STATS, _SOLVERS = LOGREG_SOLVE_STATS, ("logreg_cg_solve", "logreg_neumann_solve")
 
     def _fused_solve_ready(self, K: int, *state) -> bool:
         from ..backend import get_backend, logreg_solve_plan  # noqa: PLC0415
@@ -884,58 +954,167 @@ class LogisticRegressionL2(_QuadraticFD):
         LOGREG_SOLVE_STATS["fused"] += 1
         return True
 
-    def fused_cg_ready(self, layout, K: int) -> bool:
-        return layout.T == 1 and self._fused_solve_ready(K)
 
-    def fused_cg(self, layout, x, r, p, K: int, cg_alpha: float, rhs=None):
-        """x <- -cg_alpha * x_K and True, or False (nothing touched: the caller runs its loop).  r holds the right-hand side (cg_init)."""
-        if not (layout.T == 1 and self._fused_solve_ready(K, x, r)):
-            LOGREG_SOLVE_STATS["loop"] += 1
+class SoftmaxRegressionL2(_PerWeightL2):
+    """Softmax (multi-class logistic) regression with a per-weight L2 penalty — the reference's logistic-regression HPO example on
+    multi-class data: the inner model is ``nn.Linear(d, C, bias=False)`` under cross-entropy,
+
+        L_in(W, lam) = mean_i CE(x_i W^T, y_i) + 1/2 sum lam * W^2          W, lam: [C, d]
+
+    With P = softmax(X W^T) the labels drop out of the Hessian:
+
+        H V = U^T X + lam * V,   Z = X V^T,   U = (P * Z - P * rowsum(P * Z)) / n
+
+    and the mixed derivative of g.u w.r.t. the lam TENSOR is W * u, pushed into ``prev``'s parameters through ``lam``'s own graph.
+    ``curr.parameters()`` must be ``[weight]`` with a 2-D ``weight``; a bias is not part of this closed form (append a column of ones
+    to X instead).  ``lam_fn()`` returns lam — any tensor that broadcasts to ``weight.shape`` — as a function of ``prev``'s parameters.
+    ``batch`` is ``(X, y)``; ``y`` only serves the first-use check.
+
+    ``prepare()`` / ``hvp``: the closed form in ATen ops (three GEMMs: the logits once per step, Z and U^T X per product).
+    ``impl="torch"`` runs it on any device and must be requested explicitly (tests of the host logic); the default ``impl`` requires
+    CUDA tensors (no CPU fallback).  On the GPU it is the un-fused product of the generic loop, which runs whenever the provider's own
+    solver does not apply.
+
+    cg / neumann: ``fused_cg`` / ``fused_neumann`` run the whole K loop in native launches (csrc/bhg_softreg_solve.hip: the two thin
+    products on the fp32 matrix cores) and leave the cotangent W * (-alpha x) for ``mixed_vjp``.  Taken when K > 0, ``impl`` is hip,
+    the library has a form for the shape (2 <= C <= 16, d <= 4096, C d <= 32768), the tensors are contiguous 16-byte aligned fp32 and
+    the product is the analytic one; everything else keeps K x (``hvp`` + recurrence kernel).  SOFTREG_SOLVE_STATS
+    (hypergradient/_common.py) counts both.
+
+    darts / sama: -(W * v) exactly, the sibling's ``finite_difference`` on the flat weight (see _QuadraticFD for ``closed_form_fd``).
+
+    First use (as WeightedCEMLP): the first ``prepare()`` per (shape, n) compares the closed-form gradient, one H v and one mixed
+    derivative with a double backward through the problem's real ``training_step_exec`` on a seeded random direction and raises
+    StructureMismatchError beyond VERIFY_RTOL — label smoothing shows in the gradient, another reduction or penalty in all three;
+    ``verify=False`` or VERIFY_STRUCTURE = False skips it.
+    """
+
+    def __init__(self, curr, prev, weight: torch.nn.Parameter, lam_fn: Callable, batch=None, impl: Optional[str] = None,
+                 closed_form_fd: Optional[bool] = None, verify: bool = True):
+        self.curr, self.prev, self.weight, self.lam_fn, self.batch = curr, prev, weight, lam_fn, batch
+        self.impl, self.closed_form_fd, self.verify = impl, closed_form_fd, bool(verify)
+        params = list(curr.parameters())
+        if weight.dim() != 2:
+            raise ValueError("SoftmaxRegressionL2: weight must be the 2-D [classes, features] matrix of the linear classifier")
+        if len(params) == 2 and params[0] is weight and params[1].dim() == 1 and params[1].shape[0] == weight.shape[0]:
+            raise ValueError("SoftmaxRegressionL2: the model has a bias, which this closed form does not cover — use "
+                             "nn.Linear(d, C, bias=False) and append a column of ones to X")
+        if len(params) != 1 or params[0] is not weight:
+            raise ValueError("SoftmaxRegressionL2: curr.parameters() must be [weight] (no bias: append a column of ones to X)")
+
+    def _lam_tensor(self):
+        lam = self.lam_fn()
+        return torch.broadcast_to(lam, self.weight.shape) if torch.is_tensor(lam) and lam.shape != self.weight.shape else lam
+
+    def prepare(self):
+        from .. import _native  # noqa: PLC0415
+
+        x, y = self.batch if self.batch is not None else self.curr.cur_batch
+        impl = self.impl or "hip"
+        if impl not in ("hip", "torch"):
+            raise ValueError(f"unknown impl {impl!r}")
+        if impl == "hip" and not x.is_cuda:
+            raise _native.NativeLibraryError("SoftmaxRegressionL2 needs CUDA/HIP tensors; there is no CPU fallback")
+        dt = torch.float32 if impl == "hip" else self.weight.dtype
+        # the native solve reads the user's X in place: a copy made here (another dtype, a strided view) keeps the loop
+        self._x_in_place = x.dtype == torch.float32 and x.is_contiguous()
+        self.X = x.detach().reshape(x.shape[0], -1).to(dt).contiguous()
+        self.n, self.d = self.X.shape
+        self.C = int(self.weight.shape[0])
+        if self.weight.shape[1] != self.d:
+            raise ValueError(f"SoftmaxRegressionL2: weight is {tuple(self.weight.shape)} but X has {self.d} features")
+        self.lam = self._lam_tensor()   # keeps the graph to prev's parameters
+        self.lam_d = self.lam.detach().to(dt).contiguous()
+        self.w = self.weight.detach().to(dt).contiguous()
+        self.P = torch.softmax(self.X @ self.w.t(), dim=1)   # (the row maximum is subtracted inside)
+        self._coeff = None
+        if self.verify and VERIFY_STRUCTURE:
+            self._verify_against_autograd(y)
+        return self.hvp
+
+    def hvp(self, direction_views):
+        (v,) = direction_views
+        V = v.detach().to(self.X.dtype).reshape(self.C, self.d)
+        PZ = self.P * (self.X @ V.t())
+        U = (PZ - self.P * PZ.sum(dim=1, keepdim=True)) / self.n
+        return [(U.t() @ self.X + self.lam_d * V).view(self.weight.shape)]
+
+    def _verify_against_autograd(self, y):
+        """See VERIFY_STRUCTURE.  The verdict is cached on the problem object, keyed by the shape and the batch size."""
+        key = (tuple(self.weight.shape), int(self.n), "SoftmaxRegressionL2")
+        done = self.curr.__dict__.setdefault("_bhg_structure_verified", set()) if hasattr(self.curr, "__dict__") else set()
+        if key in done:
+            return
+        weight, upper = self.weight, list(self.prev.trainable_parameters())
+        gen = torch.Generator(device="cpu").manual_seed(20240926)
+        v = torch.randn(weight.shape, generator=gen).to(device=weight.device, dtype=weight.dtype)
+        # the extra training_step of the check must not be seen by the run: the RNG streams are forked around it
+        devs = [weight.device] if weight.is_cuda else []
+        with torch.random.fork_rng(devices=devs), torch.enable_grad():
+            loss = self.curr.training_step_exec(self.batch if self.batch is not None else self.curr.cur_batch)
+            (g_auto,) = torch.autograd.grad(loss, [weight], create_graph=True)
+            second = torch.autograd.grad((g_auto * v).sum(), [weight] + upper, allow_unused=True)
+        hv_auto, mixed_auto = second[0], second[1:]
+        onehot = F.one_hot(y.reshape(-1).long(), self.C).to(self.P.dtype)
+        g_data, g_pen = (self.P - onehot).t() @ self.X / self.n, self.lam_d * self.w
+        (hv,) = self.hvp([v])
+        mixed = torch.autograd.grad(self.lam, upper, grad_outputs=(self.w * v.to(self.w.dtype)).to(self.lam.dtype), retain_graph=True,
+                                    allow_unused=True)
+
+        def rel(got, want):
+            num = sum(float((((a.double() if a is not None else 0.0) - (b.double() if b is not None else 0.0)) ** 2).sum())
+                      for a, b in zip(got, want) if not (a is None and b is None)) ** 0.5
+            den = sum(float((b.double() ** 2).sum()) for b in want if b is not None) ** 0.5
+            return num / den if den > 0 else num
+
+        # the gradient's two terms cancel at the inner optimum: its error is measured against THEIR size, not the (vanishing) sum's
+        e_g = float((g_data + g_pen - g_auto.detach()).double().norm() / (g_data.double().norm() + g_pen.double().norm()).clamp_min(1e-300))
+        e_hvp, e_mix = rel([hv], [hv_auto]), rel(list(mixed), list(mixed_auto))
+        tol = VERIFY_RTOL
+        if precision_of(self.curr) in ("fp16", "bf16"):   # the autograd side ran under autocast: its own error
+            tol = max(tol, 5e-2)
+        if not (e_g <= tol and e_hvp <= tol and e_mix <= tol):
+            raise StructureMismatchError(
+                f"hypergradient_structure of problem {getattr(self.curr, 'name', '?')!r} declares {type(self).__name__}, but its "
+                f"training_step disagrees with that closed form: gradient off by {e_g:.2e}, Hessian-vector product on a random direction "
+                f"by {e_hvp:.2e}, mixed second derivative by {e_mix:.2e} (tolerance {tol:g}).  Typical causes: label smoothing, a "
+                f"reduction other than the batch mean, a penalty that is not `1/2 sum(lam * W^2)`, a bias or another layer in the model.")
+        done.add(key)
+
+    # ---- the provider's own solver: all K iterations in native launches (csrc/bhg_softreg_solve.hip) ----
+    _PLANS = {}   # (n, d, C) -> the library's plan line
+    _SOLVE_STATS, _SOLVERS = SOFTREG_SOLVE_STATS, ("softreg_cg_solve", "softreg_neumann_solve")
+
+    def _fused_solve_ready(self, K: int, *state) -> bool:
+        from ..backend import get_backend, softreg_solve_plan  # noqa: PLC0415
+
+        if not (K > 0 and (self.impl or "hip") == "hip") or finite_difference_wanted(self.curr):
             return False
-        return self._fused_solve("logreg_cg_solve", r, x, K, cg_alpha)
-
-    def fused_neumann_ready(self, layout, K: int) -> bool:
-        return layout.T == 1 and self._fused_solve_ready(K)
-
-    def fused_neumann(self, layout, v, p, K: int, alpha: float):
-        """p <- -alpha * p_K and True, or False.  v holds the right-hand side (neumann_init)."""
-        if not (layout.T == 1 and self._fused_solve_ready(K, v, p)):
-            LOGREG_SOLVE_STATS["loop"] += 1
+        if getattr(self, "X", None) is None or not self._x_in_place or not hasattr(get_backend(), "softreg_cg_solve"):
             return False
-        return self._fused_solve("logreg_neumann_solve", v, p, K, alpha)
+        N = self.C * self.d
+        if self.lam_d.shape != self.w.shape or self.w.numel() != N or any(t.numel() < N for t in state):
+            return False
+        for t in (self.X, self.w, self.lam_d) + state:
+            if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.data_ptr() % 16 == 0):
+                return False
+        key = (self.n, self.d, self.C)
+        plan = self._PLANS.get(key)
+        if plan is None:
+            plan = self._PLANS[key] = softreg_solve_plan(*key)
+        return not plan.startswith("none")
 
-    def mixed_vjp(self, neg_x_views, sync: bool):
-        coeff, self._coeff = getattr(self, "_coeff", None), None
-        if coeff is None:   # (else a native solve has just left w * (-alpha x) beside its solution)
-            coeff = self.w * neg_x_views[0].reshape(-1)  # d(g.(-x))/d lam
-        coeff = coeff.reshape(self.lam.shape)
-        upper = self.prev.trainable_parameters()
-        if sync:
-            torch.autograd.backward(self.lam, grad_tensors=coeff, inputs=upper)
-            return None
-        return list(torch.autograd.grad(self.lam, upper, grad_outputs=coeff))
+    def _fused_solve(self, method: str, rhs, out, K: int, step: float) -> bool:
+        from ..backend import get_backend  # noqa: PLC0415
 
-    def finite_difference(self, layout, vector, eps32, eps64, sync: bool, restore: bool = True):
-        """darts.py:37-67 / sama.py:29-59 in closed form: the kernel leaves the perturbed-and-restored weights and the ``d``-sized
-        cotangent -(w * v) of the lam tensor, ``lam``'s own graph carries it to ``prev``'s parameters as in ``mixed_vjp``.  None of
-        ``prepare()``'s state is needed.  NotImplemented (nothing touched) when the closed form does not cover the call."""
-        vector = list(vector)
-        if self._quad_fd_blocker(layout, vector) is not None:
-            return NotImplemented
-        upper = list(self.prev.trainable_parameters())
-        lam = self.lam_fn()   # keeps the graph to prev's parameters
-        if not torch.is_tensor(lam) or lam.dtype != torch.float32 or lam.numel() != self.weight.numel() or lam.device != self.weight.device:
-            return NotImplemented
-        leaves = _graph_leaves(lam)
-        if not upper or any(id(p) not in leaves for p in upper):
-            return NotImplemented   # an upper parameter lam does not depend on: the opaque path knows what the reference does with it
-        coeff = torch.empty_like(self.weight.data)
-        self._quad_fd_launch(layout, vector, [coeff], eps32, 0.0, 1, bool(restore), False)
-        coeff = coeff.reshape(lam.shape)
-        if sync:
-            torch.autograd.backward(lam, grad_tensors=coeff, inputs=upper)
-            return None
-        return list(torch.autograd.grad(lam, upper, grad_outputs=coeff))
+        be = get_backend()
+        ws = be.softreg_solve_workspace(self.n, self.d, self.C, self.X.device)
+        coeff = torch.empty(self.C * self.d, device=self.X.device)
+        # out = -step * (x_K | p_K): what the generic loop leaves in the flat solution for mixed_vjp (InnerOperator.out_sign = -1 here)
+        getattr(be, method)(self.X, self.w, self.lam_d, rhs, out, coeff, ws, K, step, -step)
+        self._coeff = coeff
+        SOFTREG_SOLVE_STATS["fused"] += 1
+        return True
 
 
 class ProximalRegularized(_QuadraticFD):

@@ -257,6 +257,23 @@ int bhg_logreg_cg_solve(const float* X, const float* w, const float* lam, const 
 int bhg_logreg_neumann_solve(const float* X, const float* w, const float* lam, const float* rhs, float* out, float* coeff, void* ws,
                              int n, int d, int K, float alpha, float out_scale, int form, int strips, void* stream);
 
+/* Softmax regression with per-weight L2, the multi-class sibling (csrc/bhg_softreg_solve.hip): W, lam [C, d] row-major (the flat
+ * vector is W row-major), X [n, d], P = softmax(X W^T) with the row maximum subtracted,
+ *   H V = U^T X + lam .* V,  Z = X V^T,  U = (P .* Z - P .* rowsum(P .* Z)) / n.
+ * The two thin products of the pass over X run on the fp32 matrix cores, classes padded to 16 inside a tile.  Supported family:
+ * 2 <= C <= 16, d <= 4096, C * d <= 32768; anything else plans "none" (ws_bytes 0, a solve call fails with "no native form").
+ * Forms: `single` (C * d <= 4096 and n * d <= 2^18: one launch of one workgroup runs all K iterations) and `strips` (the whole
+ * family: 3 launches per CG iteration, 2 per Neumann iteration; auto mode caps G so that the [G][C d] partials stay <= 16 MiB).
+ * form, strips, out_scale, coeff (= W .* out), the iterations and the contract (read-only inputs, no host synchronisation, no float
+ * atomics, bitwise run-to-run deterministic, nothing read from `ws` that the solve has not written) are those of the logreg solver.
+ * rhs / out / coeff: C * d floats.  ws: bhg_softreg_solve_ws_bytes(n, d, C) bytes of device memory, 16-byte aligned.               */
+int bhg_softreg_solve_plan(int n, int d, int C, int form, int strips, char* buf, size_t buf_bytes);
+size_t bhg_softreg_solve_ws_bytes(int n, int d, int C);
+int bhg_softreg_cg_solve(const float* X, const float* W, const float* lam, const float* rhs, float* out, float* coeff, void* ws,
+                         int n, int d, int C, int K, float cg_alpha, float out_scale, int form, int strips, void* stream);
+int bhg_softreg_neumann_solve(const float* X, const float* W, const float* lam, const float* rhs, float* out, float* coeff, void* ws,
+                              int n, int d, int C, int K, float alpha, float out_scale, int form, int strips, void* stream);
+
 /* ReLU-MLP with per-sample-weighted cross-entropy (+ ridge) — SURVEY Appendix A.3; the inner
  * problem of examples/learning_to_reweight/main.py:117-127 (BASELINE cfg 2 / the metric's 10 M
  * parameter problem).  The caller computes the direction-independent quantities once per
