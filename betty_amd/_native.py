@@ -151,6 +151,17 @@ SYMBOLS = {
         [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_float, c_int, c_int,
          c_void_p],
     ),
+    "bhg_wsoftreg_cg_solve": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_float, c_int, c_int,
+         c_void_p],
+    ),
+    "bhg_wsoftreg_neumann_solve": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_float, c_int, c_int,
+         c_void_p],
+    ),
+    "bhg_wsoftreg_mixed": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "bhg_mlp_partial_floats": (c_size_t, [POINTER(Mlp)]),
     "bhg_mlp_hvp": (c_int, [POINTER(Mlp), _PP, _PP, c_void_p]),
     "bhg_mlp_hvp_mode": (c_int, [POINTER(Mlp), _PP, _PP, c_int, c_void_p]),

@@ -405,6 +405,41 @@ class HipBackend:
             "bhg_softreg_neumann_solve",
         )
 
+    # -- sample-weighted softmax regression (same file): a [n] scales the rows, reg [C, d] is a constant; plan and workspace are the
+    #    softreg ones (softreg_solve_plan / softreg_solve_workspace) ----------------------------------------------------------
+    def wsoftreg_cg_solve(self, X, W, reg, a, rhs, out, ws, K: int, cg_alpha: float, out_scale: float, form: int = 0,
+                          strips: int = 0) -> None:
+        """out <- out_scale * x_K of K CG iterations on H V = U^T X + reg * V with U's row i scaled by a[i] (softreg_cg_solve's
+        iteration and arguments otherwise; no coeff: see wsoftreg_mixed)."""
+        n, d = X.shape
+        _native.check(
+            self.lib.bhg_wsoftreg_cg_solve(X.data_ptr(), W.data_ptr(), reg.data_ptr(), a.data_ptr(), rhs.data_ptr(), out.data_ptr(),
+                                           ws.data_ptr(), n, d, int(W.shape[0]), int(K), float(cg_alpha), float(out_scale), int(form),
+                                           int(strips), _stream_ptr()),
+            "bhg_wsoftreg_cg_solve",
+        )
+
+    def wsoftreg_neumann_solve(self, X, W, reg, a, rhs, out, ws, K: int, alpha: float, out_scale: float, form: int = 0,
+                               strips: int = 0) -> None:
+        """out <- out_scale * p_K of K Neumann iterations on the same H."""
+        n, d = X.shape
+        _native.check(
+            self.lib.bhg_wsoftreg_neumann_solve(X.data_ptr(), W.data_ptr(), reg.data_ptr(), a.data_ptr(), rhs.data_ptr(), out.data_ptr(),
+                                                ws.data_ptr(), n, d, int(W.shape[0]), int(K), float(alpha), float(out_scale), int(form),
+                                                int(strips), _stream_ptr()),
+            "bhg_wsoftreg_neumann_solve",
+        )
+
+    def wsoftreg_mixed(self, X, W, direction, y, c) -> None:
+        """c[i] <- sum_k (P_ik - [k == y_i]) (X direction^T)_ik / n, the cotangent of the sample weights along ``direction`` (C * d
+        floats in W's order).  y: int64 labels; c: n floats.  One launch, no workspace."""
+        n, d = X.shape
+        _native.check(
+            self.lib.bhg_wsoftreg_mixed(X.data_ptr(), W.data_ptr(), direction.data_ptr(), y.data_ptr(), c.data_ptr(), n, d,
+                                        int(W.shape[0]), _stream_ptr()),
+            "bhg_wsoftreg_mixed",
+        )
+
 
 LOGREG_FORM_AUTO, LOGREG_FORM_SINGLE, LOGREG_FORM_STRIPS = 0, 1, 2
 

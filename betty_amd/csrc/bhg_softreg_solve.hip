@@ -24,6 +24,11 @@
 // bitwise run-to-run deterministic; no float atomics, no workgroup waits on another inside a launch, every loop is bounded by its
 // arguments, and nothing is read from the workspace that the same solve has not written.
 //
+// The sample-weighted sibling (bhg_wsoftreg_*: one weight a_i per row of X, a constant penalty `reg` in lam's place) runs the same
+// solver: its pass scales a row of U by a_i before the division by n (pass_rows<.., kPassWeighted>, kernels of their own: the
+// unweighted kernels' device code does not know about the weight), everything after the pass is shared.  k_wsoftreg_mixed is the
+// one pass over X of its mixed second derivative: phase 1 and the softmax of phase 2, a per-row epilogue, no phase 3.
+//
 // Arithmetic of the recurrences: oracle/recurrence.c / tests/recurrence_ref.py (products rounded to fp32 before add / sub, fp64 dots,
 // fp32 quotients, den = dot(fl(cg_alpha Hp), p) but r -= alpha Hp with the un-scaled Hp, no breakdown guard, out_scale folded
 // into the last iteration).
@@ -102,15 +107,28 @@ __device__ __forceinline__ float row16_max(float v) {
 
 // acc += U^T X over the rows [row0, row1) for the columns this wave owns.  Every thread of the kT-thread workgroup calls it with the
 // same arguments.  W, dir: [C, d] (global or LDS).  sU: kSuper * 16 floats of LDS.  nf = (float)n of the WHOLE problem.
+// MODE (rw is read in the modes that name it only):
+//   kPassPlain     the product above;
+//   kPassWeighted  row i of U is scaled by rw.a[i] (the weight of the sample, indexed like the rows of X) before the division by n;
+//                  loaded in phase 2, once per row;
+//   kPassMixed     phases 1 and 2 only, for ONE super-tile [row0, row1): instead of U, lane q = 0 of row i stores
+//                  rw.c[i] = sum_c (P_ic - [c == rw.y[i]]) Z_ic / n; sU and acc are not touched.
 // Operand maps of the 16x16x4 MFMA: lane l gives A[i = l & 15][k = l >> 4] and B[k = l >> 4][j = l & 15], and holds
 // D[i = 4 (l >> 4) + reg][j = l & 15].  A k-step may take its four k's in any order as long as A and B agree, so a lane feeds the
 // four components of ONE 16-byte load to four consecutive MFMAs.
 //   phase 1: A = X[row q][k], B = V[class q][k] | W[class q][k]  -> lane holds Z | logits [row 4 g + reg][class q]
 //   phase 3: A = U[row 4 t + g][class q] (LDS), B = X[row 4 t + g][col 4 q + e] into accumulator e
 //            -> acc[slot][e][reg] = (U^T X)[class 4 g + reg][col 64 chunk + 4 q + e]
-template <bool VEC, int SLOTS>
-__device__ __forceinline__ void pass_rows(const float* __restrict__ X, const float* W, const float* dir, float* sU, const int d,
-                                          const int C, const int row0, const int row1, const float nf, f32x4 (&acc)[SLOTS][4]) {
+enum { kPassPlain = 0, kPassWeighted = 1, kPassMixed = 2 };
+struct RowArgs {
+  const float* a;        // kPassWeighted: n sample weights
+  const long long* y;    // kPassMixed: n labels
+  float* c;              // kPassMixed: n cotangents
+};
+template <bool VEC, int SLOTS, int MODE>
+__device__ __forceinline__ void pass_rows(const float* __restrict__ X, const float* W, const float* dir, const RowArgs rw, float* sU,
+                                          const int d, const int C, const int row0, const int row1, const float nf,
+                                          f32x4 (&acc)[SLOTS][4]) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4, q = lane & 15;
 #pragma unroll
   for (int s = 0; s < SLOTS; ++s)
@@ -163,11 +181,26 @@ __device__ __forceinline__ void pass_rows(const float* __restrict__ X, const flo
         const float m = row16_max(lg);
         const float e = cls ? expf(lg - m) : 0.f;
         const float p = e / row16_sum(e);
-        const float pz = p * az[r];
-        const float t = row16_sum(pz);
-        sU[(t0 + 4 * g + r) * 16 + q] = st + t0 + 4 * g + r < row1 ? (pz - p * t) / nf : 0.f;
+        if constexpr (MODE == kPassMixed) {
+          // the epilogue of the mixed second derivative: one lane per row stores c; a label outside [0, C) matches no class
+          const int row = st + t0 + 4 * g + r;
+          const long long yi = row < row1 ? rw.y[row] : -1;
+          const float t = row16_sum(cls ? (p - ((long long)q == yi ? 1.f : 0.f)) * az[r] : 0.f);
+          if (row < row1 && q == 0) rw.c[row] = t / nf;
+        } else {
+          const float pz = p * az[r];
+          const float t = row16_sum(pz);
+          if constexpr (MODE == kPassWeighted) {
+            const int row = st + t0 + 4 * g + r;
+            const float ai = row < row1 ? rw.a[row] : 0.f;
+            sU[(t0 + 4 * g + r) * 16 + q] = row < row1 ? ((pz - p * t) * ai) / nf : 0.f;
+          } else {
+            sU[(t0 + 4 * g + r) * 16 + q] = st + t0 + 4 * g + r < row1 ? (pz - p * t) / nf : 0.f;
+          }
+        }
       }
     }
+    if constexpr (MODE == kPassMixed) return;     // (one super-tile per workgroup, no phase 3)
     __syncthreads();
     const int rows4 = (live + 3) & ~3;          // (rows past `live` up to here belong to a live tile: their U is zero)
     const int rows8 = VEC ? live & ~7 : 0;      // phase 3: rows taken two unconditional 16-byte k-steps at a time
@@ -243,13 +276,13 @@ __device__ __forceinline__ double block_sum_w(double v, double* red) {
 // ---- single: the whole solve in one workgroup ---------------------------------------------------------------------------------
 // CG: x, r in registers, sdir = p.  Neumann: sdir = v (the direction), x = the accumulator p.  `a`: cg_alpha | alpha.  A thread owns
 // the flat elements {tid, tid + kT, ...}.
-template <bool VEC>
-__global__ __launch_bounds__(kT) void k_softreg_single(const float* __restrict__ X, const float* __restrict__ W,
-                                                       const float* __restrict__ lam, const float* __restrict__ rhs,
-                                                       float* __restrict__ out, float* __restrict__ coeff, const int n, const int d,
-                                                       const int C, const int K, const int cg, const float a, const float out_scale) {
-  __shared__ __align__(16) float sdir[kSingleMaxN], sh[kSingleMaxN], sU[kSuper * 16];
-  __shared__ double sred[kW];
+// The body of both single kernels.  sdir, sh: kSingleMaxN floats of LDS each, sU: kSuper * 16, sred: kW doubles.  ROWW: `aw` holds one
+// weight per row of X (pass_rows).
+template <bool VEC, bool ROWW>
+__device__ __forceinline__ void single_body(const float* __restrict__ X, const float* __restrict__ W, const float* __restrict__ lam,
+                                            const float* __restrict__ aw, const float* __restrict__ rhs, float* __restrict__ out,
+                                            float* __restrict__ coeff, const int n, const int d, const int C, const int K, const int cg,
+                                            const float a, const float out_scale, float* sdir, float* sh, float* sU, double* sred) {
   const int tid = threadIdx.x, N = C * d;
   float wv[kSinglePer], lv[kSinglePer], xv[kSinglePer], rv[kSinglePer];
 #pragma unroll
@@ -273,7 +306,7 @@ __global__ __launch_bounds__(kT) void k_softreg_single(const float* __restrict__
   const float nf = (float)n;
   for (int k = 0; k < K; ++k) {
     f32x4 acc[kSingleSlots][4];
-    pass_rows<VEC, kSingleSlots>(X, W, sdir, sU, d, C, 0, n, nf, acc);
+    pass_rows<VEC, kSingleSlots, ROWW ? kPassWeighted : kPassPlain>(X, W, sdir, RowArgs{aw, nullptr, nullptr}, sU, d, C, 0, n, nf, acc);
     store_acc<VEC, kSingleSlots>(sh, d, C, acc);
     __syncthreads();
     // from here every thread touches its own elements only
@@ -341,6 +374,27 @@ __global__ __launch_bounds__(kT) void k_softreg_single(const float* __restrict__
   }
 }
 
+template <bool VEC>
+__global__ __launch_bounds__(kT) void k_softreg_single(const float* __restrict__ X, const float* __restrict__ W,
+                                                       const float* __restrict__ lam, const float* __restrict__ rhs,
+                                                       float* __restrict__ out, float* __restrict__ coeff, const int n, const int d,
+                                                       const int C, const int K, const int cg, const float a, const float out_scale) {
+  __shared__ __align__(16) float sdir[kSingleMaxN], sh[kSingleMaxN], sU[kSuper * 16];
+  __shared__ double sred[kW];
+  single_body<VEC, false>(X, W, lam, nullptr, rhs, out, coeff, n, d, C, K, cg, a, out_scale, sdir, sh, sU, sred);
+}
+
+// the sample-weighted problem: aw[n], `reg` in lam's place, no coeff (its cotangent is k_wsoftreg_mixed's)
+template <bool VEC>
+__global__ __launch_bounds__(kT) void k_wsoftreg_single(const float* __restrict__ X, const float* __restrict__ W,
+                                                        const float* __restrict__ reg, const float* __restrict__ aw,
+                                                        const float* __restrict__ rhs, float* __restrict__ out, const int n, const int d,
+                                                        const int C, const int K, const int cg, const float a, const float out_scale) {
+  __shared__ __align__(16) float sdir[kSingleMaxN], sh[kSingleMaxN], sU[kSuper * 16];
+  __shared__ double sred[kW];
+  single_body<VEC, true>(X, W, reg, aw, rhs, out, nullptr, n, d, C, K, cg, a, out_scale, sdir, sh, sU, sred);
+}
+
 // ---- strips ----------------------------------------------------------------------------------------------------------------------
 // Launch 1 of an iteration: workgroup b sums its rows [b rps, (b + 1) rps) into part[b][0..N); an empty strip writes zeros.
 template <bool VEC>
@@ -351,8 +405,35 @@ __global__ __launch_bounds__(kT) void k_softreg_strip_pass(const float* __restri
   const int64_t lo = (int64_t)blockIdx.x * rps, hi = lo + rps;
   const int row0 = (int)(lo < n ? lo : n), row1 = (int)(hi < n ? hi : n);
   f32x4 acc[kSlots][4];
-  pass_rows<VEC, kSlots>(X, W, dir, sU, d, C, row0, row1, (float)n, acc);
+  pass_rows<VEC, kSlots, kPassPlain>(X, W, dir, RowArgs{nullptr, nullptr, nullptr}, sU, d, C, row0, row1, (float)n, acc);
   store_acc<VEC, kSlots>(part + (int64_t)blockIdx.x * C * d, d, C, acc);
+}
+
+// ... of the sample-weighted problem: aw[n], indexed like the rows of X
+template <bool VEC>
+__global__ __launch_bounds__(kT) void k_wsoftreg_strip_pass(const float* __restrict__ X, const float* __restrict__ W,
+                                                            const float* __restrict__ dir, const float* __restrict__ aw,
+                                                            float* __restrict__ part, const int n, const int d, const int C,
+                                                            const int rps) {
+  __shared__ float sU[kSuper * 16];
+  const int64_t lo = (int64_t)blockIdx.x * rps, hi = lo + rps;
+  const int row0 = (int)(lo < n ? lo : n), row1 = (int)(hi < n ? hi : n);
+  f32x4 acc[kSlots][4];
+  pass_rows<VEC, kSlots, kPassWeighted>(X, W, dir, RowArgs{aw, nullptr, nullptr}, sU, d, C, row0, row1, (float)n, acc);
+  store_acc<VEC, kSlots>(part + (int64_t)blockIdx.x * C * d, d, C, acc);
+}
+
+// ---- the mixed second derivative of the sample-weighted problem -------------------------------------------------------------------
+// c_i = sum_c (P_ic - [c == y_i]) Z_ic / n with Z = X dir^T: the cotangent of the weight a_i along `dir`.  Workgroup b owns the 256 rows
+// of super-tile b, a wave a 16-row tile: phase 1 and the softmax of pass_rows (kPassMixed), then lane q = 0 of each row stores its c.
+// Nothing is combined across waves or workgroups; rows past n store nothing; a label outside [0, C) matches no class.
+template <bool VEC>
+__global__ __launch_bounds__(kT) void k_wsoftreg_mixed(const float* __restrict__ X, const float* __restrict__ W,
+                                                       const float* __restrict__ dir, const long long* __restrict__ y,
+                                                       float* __restrict__ c, const int n, const int d, const int C) {
+  const int st = blockIdx.x * kSuper;           // (the grid is ceil(n / kSuper) workgroups: st < n <= 2^30)
+  f32x4 acc[1][4];
+  pass_rows<VEC, 1, kPassMixed>(X, W, dir, RowArgs{nullptr, y, c}, nullptr, d, C, st, n - st < kSuper ? n : st + kSuper, (float)n, acc);
 }
 
 // sum over the strips, in strip order, of flat element j (eight loads in flight)
@@ -523,25 +604,34 @@ int make_plan(const char* fn, int n, int d, int C, int form, int strips, Plan* o
   return BHG_OK;
 }
 
-void launch_single(hipStream_t st, const float* X, const float* W, const float* lam, const float* rhs, float* out, float* coeff, int n,
-                   int d, int C, int K, int cg, float a, float out_scale, bool vec) {
-  if (vec)
+// aw: the row weights of the sample-weighted problem (then lam is its `reg` and coeff is not written), or NULL
+void launch_single(hipStream_t st, const float* X, const float* W, const float* lam, const float* aw, const float* rhs, float* out,
+                   float* coeff, int n, int d, int C, int K, int cg, float a, float out_scale, bool vec) {
+  if (aw && vec)
+    hipLaunchKernelGGL((k_wsoftreg_single<true>), dim3(1), dim3(kT), 0, st, X, W, lam, aw, rhs, out, n, d, C, K, cg, a, out_scale);
+  else if (aw)
+    hipLaunchKernelGGL((k_wsoftreg_single<false>), dim3(1), dim3(kT), 0, st, X, W, lam, aw, rhs, out, n, d, C, K, cg, a, out_scale);
+  else if (vec)
     hipLaunchKernelGGL((k_softreg_single<true>), dim3(1), dim3(kT), 0, st, X, W, lam, rhs, out, coeff, n, d, C, K, cg, a, out_scale);
   else
     hipLaunchKernelGGL((k_softreg_single<false>), dim3(1), dim3(kT), 0, st, X, W, lam, rhs, out, coeff, n, d, C, K, cg, a, out_scale);
 }
 
-void launch_pass(hipStream_t st, const Plan& pl, const float* X, const float* W, const float* dir, float* part, int n, int d, int C,
-                 bool vec) {
-  if (vec)
+void launch_pass(hipStream_t st, const Plan& pl, const float* X, const float* W, const float* dir, const float* aw, float* part, int n,
+                 int d, int C, bool vec) {
+  if (aw && vec)
+    hipLaunchKernelGGL((k_wsoftreg_strip_pass<true>), dim3(pl.G), dim3(kT), 0, st, X, W, dir, aw, part, n, d, C, pl.rps);
+  else if (aw)
+    hipLaunchKernelGGL((k_wsoftreg_strip_pass<false>), dim3(pl.G), dim3(kT), 0, st, X, W, dir, aw, part, n, d, C, pl.rps);
+  else if (vec)
     hipLaunchKernelGGL((k_softreg_strip_pass<true>), dim3(pl.G), dim3(kT), 0, st, X, W, dir, part, n, d, C, pl.rps);
   else
     hipLaunchKernelGGL((k_softreg_strip_pass<false>), dim3(pl.G), dim3(kT), 0, st, X, W, dir, part, n, d, C, pl.rps);
 }
 
 template <bool CG>
-int solve(const char* fn, const float* X, const float* W, const float* lam, const float* rhs, float* out, float* coeff, void* ws, int n,
-          int d, int C, int K, float a, float out_scale, int form, int strips, void* stream) {
+int solve(const char* fn, const float* X, const float* W, const float* lam, const float* aw, const float* rhs, float* out, float* coeff,
+          void* ws, int n, int d, int C, int K, float a, float out_scale, int form, int strips, void* stream) {
   if (!(X && W && lam && rhs && out && ws)) { set_error("%s: NULL pointer", fn); return BHG_ERR_ARG; }
   if (K < 0) { set_error("%s: negative iteration count", fn); return BHG_ERR_ARG; }
   Plan pl;
@@ -563,7 +653,7 @@ int solve(const char* fn, const float* X, const float* W, const float* lam, cons
   // else row starts (of X, W or the direction) are unaligned: the scalar path
   const bool vec = d % 4 == 0 && (((uintptr_t)X | (uintptr_t)W | (uintptr_t)rhs) & 15) == 0;
   if (pl.form == kFormSingle) {
-    launch_single(st, X, W, lam, rhs, out, coeff, n, d, C, K, CG ? 1 : 0, a, out_scale, vec);
+    launch_single(st, X, W, lam, aw, rhs, out, coeff, n, d, C, K, CG ? 1 : 0, a, out_scale, vec);
     BHG_HIP_CHECK(hipGetLastError());
     return BHG_OK;
   }
@@ -578,13 +668,13 @@ int solve(const char* fn, const float* X, const float* W, const float* lam, cons
   for (int k = 0; k < K; ++k) {
     const int last = k == K - 1;
     if (CG) {
-      launch_pass(st, pl, X, W, k == 0 ? rhs : sp, part, n, d, C, vec);
+      launch_pass(st, pl, X, W, k == 0 ? rhs : sp, aw, part, n, d, C, vec);
       hipLaunchKernelGGL(k_softreg_strip_hp, dim3(cb), dim3(kColBlock), 0, st, (const float*)part, pl.G, lam, k == 0 ? rhs : (const float*)sp,
                          Hp, den, N, a);
       hipLaunchKernelGGL(k_softreg_strip_cg_update, dim3(1), dim3(kT), 0, st, rhs, W, (const float*)Hp, (const double*)den, cb, rr, sx, sr,
                          sp, out, coeff, N, k, last, out_scale);
     } else {
-      launch_pass(st, pl, X, W, k == 0 ? rhs : sr, part, n, d, C, vec);
+      launch_pass(st, pl, X, W, k == 0 ? rhs : sr, aw, part, n, d, C, vec);
       hipLaunchKernelGGL(k_softreg_strip_neumann_update, dim3(cb), dim3(kColBlock), 0, st, (const float*)part, pl.G, lam, W,
                          k == 0 ? rhs : (const float*)sr, k == 0 ? rhs : (const float*)sp, sr, sp, out, coeff, N, a, last, out_scale);
     }
@@ -621,12 +711,45 @@ size_t bhg_softreg_solve_ws_bytes(int n, int d, int C) {
 
 int bhg_softreg_cg_solve(const float* X, const float* W, const float* lam, const float* rhs, float* out, float* coeff, void* ws, int n,
                          int d, int C, int K, float cg_alpha, float out_scale, int form, int strips, void* stream) {
-  return solve<true>(__func__, X, W, lam, rhs, out, coeff, ws, n, d, C, K, cg_alpha, out_scale, form, strips, stream);
+  return solve<true>(__func__, X, W, lam, nullptr, rhs, out, coeff, ws, n, d, C, K, cg_alpha, out_scale, form, strips, stream);
 }
 
 int bhg_softreg_neumann_solve(const float* X, const float* W, const float* lam, const float* rhs, float* out, float* coeff, void* ws, int n,
                               int d, int C, int K, float alpha, float out_scale, int form, int strips, void* stream) {
-  return solve<false>(__func__, X, W, lam, rhs, out, coeff, ws, n, d, C, K, alpha, out_scale, form, strips, stream);
+  return solve<false>(__func__, X, W, lam, nullptr, rhs, out, coeff, ws, n, d, C, K, alpha, out_scale, form, strips, stream);
+}
+
+// The sample-weighted problem: plan, family and workspace are bhg_softreg_solve_plan's / bhg_softreg_solve_ws_bytes'.
+int bhg_wsoftreg_cg_solve(const float* X, const float* W, const float* reg, const float* a, const float* rhs, float* out, void* ws, int n,
+                          int d, int C, int K, float cg_alpha, float out_scale, int form, int strips, void* stream) {
+  BHG_REQUIRE(a, "NULL pointer");
+  return solve<true>(__func__, X, W, reg, a, rhs, out, nullptr, ws, n, d, C, K, cg_alpha, out_scale, form, strips, stream);
+}
+
+int bhg_wsoftreg_neumann_solve(const float* X, const float* W, const float* reg, const float* a, const float* rhs, float* out, void* ws,
+                               int n, int d, int C, int K, float alpha, float out_scale, int form, int strips, void* stream) {
+  BHG_REQUIRE(a, "NULL pointer");
+  return solve<false>(__func__, X, W, reg, a, rhs, out, nullptr, ws, n, d, C, K, alpha, out_scale, form, strips, stream);
+}
+
+int bhg_wsoftreg_mixed(const float* X, const float* W, const float* dir, const int64_t* y, float* c, int n, int d, int C, void* stream) {
+  BHG_REQUIRE(X && W && dir && y && c, "NULL pointer");
+  BHG_REQUIRE(n > 0 && d > 0 && C > 0, "empty problem");
+  BHG_REQUIRE(n <= (1 << 30), "more than 2^30 rows");
+  if (!family_admits(d, C)) {
+    set_error("%s: no native form takes C = %d, d = %d (2 <= C <= %d, d <= %d, C * d <= %d)", __func__, C, d, kMaxC, kMaxD, kMaxN);
+    return BHG_ERR_ARG;
+  }
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const bool vec = d % 4 == 0 && (((uintptr_t)X | (uintptr_t)W | (uintptr_t)dir) & 15) == 0;
+  const dim3 grid((n + kSuper - 1) / kSuper);
+  const long long* yy = reinterpret_cast<const long long*>(y);
+  if (vec)
+    hipLaunchKernelGGL((k_wsoftreg_mixed<true>), grid, dim3(kT), 0, st, X, W, dir, yy, c, n, d, C);
+  else
+    hipLaunchKernelGGL((k_wsoftreg_mixed<false>), grid, dim3(kT), 0, st, X, W, dir, yy, c, n, d, C);
+  BHG_HIP_CHECK(hipGetLastError());
+  return BHG_OK;
 }
 
 }  // extern "C"

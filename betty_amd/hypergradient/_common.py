@@ -200,6 +200,8 @@ LOGREG_SOLVE_STATS = {"fused": 0, "loop": 0}
 # the same for a declared SoftmaxRegressionL2 (csrc/bhg_softreg_solve.hip): `loop` — K = 0, impl = "torch", a shape outside the family
 # (C > 16, d > 4096, C d > 32768), unaligned / non-contiguous / non-fp32 tensors, hypergradient_hvp = "finite_difference"
 SOFTREG_SOLVE_STATS = {"fused": 0, "loop": 0}
+# ... and for a declared WeightedSoftmaxRegression (the row-weighted kernels of the same file): `loop` under the same conditions
+WSOFTREG_SOLVE_STATS = {"fused": 0, "loop": 0}
 
 
 def finite_difference_wanted(curr) -> bool:

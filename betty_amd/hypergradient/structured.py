@@ -43,7 +43,7 @@ import warnings
 import torch
 import torch.nn.functional as F
 
-from ._common import LOGREG_SOLVE_STATS, SOFTREG_SOLVE_STATS, _uses_ddp, finite_difference_wanted, is_fsdp, precision_of
+from ._common import LOGREG_SOLVE_STATS, SOFTREG_SOLVE_STATS, WSOFTREG_SOLVE_STATS, _uses_ddp, finite_difference_wanted, is_fsdp, precision_of
 
 
 class StructureMismatchError(RuntimeError):
@@ -786,19 +786,13 @@ class _QuadraticFD:
                 o.add_(r) if accumulate else o.copy_(r)
 
 
-class _PerWeightL2(_QuadraticFD):
-    """What LogisticRegressionL2 and SoftmaxRegressionL2 share: the upper parameters enter through ``1/2 sum lam * w^2`` with one
-    coefficient per weight, so the cotangent of the lam tensor is ``w * u`` for cg / neumann and ``-(w * v)`` for darts / sama, and
-    ``lam``'s own graph carries it to ``prev``'s parameters; and the front of the provider's own solver (``fused_cg`` /
-    ``fused_neumann``).  A subclass sets ``_SOLVE_STATS`` / ``_SOLVERS`` and has ``_fused_solve_ready(K, *state)`` and
-    ``_fused_solve(method, rhs, out, K, step)``; after ``prepare()`` it holds ``self.w`` (the flat weights) and ``self.lam``."""
+class _NativeSolveFront:
+    """The front of a provider's own solver (``fused_cg`` / ``fused_neumann``) for the linear models whose whole K loop runs in native
+    launches.  A subclass sets ``_SOLVE_STATS`` / ``_SOLVERS`` and has ``_fused_solve_ready(K, *state)`` and
+    ``_fused_solve(method, rhs, out, K, step)``."""
 
     _SOLVE_STATS: dict = {}
     _SOLVERS = ("", "")   # the backend's cg / neumann solve methods
-
-    def _lam_tensor(self):
-        """lam with its graph to prev's parameters, one coefficient per weight."""
-        return self.lam_fn()
 
     def fused_cg_ready(self, layout, K: int) -> bool:
         return layout.T == 1 and self._fused_solve_ready(K)
@@ -819,6 +813,17 @@ class _PerWeightL2(_QuadraticFD):
             self._SOLVE_STATS["loop"] += 1
             return False
         return self._fused_solve(self._SOLVERS[1], v, p, K, alpha)
+
+
+class _PerWeightL2(_NativeSolveFront, _QuadraticFD):
+    """What LogisticRegressionL2 and SoftmaxRegressionL2 share: the upper parameters enter through ``1/2 sum lam * w^2`` with one
+    coefficient per weight, so the cotangent of the lam tensor is ``w * u`` for cg / neumann and ``-(w * v)`` for darts / sama, and
+    ``lam``'s own graph carries it to ``prev``'s parameters; the front of the provider's own solver is _NativeSolveFront's.  After
+    ``prepare()`` a subclass holds ``self.w`` (the flat weights) and ``self.lam``."""
+
+    def _lam_tensor(self):
+        """lam with its graph to prev's parameters, one coefficient per weight."""
+        return self.lam_fn()
 
     def mixed_vjp(self, neg_x_views, sync: bool):
         coeff, self._coeff = getattr(self, "_coeff", None), None
@@ -1114,6 +1119,212 @@ class SoftmaxRegressionL2(_PerWeightL2):
         getattr(be, method)(self.X, self.w, self.lam_d, rhs, out, coeff, ws, K, step, -step)
         self._coeff = coeff
         SOFTREG_SOLVE_STATS["fused"] += 1
+        return True
+
+
+class WeightedSoftmaxRegression(_NativeSolveFront):
+    """Softmax regression whose upper variable is ONE WEIGHT PER TRAINING SAMPLE — data hyper-cleaning, example reweighting on a frozen
+    backbone: the inner model is ``nn.Linear(d, C, bias=False)`` on fixed features,
+
+        L_in(W, theta) = (1/n) sum_i a_i CE(x_i W^T, y_i) + 1/2 sum reg * W^2          a = weight_fn(), shape [n]
+
+    With P = softmax(X W^T) and Y the one-hot labels
+
+        H V = U^T X + reg * V,   Z = X V^T,   U_i = a_i (P_i * Z_i - P_i (P_i . Z_i)) / n
+        cotangent of a along a direction D:   c_i = sum_c (P_ic - Y_ic) (X D^T)_ic / n
+
+    and ``a``'s own graph carries c to ``prev``'s parameters.  ``curr.parameters()`` must be ``[weight]`` with a 2-D ``weight``; a bias
+    is not part of this closed form (append a column of ones to X instead).  ``weight_fn()`` returns ``a`` with its graph to ``prev``'s
+    parameters; ``reg`` is a float or a ``[C, d]`` tensor that does not require grad (a learned penalty is SoftmaxRegressionL2's
+    problem).  ``batch`` is ``(X, y)``, the rows of X in the order of ``a``.
+
+    ``prepare()`` / ``hvp``: the closed form in ATen ops.  ``impl="torch"`` runs it on any device and must be requested explicitly (tests
+    of the host logic); the default ``impl`` requires CUDA tensors (no CPU fallback).  On the GPU it is the un-fused product of the
+    generic loop, which runs whenever the provider's own solver does not apply.
+
+    cg / neumann: ``fused_cg`` / ``fused_neumann`` run the whole K loop in native launches (csrc/bhg_softreg_solve.hip, the row-weighted
+    kernels) under SoftmaxRegressionL2's conditions — K > 0, ``impl`` is hip, 2 <= C <= 16, d <= 4096, C d <= 32768, contiguous 16-byte
+    aligned fp32 tensors, the analytic product — and ``mixed_vjp`` then takes c from one more pass over X (bhg_wsoftreg_mixed);
+    everything else keeps K x (``hvp`` + recurrence kernel) and three ATen lines for c.  WSOFTREG_SOLVE_STATS (hypergradient/_common.py)
+    counts both.
+
+    darts / sama: no closed-form hop here (the weights enter through the data term: the central difference needs CE at perturbed
+    logits); the provider has no ``finite_difference`` and both stay on the opaque path.
+
+    First use (as SoftmaxRegressionL2): the first ``prepare()`` per (shape, n) refuses labels outside [0, C), then compares the
+    closed-form gradient, one H v and one mixed derivative with a double backward through the problem's real ``training_step_exec`` on a
+    seeded random direction and raises StructureMismatchError beyond VERIFY_RTOL; ``verify=False`` or VERIFY_STRUCTURE = False skips it.
+    """
+
+    def __init__(self, curr, prev, weight: torch.nn.Parameter, weight_fn: Callable, reg, batch=None, impl: Optional[str] = None,
+                 verify: bool = True):
+        self.curr, self.prev, self.weight, self.weight_fn, self.reg, self.batch = curr, prev, weight, weight_fn, reg, batch
+        self.impl, self.verify = impl, bool(verify)
+        params = list(curr.parameters())
+        if weight.dim() != 2:
+            raise ValueError("WeightedSoftmaxRegression: weight must be the 2-D [classes, features] matrix of the linear classifier")
+        if len(params) == 2 and params[0] is weight and params[1].dim() == 1 and params[1].shape[0] == weight.shape[0]:
+            raise ValueError("WeightedSoftmaxRegression: the model has a bias, which this closed form does not cover — use "
+                             "nn.Linear(d, C, bias=False) and append a column of ones to X")
+        if len(params) != 1 or params[0] is not weight:
+            raise ValueError("WeightedSoftmaxRegression: curr.parameters() must be [weight] (no bias: append a column of ones to X)")
+        if torch.is_tensor(reg):
+            if reg.requires_grad:
+                raise ValueError("WeightedSoftmaxRegression: reg is a constant here and must not require grad — a learned per-weight "
+                                 "penalty is SoftmaxRegressionL2's problem")
+            if tuple(reg.shape) != tuple(weight.shape):
+                raise ValueError(f"WeightedSoftmaxRegression: reg must be a float or a tensor of weight's shape {tuple(weight.shape)}")
+        else:
+            self.reg = float(reg)
+
+    def prepare(self):
+        from .. import _native  # noqa: PLC0415
+
+        x, y = self.batch if self.batch is not None else self.curr.cur_batch
+        impl = self.impl or "hip"
+        if impl not in ("hip", "torch"):
+            raise ValueError(f"unknown impl {impl!r}")
+        if impl == "hip" and not x.is_cuda:
+            raise _native.NativeLibraryError("WeightedSoftmaxRegression needs CUDA/HIP tensors; there is no CPU fallback")
+        dt = torch.float32 if impl == "hip" else self.weight.dtype
+        # the native solve reads the user's X in place: a copy made here (another dtype, a strided view) keeps the loop
+        self._x_in_place = x.dtype == torch.float32 and x.is_contiguous()
+        self.X = x.detach().reshape(x.shape[0], -1).to(dt).contiguous()
+        self.n, self.d = self.X.shape
+        self.C = int(self.weight.shape[0])
+        if self.weight.shape[1] != self.d:
+            raise ValueError(f"WeightedSoftmaxRegression: weight is {tuple(self.weight.shape)} but X has {self.d} features")
+        self.y = y.detach().reshape(-1).to(torch.int64).contiguous()
+        self.a = self.weight_fn()   # keeps the graph to prev's parameters
+        if not torch.is_tensor(self.a) or self.a.numel() != self.n:
+            raise ValueError(f"WeightedSoftmaxRegression: weight_fn() must return one weight per row of X ({self.n})")
+        self.a_d = self.a.detach().reshape(-1).to(dt).contiguous()
+        self.w = self.weight.detach().to(dt).contiguous()
+        if torch.is_tensor(self.reg):
+            self.reg_d = self.reg.detach().to(device=self.w.device, dtype=dt).contiguous()
+        else:
+            self.reg_d = torch.full_like(self.w, self.reg)
+        self.P = torch.softmax(self.X @ self.w.t(), dim=1)   # (the row maximum is subtracted inside)
+        self._solved = False
+        if self.verify and VERIFY_STRUCTURE:
+            self._verify_against_autograd()
+        return self.hvp
+
+    def hvp(self, direction_views):
+        (v,) = direction_views
+        V = v.detach().to(self.X.dtype).reshape(self.C, self.d)
+        PZ = self.P * (self.X @ V.t())
+        U = (PZ - self.P * PZ.sum(dim=1, keepdim=True)) * self.a_d.unsqueeze(1) / self.n
+        return [(U.t() @ self.X + self.reg_d * V).view(self.weight.shape)]
+
+    def _mixed_coeff_aten(self, direction):
+        """c [n] along ``direction`` ([C, d] or flat), the three ATen lines."""
+        Z = self.X @ direction.detach().to(self.X.dtype).reshape(self.C, self.d).t()
+        PmY = self.P.clone()
+        PmY[torch.arange(self.n, device=PmY.device), self.y] -= 1.0
+        return (PmY * Z).sum(dim=1) / self.n
+
+    def mixed_vjp(self, neg_x_views, sync: bool):
+        (u,) = neg_x_views
+        solved, self._solved = self._solved, False
+        if solved and self._tensors_native(u) and self.y.is_cuda:
+            from ..backend import get_backend  # noqa: PLC0415
+
+            c = torch.empty(self.n, device=self.X.device)
+            get_backend().wsoftreg_mixed(self.X, self.w, u, self.y, c)
+        else:
+            c = self._mixed_coeff_aten(u)
+        c = c.to(self.a.dtype).reshape(self.a.shape)
+        upper = self.prev.trainable_parameters()
+        if sync:
+            torch.autograd.backward(self.a, grad_tensors=c, inputs=upper)
+            return None
+        return list(torch.autograd.grad(self.a, upper, grad_outputs=c))
+
+    def _verify_against_autograd(self):
+        """See VERIFY_STRUCTURE.  The verdict is cached on the problem object, keyed by the shape and the batch size."""
+        key = (tuple(self.weight.shape), int(self.n), "WeightedSoftmaxRegression")
+        done = self.curr.__dict__.setdefault("_bhg_structure_verified", set()) if hasattr(self.curr, "__dict__") else set()
+        if key in done:
+            return
+        name = getattr(self.curr, "name", "?")
+        # before the training_step runs: cross_entropy itself fails on such labels, on a GPU with a device-side assertion; and
+        # ignore_index rows are not part of this closed form
+        if self.n > 0 and (int(self.y.min()) < 0 or int(self.y.max()) >= self.C):
+            raise StructureMismatchError(
+                f"hypergradient_structure of problem {name!r} declares {type(self).__name__} with {self.C} classes, but the batch holds "
+                f"labels outside [0, {self.C}) (min {int(self.y.min())}, max {int(self.y.max())}).")
+        weight, upper = self.weight, list(self.prev.trainable_parameters())
+        gen = torch.Generator(device="cpu").manual_seed(20240926)
+        v = torch.randn(weight.shape, generator=gen).to(device=weight.device, dtype=weight.dtype)
+        # the extra training_step of the check must not be seen by the run: the RNG streams are forked around it
+        devs = [weight.device] if weight.is_cuda else []
+        with torch.random.fork_rng(devices=devs), torch.enable_grad():
+            loss = self.curr.training_step_exec(self.batch if self.batch is not None else self.curr.cur_batch)
+            (g_auto,) = torch.autograd.grad(loss, [weight], create_graph=True)
+            second = torch.autograd.grad((g_auto * v).sum(), [weight] + upper, allow_unused=True)
+        hv_auto, mixed_auto = second[0], second[1:]
+        onehot = F.one_hot(self.y, self.C).to(self.P.dtype)
+        g_data, g_pen = ((self.P - onehot) * self.a_d.unsqueeze(1)).t() @ self.X / self.n, self.reg_d * self.w
+        (hv,) = self.hvp([v])
+        c = self._mixed_coeff_aten(v).to(self.a.dtype).reshape(self.a.shape)
+        mixed = torch.autograd.grad(self.a, upper, grad_outputs=c, retain_graph=True, allow_unused=True)
+
+        def rel(got, want):
+            num = sum(float((((a.double() if a is not None else 0.0) - (b.double() if b is not None else 0.0)) ** 2).sum())
+                      for a, b in zip(got, want) if not (a is None and b is None)) ** 0.5
+            den = sum(float((b.double() ** 2).sum()) for b in want if b is not None) ** 0.5
+            return num / den if den > 0 else num
+
+        # the gradient's two terms cancel at the inner optimum: its error is measured against THEIR size, not the (vanishing) sum's
+        e_g = float((g_data + g_pen - g_auto.detach()).double().norm() / (g_data.double().norm() + g_pen.double().norm()).clamp_min(1e-300))
+        e_hvp, e_mix = rel([hv], [hv_auto]), rel(list(mixed), list(mixed_auto))
+        tol = VERIFY_RTOL
+        if precision_of(self.curr) in ("fp16", "bf16"):   # the autograd side ran under autocast: its own error
+            tol = max(tol, 5e-2)
+        if not (e_g <= tol and e_hvp <= tol and e_mix <= tol):
+            raise StructureMismatchError(
+                f"hypergradient_structure of problem {name!r} declares {type(self).__name__}, but its training_step disagrees with that "
+                f"closed form: gradient off by {e_g:.2e}, Hessian-vector product on a random direction by {e_hvp:.2e}, mixed second "
+                f"derivative by {e_mix:.2e} (tolerance {tol:g}).  Typical causes: label smoothing, a reduction other than the sum over "
+                f"the batch divided by n (`sum`, or weights normalised by their own sum), a penalty that is not `1/2 sum(reg * W^2)`, a "
+                f"bias or another layer in the model.")
+        done.add(key)
+
+    # ---- the provider's own solver: all K iterations in native launches (csrc/bhg_softreg_solve.hip, the row-weighted kernels) ----
+    _SOLVE_STATS, _SOLVERS = WSOFTREG_SOLVE_STATS, ("wsoftreg_cg_solve", "wsoftreg_neumann_solve")
+
+    def _tensors_native(self, *state) -> bool:
+        N = self.C * self.d
+        if self.reg_d.shape != self.w.shape or self.w.numel() != N or self.a_d.numel() != self.n or any(t.numel() < N for t in state):
+            return False
+        return all(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.data_ptr() % 16 == 0
+                   for t in (self.X, self.w, self.reg_d, self.a_d) + state)
+
+    def _fused_solve_ready(self, K: int, *state) -> bool:
+        from ..backend import get_backend, softreg_solve_plan  # noqa: PLC0415
+
+        if not (K > 0 and (self.impl or "hip") == "hip") or finite_difference_wanted(self.curr):
+            return False
+        if getattr(self, "X", None) is None or not self._x_in_place or not hasattr(get_backend(), "wsoftreg_cg_solve"):
+            return False
+        if not self._tensors_native(*state):
+            return False
+        key = (self.n, self.d, self.C)
+        plan = SoftmaxRegressionL2._PLANS.get(key)   # (one plan function serves both structures)
+        if plan is None:
+            plan = SoftmaxRegressionL2._PLANS[key] = softreg_solve_plan(*key)
+        return not plan.startswith("none")
+
+    def _fused_solve(self, method: str, rhs, out, K: int, step: float) -> bool:
+        from ..backend import get_backend  # noqa: PLC0415
+
+        be = get_backend()
+        ws = be.softreg_solve_workspace(self.n, self.d, self.C, self.X.device)
+        # out = -step * (x_K | p_K): what the generic loop leaves in the flat solution for mixed_vjp (InnerOperator.out_sign = -1 here)
+        getattr(be, method)(self.X, self.w, self.reg_d, self.a_d, rhs, out, ws, K, step, -step)
+        self._solved = True
+        WSOFTREG_SOLVE_STATS["fused"] += 1
         return True
 
 

@@ -274,6 +274,23 @@ int bhg_softreg_cg_solve(const float* X, const float* W, const float* lam, const
 int bhg_softreg_neumann_solve(const float* X, const float* W, const float* lam, const float* rhs, float* out, float* coeff, void* ws,
                               int n, int d, int C, int K, float alpha, float out_scale, int form, int strips, void* stream);
 
+/* Sample-weighted softmax regression (same file): one weight a_i per row of X — a function of the upper problem's parameters — and a
+ * constant penalty reg [C, d] in lam's place,
+ *   L(W) = (1/n) sum_i a_i CE(x_i W^T, y_i) + 1/2 sum reg .* W^2,
+ *   H V = U^T X + reg .* V,  U_i = a_i (P_i .* Z_i - P_i (P_i . Z_i)) / n       (a_i multiplies before the division by n).
+ * The plan, the supported family, the forms and the workspace ARE the softreg ones: bhg_softreg_solve_plan(n, d, C, form, strips)
+ * names the form these solves take and bhg_softreg_solve_ws_bytes(n, d, C) sizes `ws`; the iterations, form / strips / out_scale and
+ * the contract are those of bhg_softreg_*_solve, with which a == 1 agrees bit for bit.  There is no coeff: the cotangent of a along
+ * a direction `dir` [C, d] (the solution) needs the labels,
+ *   c_i = sum_c (P_ic - [c == y_i]) (X dir^T)_ic / n,
+ * and is bhg_wsoftreg_mixed's one pass over X (same family, any n >= 1, no workspace, nothing combined across workgroups).
+ * y: n int64 labels (a label outside [0, C) matches no class); c: n floats, each written once.                                       */
+int bhg_wsoftreg_cg_solve(const float* X, const float* W, const float* reg, const float* a, const float* rhs, float* out, void* ws,
+                          int n, int d, int C, int K, float cg_alpha, float out_scale, int form, int strips, void* stream);
+int bhg_wsoftreg_neumann_solve(const float* X, const float* W, const float* reg, const float* a, const float* rhs, float* out, void* ws,
+                               int n, int d, int C, int K, float alpha, float out_scale, int form, int strips, void* stream);
+int bhg_wsoftreg_mixed(const float* X, const float* W, const float* dir, const int64_t* y, float* c, int n, int d, int C, void* stream);
+
 /* ReLU-MLP with per-sample-weighted cross-entropy (+ ridge) — SURVEY Appendix A.3; the inner
  * problem of examples/learning_to_reweight/main.py:117-127 (BASELINE cfg 2 / the metric's 10 M
  * parameter problem).  The caller computes the direction-independent quantities once per
