@@ -238,6 +238,7 @@ SYMBOLS = {
     "bhg_mlp_plan_describe": (c_int, [POINTER(Mlp), c_int, c_int, ctypes.c_char_p, c_size_t]),
     "bhg_copy2d": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_void_p]),
     "bhg_bn_ws_bytes": (c_size_t, [c_int]),
+    "bhg_bn_plan": (c_int, [c_int, c_int, c_int, c_char_p, c_size_t]),
     "bhg_bn_backward_vjp": (
         c_int,
         [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,

@@ -12,6 +12,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes
+import re
 import weakref
 from typing import List, Optional, Sequence
 
@@ -463,6 +464,16 @@ def softreg_solve_plan(n: int, d: int, C: int, form: int = SOFTREG_FORM_AUTO, st
     buf = ctypes.create_string_buffer(256)
     _native.check(_native.load().bhg_softreg_solve_plan(int(n), int(d), int(C), int(form), int(strips), buf, 256), "bhg_softreg_solve_plan")
     return buf.value.decode()
+
+
+def bn_plan(N: int, C: int, HW: int) -> dict:
+    """The launch geometry bhg_bn_backward_vjp takes for N samples, C channels and runs of HW elements, as a dict: ``vec`` (4: 16-byte
+    accesses, 1: scalar), ``groups`` sample groups of ``ng`` samples x ``chunks`` chunks of ``chunk`` elements = ``slices`` workgroups
+    per channel, ``tpr`` threads per run (bhg_bn_plan — host logic only: works on a box without a GPU).  A shape the launch refuses
+    raises."""
+    buf = ctypes.create_string_buffer(256)
+    _native.check(_native.load().bhg_bn_plan(int(N), int(C), int(HW), buf, 256), "bhg_bn_plan")
+    return {k: int(v) for k, v in re.findall(r"(\w+)=(-?\d+)", buf.value.decode())}
 
 
 _backend = None

@@ -172,6 +172,10 @@ inline void bn_slicing(BnArgs* q, int vec) {
   int chunks = (target + N - 1) / N;                            // more than one chunk per run only when there are few samples
   const int max_chunks = (HW + 1023) / 1024;
   if (chunks > max_chunks) chunks = max_chunks;
+  // One group must satisfy the slice bound whatever N is: the loop below only shrinks `groups`, and with chunks > kBnMaxSlices it had no
+  // fixed point to reach (N * C <= 3 and HW > 512 * 1024: `ng` counted up until it overflowed).  `chunk` is derived from the bounded
+  // count, so the recomputed count cannot exceed it.
+  if (chunks > kBnMaxSlices) chunks = kBnMaxSlices;
   if (chunks < 1) chunks = 1;
   const int chunk = (((HW + chunks - 1) / chunks) + 3) & ~3;
   chunks = (HW + chunk - 1) / chunk;
@@ -189,6 +193,13 @@ inline void bn_slicing(BnArgs* q, int vec) {
   q->ng = ng; q->groups = groups; q->chunks = chunks; q->chunk = chunk; q->slices = groups * chunks; q->tpr = tpr;
 }
 
+// Why the launch does not take a shape, or NULL where it does: bhg_bn_backward_vjp and bhg_bn_plan refuse the same shapes.
+inline const char* bn_shape_error(int N, int C, int HW) {
+  if (!(N > 0 && C > 0 && HW > 0)) return "empty tensor";
+  if (C > 65535) return "more than 65535 channels";   // the channel is the grid's y dimension
+  return nullptr;
+}
+
 }  // namespace
 }  // namespace bhg
 
@@ -198,12 +209,26 @@ extern "C" {
 
 size_t bhg_bn_ws_bytes(int C) { return C > 0 ? sizeof(double) * kBnSums * kBnMaxSlices * (size_t)C : 0; }
 
+int bhg_bn_plan(int N, int C, int HW, char* buf, size_t buf_bytes) {
+  BHG_REQUIRE(buf && buf_bytes > 0, "NULL buffer");
+  const char* bad = bn_shape_error(N, C, HW);
+  BHG_REQUIRE(!bad, bad);
+  const int vec = HW % 4 == 0 ? 4 : 1;
+  BnArgs q{};
+  q.N = N; q.C = C; q.HW = HW;
+  bn_slicing(&q, vec);
+  const int len = snprintf(buf, buf_bytes, "vec=%d groups=%d ng=%d chunks=%d chunk=%d slices=%d tpr=%d", vec, q.groups, q.ng, q.chunks,
+                           q.chunk, q.slices, q.tpr);
+  BHG_REQUIRE(len > 0 && (size_t)len < buf_bytes, "buffer too small for the plan line");
+  return BHG_OK;
+}
+
 int bhg_bn_backward_vjp(const float* x, const float* gy, const float* a, const float* gamma, const float* mean, const float* invstd,
                         const float* b, const float* c, int N, int C, int HW, float* dx, float* dgy, float* dgamma, void* ws,
                         size_t ws_bytes, void* stream) {
   BHG_REQUIRE(x && gy && mean && invstd && dx && dgy && ws, "null pointer");
-  BHG_REQUIRE(N > 0 && C > 0 && HW > 0, "empty tensor");
-  BHG_REQUIRE(C <= 65535, "more than 65535 channels");
+  const char* bad = bn_shape_error(N, C, HW);
+  BHG_REQUIRE(!bad, bad);
   BHG_REQUIRE(ws_bytes >= bhg_bn_ws_bytes(C), "workspace smaller than bhg_bn_ws_bytes(C)");
   const bool vec = HW % 4 == 0;
   if (vec)

@@ -552,8 +552,16 @@ int bhg_copy2d(float* dst, int64_t ldd, const float* src, int64_t lds, int64_t r
  *     dx, dgy (shaped like x, overwritten), dgamma ([C], overwritten; may be NULL)  =  d( <a, gx> + <b, ggamma> + <c, gbeta> ) / d(x, gy, gamma)
  * with mean / invstd ([C], what the forward saved) treated as the functions of x they are.  x, gy, a, dx, dgy: fp32, NCHW contiguous,
  * N x C x HW elements, 16-byte aligned when HW % 4 == 0; gamma may be NULL (affine = False).  `ws`: bhg_bn_ws_bytes(C) bytes of scratch.
- * Deterministic (two-stage sums in fixed order, fp64 accumulation), asynchronous on `stream`; 32 algorithmic bytes per element.          */
+ * Deterministic (two-stage sums in fixed order, fp64 accumulation), asynchronous on `stream`; 32 algorithmic bytes per element.
+ *
+ * bhg_bn_plan is host logic only (no launch, no device access): the geometry the two launches take for a shape, from the very slicing
+ * function the launch path calls, as one line of `key=value` pairs in buf: vec (4: 16-byte accesses, HW % 4 == 0; 1: scalar), groups
+ * (sample groups) x chunks (of the H*W run) = slices (workgroups per channel, <= 512: what bhg_bn_ws_bytes reserves), ng (samples per
+ * group), chunk (elements per chunk, a multiple of 4), tpr (threads per run, a power of two in [16, 256]).  A shape that
+ * bhg_bn_backward_vjp refuses (N, C or HW <= 0, C > 65535) is refused here with the same message.  For tests of the shape -> geometry
+ * map and for diagnostics.                                                                                                            */
 size_t bhg_bn_ws_bytes(int C);
+int bhg_bn_plan(int N, int C, int HW, char* buf, size_t buf_bytes);
 int bhg_bn_backward_vjp(const float* x, const float* gy, const float* a, const float* gamma, const float* mean, const float* invstd,
                         const float* b, const float* c, int N, int C, int HW, float* dx, float* dgy, float* dgamma, void* ws,
                         size_t ws_bytes, void* stream);

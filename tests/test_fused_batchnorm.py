@@ -5,7 +5,8 @@ CPU: the closed form (tests/bn_ref.py, the checker) against autograd's own doubl
 nodes wired as the package wires them, with the checker standing in for the HIP call — gradient, Hessian-vector product and a whole CG
 hypergradient equal to nn.BatchNorm2d's; the module's bookkeeping (running statistics, eval mode, state_dict, affine = False).
 GPU: the HIP kernels against the checker on the layer shapes of ResNet-12 (vector and scalar access paths, NULL cotangents), bit
-reproducibility, and the BASELINE cfg 3 solve with declared layers against the same solve with nn.BatchNorm2d."""
+reproducibility, and the BASELINE cfg 3 solve with declared layers against the same solve with nn.BatchNorm2d.  (The kernel pair in
+every regime of its slicing, per channel and with bounds checks: tests/test_bn_vjp_kernels.py; the slicing itself: tests/test_bn_plan.py.)"""
 import contextlib
 import os
 import sys
@@ -202,8 +203,7 @@ def test_hip_kernels_match_the_checker(shape, nulls):
         assert rel <= (2e-6 if N * H * W >= 16 else 1e-3), (shape, nulls, i, rel)
 
 
-@pytest.mark.gpu
-def test_module_on_the_gpu_matches_nn_batchnorm_gradient_and_hvp():
+def _module_matches_nn_batchnorm_on_the_gpu(shape):
     res = {}
     for fused in (False, True):
         torch.manual_seed(1)
@@ -211,7 +211,7 @@ def test_module_on_the_gpu_matches_nn_batchnorm_gradient_and_hvp():
         if fused:
             assert bnn.fuse_batchnorm_(net) == 2
         g = torch.Generator().manual_seed(1)
-        x, y = torch.randn(16, 3, 12, 12, generator=g).to(DEV), torch.randint(0, 3, (16,), generator=g).to(DEV)
+        x, y = torch.randn(shape, generator=g).to(DEV), torch.randint(0, 3, (shape[0],), generator=g).to(DEV)
         params = list(net.parameters())
         vec = [torch.randn(p.shape, generator=g).to(DEV) for p in params]
         c0 = bnn.fused_batchnorm_calls()
@@ -223,9 +223,27 @@ def test_module_on_the_gpu_matches_nn_batchnorm_gradient_and_hvp():
         res[fused] = ([t.detach().cpu().numpy() for t in grads], [t.cpu().numpy() for t in hv], net.b2.running_var.cpu())
     e_g, _ = rel_err(res[True][0], res[False][0])
     e_h, _ = rel_err(res[True][1], res[False][1])
-    print(f"FusedBatchNorm2d vs nn.BatchNorm2d on the GPU: gradient {e_g:.2e}, Hessian-vector product {e_h:.2e}")
+    print(f"FusedBatchNorm2d vs nn.BatchNorm2d on the GPU, input {tuple(shape)}: gradient {e_g:.2e}, Hessian-vector product {e_h:.2e}")
     assert e_g <= 1e-5 and e_h <= 1e-4, (e_g, e_h)
     torch.testing.assert_close(res[True][2], res[False][2])
+
+
+@pytest.mark.gpu
+def test_module_on_the_gpu_matches_nn_batchnorm_gradient_and_hvp():
+    _module_matches_nn_batchnorm_on_the_gpu((16, 3, 12, 12))
+
+
+@pytest.mark.gpu
+def test_module_on_the_gpu_matches_nn_batchnorm_where_a_run_takes_several_chunks():
+    """Through FusedBatchNorm2d itself on layers whose slicing cuts every H * W run into 33 chunks, the last one ragged (the kernel
+    pair alone, in every slicing regime: tests/test_bn_vjp_kernels.py)."""
+    from betty_amd.backend import bn_plan
+
+    shape = (2, 3, 32, 1028)
+    for C in (6, 4):                                   # _Net's two batch-norm layers
+        plan = bn_plan(shape[0], C, shape[2] * shape[3])
+        assert plan["vec"] == 4 and plan["chunks"] == 33 and plan["chunk"] == 1000 and plan["groups"] == 1, plan
+    _module_matches_nn_batchnorm_on_the_gpu(shape)
 
 
 # ---- PointwiseConv2d: a 1 x 1 convolution as the matrix product it is ---------------------------------------------------------------

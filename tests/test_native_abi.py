@@ -161,6 +161,29 @@ def test_argument_validation_without_gpu():
     assert lib.bhg_mlp_cg_global_phase(ctypes.byref(d), None, None, None, None, None, 1, 0, 1, _native.BHG_CG_GLOBAL_DOTS, 2, None, 1.0,
                                        0.0, None, None, 0, None) == -1
     assert b"multiple of 128" in lib.bhg_last_error()
+    # fused batch-norm double backward: shape, workspace, alignment and NULL checks come before the slicing and the launches (the
+    # pointers below are host memory: a call that got past the checks would not return -1 with these words)
+    host = (ctypes.c_float * 64)()
+    q = (ctypes.addressof(host) + 15) & ~15
+    need = lib.bhg_bn_ws_bytes(3)
+    assert need == 8 * 5 * 512 * 3 and lib.bhg_bn_ws_bytes(0) == 0 and lib.bhg_bn_ws_bytes(-1) == 0
+
+    def bn(x=q, gy=q, a=q, mean=q, invstd=q, dx=q, dgy=q, ws=q, N=2, C=3, HW=4, ws_bytes=None):
+        return lib.bhg_bn_backward_vjp(x, gy, a, q, mean, invstd, q, q, N, C, HW, dx, dgy, q, ws,
+                                       lib.bhg_bn_ws_bytes(C) if ws_bytes is None else ws_bytes, None)
+
+    for kw, word in [(dict(C=65536), b"65535 channels"), (dict(N=0), b"empty"), (dict(C=0), b"empty"), (dict(HW=0), b"empty"),
+                     (dict(N=-2), b"empty"), (dict(C=-1), b"empty"), (dict(HW=-4), b"empty"), (dict(ws_bytes=need - 1), b"workspace smaller"),
+                     (dict(ws_bytes=0), b"workspace smaller")]:
+        assert bn(**kw) == -1, kw
+        assert word in lib.bhg_last_error(), (kw, lib.bhg_last_error())
+    for name in ("x", "gy", "a", "dx", "dgy"):                 # H * W % 4 == 0: 16-byte accesses
+        for off in (4, 8, 12):
+            assert bn(**{name: q + off}) == -1, (name, off)
+            assert b"16-byte aligned" in lib.bhg_last_error(), (name, off, lib.bhg_last_error())
+    for name in ("x", "gy", "mean", "invstd", "dx", "dgy", "ws"):
+        assert bn(**{name: None}) == -1, name
+        assert b"null pointer" in lib.bhg_last_error(), (name, lib.bhg_last_error())
     # timing API
     tot, cnt = ctypes.c_double(1.0), ctypes.c_int(7)
     assert lib.bhg_timing_enable(0) == 0
