@@ -244,6 +244,13 @@ SYMBOLS = {
         [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
          c_void_p, c_size_t, c_void_p],
     ),
+    "bhg_dwconv_ws_bytes": (c_size_t, [c_int, c_int]),
+    "bhg_dwconv_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_char_p, c_size_t]),
+    "bhg_dwconv_backward_vjp": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+         c_void_p, c_void_p, c_size_t, c_void_p],
+    ),
 }
 
 _libs = {}          # path -> bound CDLL

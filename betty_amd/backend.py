@@ -476,6 +476,15 @@ def bn_plan(N: int, C: int, HW: int) -> dict:
     return {k: int(v) for k, v in re.findall(r"(\w+)=(-?\d+)", buf.value.decode())}
 
 
+def dwconv_plan(N: int, C: int, H: int, W: int, k: int, stride: int = 1, pad: int = 0, dil: int = 1) -> dict:
+    """The launch geometry bhg_dwconv_backward_vjp takes for a depthwise layer, as a dict (include/bhg.h: bhg_dwconv_plan — host logic
+    only: works on a box without a GPU).  A shape the launch refuses raises."""
+    buf = ctypes.create_string_buffer(512)
+    _native.check(_native.load().bhg_dwconv_plan(int(N), int(C), int(H), int(W), int(k), int(stride), int(pad), int(dil), buf, 512),
+                  "bhg_dwconv_plan")
+    return {k_: int(v) for k_, v in re.findall(r"(\w+)=(-?\d+)", buf.value.decode())}
+
+
 _backend = None
 _override = None
 

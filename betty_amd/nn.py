@@ -15,6 +15,9 @@ Parameters, buffers, ``state_dict`` keys, running-statistics updates and eval-mo
 class is a subclass that only overrides ``forward`` for CUDA fp32 training-mode inputs); on anything else — CPU tensors, eval mode,
 other dtypes, channels-last — it IS ``nn.BatchNorm2d``.  Third derivatives are not provided (the backward of the backward node is
 ``once_differentiable``): implicit differentiation needs second order only.
+
+``PointwiseConv2d`` and ``DepthwiseConv2d`` (further down) declare the other two layers of a DARTS / MobileNet-style block,
+ReLU -> depthwise k x k -> 1 x 1 -> BatchNorm2d; ``declare_layers_(module, depthwise=True)`` applies all three.
 """
 from __future__ import annotations
 
@@ -25,7 +28,8 @@ from torch.autograd.function import once_differentiable
 
 from . import _native
 
-__all__ = ["FusedBatchNorm2d", "fuse_batchnorm_", "fused_batchnorm_calls", "PointwiseConv2d", "declare_pointwise_convs_", "declare_layers_"]
+__all__ = ["FusedBatchNorm2d", "fuse_batchnorm_", "fused_batchnorm_calls", "PointwiseConv2d", "declare_pointwise_convs_", "DepthwiseConv2d",
+           "declare_depthwise_convs_", "depthwise_conv_calls", "declare_layers_"]
 
 _CALLS = {"forward": 0, "backward": 0, "backward_vjp": 0}   # test / measurement hook: which nodes ran
 
@@ -189,6 +193,143 @@ def declare_pointwise_convs_(module: torch.nn.Module) -> int:
     return n
 
 
-def declare_layers_(module: torch.nn.Module) -> dict:
-    """Every layer declaration this module offers, in place: ``{"batchnorm": n, "pointwise_conv": m}``."""
-    return {"batchnorm": fuse_batchnorm_(module), "pointwise_conv": declare_pointwise_convs_(module)}
+# ---- DepthwiseConv2d: the depthwise convolution of a DARTS SepConv / DilConv (or MobileNet) block ------------------------------------------
+# ReLU -> depthwise k x k -> 1 x 1 -> BatchNorm2d: with PointwiseConv2d and FusedBatchNorm2d this declares the whole block.  ATen's
+# _convolution_double_backward handles a grouped convolution with a loop over its groups — C tiny convolutions per depthwise layer and
+# term of a Hessian-vector product, enqueue-bound.  Declared, the layer's forward and first backward stay ATen's own
+# kernels, tied into the graph as two autograd.Function nodes as for batch norm, and the backward OF the backward node is one
+# bhg_dwconv_backward_vjp call (csrc/bhg_dwconv.hip): at most four launches.
+_DW_CALLS = {"forward": 0, "backward": 0, "backward_vjp": 0}   # test / measurement hook: which nodes ran
+_DW_KERNELS, _DW_STRIDES, _DW_DILATIONS = (3, 5, 7), (1, 2), (1, 2)   # the family bhg_dwconv_backward_vjp takes
+
+
+def depthwise_conv_calls() -> dict:
+    return dict(_DW_CALLS)
+
+
+_DW_WS = {}   # (device, stream) -> scratch for the per-slice sums of dw
+
+
+def _dw_workspace(device, C, k, lib):
+    key = (str(device), int(torch.cuda.current_stream(device).cuda_stream))
+    n = int(lib.bhg_dwconv_ws_bytes(int(C), int(k)))
+    ws = _DW_WS.get(key)
+    if ws is None or ws.numel() < n:
+        ws = _DW_WS[key] = torch.empty(max(n, 1 << 16), dtype=torch.uint8, device=device)
+    return ws
+
+
+def _dw_vjp_hip(x, w, gy, a, b, stride, pad, dil, need_dx=True, need_dw=True):
+    """(dx, dw, dgy) through bhg_dwconv_backward_vjp; dx / dw are None where not needed.  The product's only implementation: it raises
+    when the HIP extension is missing or the tensors are not on the GPU."""
+    if not x.is_cuda:
+        raise _native.NativeLibraryError("DepthwiseConv2d's double backward needs CUDA/HIP tensors; there is no CPU fallback")
+    lib = _native.load()
+    N, C, H, W = x.shape
+    k = w.shape[-1]
+
+    def prep(t):
+        if t is None:
+            return None
+        t = t.detach()
+        return t if (t.dtype == torch.float32 and t.is_contiguous() and t.data_ptr() % 16 == 0) else t.to(torch.float32).contiguous().clone()
+
+    x, w, gy, a, b = prep(x), prep(w), prep(gy), prep(a), prep(b)
+    dx = torch.empty_like(x) if need_dx else None
+    dw = torch.empty_like(w) if need_dw else None
+    dgy = torch.empty_like(gy)
+    ws = _dw_workspace(x.device, C, k, lib)
+    ptr = lambda t: None if t is None else t.data_ptr()   # noqa: E731
+    _native.check(
+        lib.bhg_dwconv_backward_vjp(x.data_ptr(), w.data_ptr(), gy.data_ptr(), ptr(a), ptr(b), int(N), int(C), int(H), int(W), int(k),
+                                    int(stride), int(pad), int(dil), ptr(dx), ptr(dw), dgy.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
+        "bhg_dwconv_backward_vjp")
+    return dx, dw, dgy
+
+
+_DW_VJP_IMPL = [_dw_vjp_hip]   # TEST HOOK ONLY (tests/test_depthwise_conv.py swaps in the float64 restatement to check the graph plumbing on CPU)
+
+
+class _DWConvBackward(torch.autograd.Function):
+    """(x, w, gy) -> (gx, gw): the depthwise convolution's backward as a graph node whose own backward is ONE fused call."""
+
+    @staticmethod
+    def forward(ctx, x, w, gy, stride, pad, dil, mask):
+        _DW_CALLS["backward"] += 1
+        gy = gy.contiguous()
+        # the backward nn.Conv2d itself would have run: the same kernels as an undeclared layer
+        gx, gw, _ = torch.ops.aten.convolution_backward(gy, x, w, None, [stride, stride], [pad, pad], [dil, dil], False, [0, 0], w.shape[0],
+                                                        [bool(mask[0]), bool(mask[1]), False])
+        ctx.save_for_backward(x, w, gy)
+        ctx.geometry = (stride, pad, dil)
+        ctx.set_materialize_grads(False)
+        return gx, gw
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, a, b):
+        x, w, gy = ctx.saved_tensors
+        _DW_CALLS["backward_vjp"] += 1
+        dx, dw, dgy = _DW_VJP_IMPL[0](x, w, gy, a, b, *ctx.geometry, need_dx=ctx.needs_input_grad[0], need_dw=ctx.needs_input_grad[1])
+        return dx, dw, dgy, None, None, None, None
+
+
+class _DWConv(torch.autograd.Function):
+    """The depthwise convolution on ATen's own kernel; its backward is the node above (so create_graph=True records THAT node)."""
+
+    @staticmethod
+    def forward(ctx, x, w, stride, pad, dil):
+        _DW_CALLS["forward"] += 1
+        ctx.save_for_backward(x, w)
+        ctx.geometry = (stride, pad, dil)
+        return torch.nn.functional.conv2d(x, w, None, stride, pad, dil, w.shape[0])
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, w = ctx.saved_tensors
+        gx, gw = _DWConvBackward.apply(x, w, gy, *ctx.geometry, (ctx.needs_input_grad[0], ctx.needs_input_grad[1]))
+        return gx, gw, None, None, None
+
+
+class DepthwiseConv2d(torch.nn.Conv2d):
+    """``nn.Conv2d`` with ``groups == in_channels == out_channels`` whose double backward is fused (comment above).  Same parameters and
+    ``state_dict``; any configuration or input outside the declared family IS ``nn.Conv2d``."""
+
+    def _family(self) -> bool:
+        k, s, d, p = self.kernel_size, self.stride, self.dilation, self.padding
+        return (self.groups == self.in_channels == self.out_channels and self.in_channels <= 65535 and self.bias is None
+                and self.padding_mode == "zeros" and k[0] == k[1] and k[0] in _DW_KERNELS and s[0] == s[1] and s[0] in _DW_STRIDES
+                and d[0] == d[1] and d[0] in _DW_DILATIONS and not isinstance(p, str) and p[0] == p[1] and isinstance(p[0], int)
+                and 0 <= p[0] <= d[0] * (k[0] - 1))
+
+    def _declared(self, x) -> bool:
+        if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.is_contiguous() and x.data_ptr() % 16 == 0):
+            return False
+        return self.weight.dtype == torch.float32 and self.weight.is_contiguous()
+
+    def forward(self, x):
+        if not self._family() or not self._declared(x) or not torch.is_grad_enabled():
+            return super().forward(x)
+        k, s, d, p = self.kernel_size[0], self.stride[0], self.dilation[0], self.padding[0]
+        if min(x.shape[2], x.shape[3]) + 2 * p - d * (k - 1) - 1 < 0 or x.shape[1] != self.in_channels:
+            return super().forward(x)     # nn.Conv2d's own error
+        return _DWConv.apply(x, self.weight, s, p, d)
+
+
+def declare_depthwise_convs_(module: torch.nn.Module) -> int:
+    """Re-class every depthwise ``nn.Conv2d`` of ``module`` (exact class) in :class:`DepthwiseConv2d`'s family, in place."""
+    n = 0
+    for m in module.modules():
+        if type(m) is torch.nn.Conv2d and DepthwiseConv2d._family(m):
+            m.__class__ = DepthwiseConv2d
+            n += 1
+    return n
+
+
+def declare_layers_(module: torch.nn.Module, depthwise: bool = False) -> dict:
+    """Every layer declaration this module offers, in place: ``{"batchnorm": n, "pointwise_conv": m}``, and with ``depthwise=True``
+    also ``"depthwise_conv": k``."""
+    out = {"batchnorm": fuse_batchnorm_(module), "pointwise_conv": declare_pointwise_convs_(module)}
+    if depthwise:
+        out["depthwise_conv"] = declare_depthwise_convs_(module)
+    return out

@@ -566,6 +566,38 @@ int bhg_bn_backward_vjp(const float* x, const float* gy, const float* a, const f
                         const float* b, const float* c, int N, int C, int HW, float* dx, float* dgy, float* dgamma, void* ws,
                         size_t ws_bytes, void* stream);
 
+/* ---- depthwise convolution inside an opaque Hessian-vector product (csrc/bhg_dwconv.hip) ------------------------------------------------
+ * ATen's convolution double backward handles a grouped convolution with a loop over its groups: C tiny convolutions per depthwise layer
+ * and term of a DARTS / MobileNet-style block.  This entry point is that derivative in at most four launches.  The layer: groups ==
+ * C_in == C_out, no bias, a square k x k filter w[C][k][k], `stride`, `pad`, `dil` the same in both dimensions, zero padding:
+ *     y[n,c,i,j] = sum_{u,v} w[c,u,v] x[n,c, i stride - pad + u dil, j stride - pad + v dil]
+ * Its first backward is F : (x, w, gy) -> (gx, gw); for cotangents a (of gx, shaped like x; may be NULL = zero) and b (of gw, shaped
+ * like w; may be NULL) the call writes d( <a, gx> + <b, gw> ) / d(x, w, gy):
+ *     dgy = conv(a, w) + conv(x, b)        dx = conv_backward_input(gy; filter b)        dw = conv_backward_weight(input a, gy)
+ * dx (shaped like x) and dw (shaped like w) may be NULL (not wanted); dgy (N x C x H_out x W_out) is required.  Every non-NULL output is
+ * overwritten in full (with zeros where its cotangent is absent, and in the rows and columns of dx that no output position reaches).
+ * fp32, NCHW contiguous.  Supported: k in {3, 5, 7}, stride in {1, 2}, dil in {1, 2}, 0 <= pad <= dil (k - 1), C <= 65535, H_out and
+ * W_out >= 1.  x and a must be 16-byte aligned when W % 4 == 0, gy when W_out % 4 == 0 (their planes are staged in 16-byte groups).
+ * (x only when b is given: it is staged for the conv(x, b) term alone.)
+ * `ws`: bhg_dwconv_ws_bytes(C, k) bytes of scratch (0 for non-positive arguments), 8-byte aligned — the per-slice sums of dw, at most 64
+ * slices per channel.  Refused with -1 and a message, before any device access: a shape outside the family, non-positive sizes, an
+ * empty output, NULL x / w / gy / dgy / ws, a workspace that is too small or not 8-byte aligned, a pointer that is not 16-byte aligned
+ * where that is required, and a tensor of more than 2^31 - 1 tiles in one pass (N C ceil(H / th) ceil(W / tw): beyond 10^11 elements).
+ * Every shape of the family fits the LDS budget (units per workgroup are halved until the staged tiles take at most 60 KiB; the plan's
+ * closing check 'tile larger than the LDS budget' cannot trigger inside the family).  Deterministic (dw: two-stage sums in fixed order, fp64), asynchronous on `stream`, no host synchronisation.
+ *
+ * bhg_dwconv_plan is host logic only (no launch, no device access): the geometry the launches take for a shape, from the very function
+ * the launch path calls, as one line of `key=value` pairs in buf: Ho, Wo; the tiling of the OUTPUT plane (dgy, dw) th x tw, pb units
+ * (plane tiles) per workgroup, ty x tx tiles per plane, rows x ls floats of LDS per unit, vec (4: 16-byte staging, 1: scalar); the same
+ * for the tiling of the INPUT plane (dx) with an `i` in front; units (sample tiles per channel) in `groups` of pb, gps groups per slice,
+ * slices per channel (<= max_slices: what bhg_dwconv_ws_bytes reserves); lds_dgy, lds_dx (bytes of LDS).  A shape that
+ * bhg_dwconv_backward_vjp refuses is refused here with the same message.                                                               */
+size_t bhg_dwconv_ws_bytes(int C, int k);
+int bhg_dwconv_plan(int N, int C, int H, int W, int k, int stride, int pad, int dil, char* buf, size_t buf_bytes);
+int bhg_dwconv_backward_vjp(const float* x, const float* w, const float* gy, const float* a, const float* b, int N, int C, int H, int W,
+                            int k, int stride, int pad, int dil, float* dx, float* dw, float* dgy, void* ws, size_t ws_bytes,
+                            void* stream);
+
 /* ---- finite-difference hypergradient of a ReLU-MLP inner problem (darts, SAMA; csrc/bhg_fd.hip) ------------------------------------
  * betty/hypergradient/darts.py:29-67 (sama.py:25-59 alike) for L_in = (1/B) sum_i s_lam(CE_i.detach()) * CE_i(w) (+ a ridge without lam):
  *   bhg_mlp_fd_forward  evaluates the network y = (... relu(x W_1^T + b_1) ...) W_L^T + b_L at w+ = w + eps v and w- = w+ - 2 eps v and
