@@ -16,7 +16,7 @@
 // Arithmetic of the recurrences: oracle/recurrence.c / tests/recurrence_ref.py (products rounded to fp32 before add / sub, fp64 dots,
 // fp32 quotients, den = dot(fl(cg_alpha Hp), p) but r -= alpha Hp with the un-scaled Hp, no breakdown guard, out_scale folded
 // into the last iteration).
-#include "bhg_common.hpp"
+#include "bhg_linear_solve.hpp"
 
 namespace bhg {
 namespace {
@@ -24,17 +24,10 @@ namespace {
 constexpr int kSingleMaxD = 1024;
 constexpr int64_t kSingleMaxElems = (int64_t)1 << 18;
 constexpr int kStripsMaxD = 4096;
-constexpr int kMaxStrips = 512;       // 2 workgroups of the widest pass per CU x 256 CUs
 constexpr int kRowsPerStrip = 16;     // auto: G = ceil(n / 16), capped at kMaxStrips
-constexpr int kColBlock = 64;         // columns per workgroup (one wave) of the partial-summing launches
 constexpr int kMaxColBlocks = kStripsMaxD / kColBlock;
-static_assert(64 + 8 * kMaxColBlocks <= 1024, "the den partials end before the vectors of the workspace");
-
-// workspace (strips form), byte offsets: [0] rr (fp64) | [64] den partials (kMaxColBlocks fp64) | [1024] Hp, x, r, p (CG) or
-// -, -, v, p (Neumann): 4 x dpad floats | partials [G][d]
-constexpr size_t kWsRr = 0, kWsDen = 64, kWsVec = 1024;
-inline size_t dpad(int d) { return ((size_t)d + 3) & ~(size_t)3; }
-inline size_t ws_part_off(int d) { return kWsVec + 4 * sizeof(float) * dpad(d); }
+constexpr size_t kWsVec = 1024;       // byte offset of the vectors of the workspace (strips_ws), past the den partials
+static_assert(kWsDen + 8 * kMaxColBlocks <= kWsVec, "the den partials end before the vectors of the workspace");
 
 // ---- the pass over X -------------------------------------------------------------------------------------------------
 // A lane holds NR elements of a row: 16-byte path, element e = float (e & 3) of the float4 at column (e / 4) * 256 + lane * 4;
@@ -142,19 +135,6 @@ __device__ __forceinline__ void combine_waves(float* red, const float (&acc)[NR]
     }
     __syncthreads();
   }
-}
-
-template <int W>
-__device__ __forceinline__ double block_sum_w(double v, double* red) {
-  v = wave_sum(v);
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  __syncthreads();  // protect `red` against the previous use
-  if (lane == 0) red[w] = v;
-  __syncthreads();
-  double s = 0.0;
-#pragma unroll
-  for (int i = 0; i < W; ++i) s += red[i];
-  return s;
 }
 
 constexpr int rows_in_flight(int NR) { return NR <= 4 ? 8 : NR <= 16 ? 4 : 1; }   // (a row of the widest instance is 64 registers)
@@ -267,163 +247,56 @@ __global__ __launch_bounds__(kThreads) void k_logreg_strip_pass(const float* __r
   }
 }
 
-// sum over the strips, in strip order, of column j (eight loads in flight)
-__device__ __forceinline__ double strip_sum(const float* __restrict__ part, const int G, const int d, const int j) {
-  double acc = 0.0;
-  int g = 0;
-  for (; g + 8 <= G; g += 8) {
-    float v[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) v[u] = part[(int64_t)(g + u) * d + j];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) acc += (double)v[u];
-  }
-  for (; g < G; ++g) acc += (double)part[(int64_t)g * d + j];
-  return acc;
-}
-
-// CG launch 2 (one wave per 64 columns): Hp = sum_g part[g] + fl(lam p), den partial of dot(fl(cg_alpha Hp), p) per workgroup.
+// The launches after the pass: thin wrappers of the shared bodies (bhg_linear_solve.hpp), N = d.  The CG update adds the den partials
+// serially in workgroup order in every thread.
 __global__ __launch_bounds__(kColBlock) void k_logreg_strip_hp(const float* __restrict__ part, const int G,
                                                                const float* __restrict__ lam, const float* __restrict__ p,
                                                                float* __restrict__ Hp, double* __restrict__ denpart, const int d,
                                                                const float cg_alpha) {
-  const int j = blockIdx.x * kColBlock + threadIdx.x;
-  double t = 0.0;
-  if (j < d) {
-    const float pj = p[j];
-    const float lp = lam[j] * pj;
-    const float hp = (float)strip_sum(part, G, d, j) + lp;
-    Hp[j] = hp;
-    const float ahp = cg_alpha * hp;
-    t = (double)ahp * (double)pj;
-  }
-  t = wave_sum(t);
-  if (threadIdx.x == 0) denpart[blockIdx.x] = t;
+  strip_hp_body(part, G, lam, p, Hp, denpart, d, cg_alpha);
 }
 
-// CG launch 3 (ONE workgroup: d <= 4096): both step lengths from fp64 sums in a fixed order, then x, r, p.  Iteration 0 takes
-// x = 0, r = p = rhs and r.r from rhs itself; rr travels to the next iteration in the workspace.  The last iteration writes out / coeff.
 __global__ __launch_bounds__(kThreads) void k_logreg_strip_cg_update(const float* __restrict__ rhs, const float* __restrict__ w,
                                                                      const float* __restrict__ Hp, const double* __restrict__ denpart,
                                                                      const int nden, double* __restrict__ rr_slot, float* __restrict__ x,
                                                                      float* __restrict__ r, float* __restrict__ p, float* __restrict__ out,
                                                                      float* __restrict__ coeff, const int d, const int k, const int last,
                                                                      const float out_scale) {
-  __shared__ double sred[kWaves];
-  const int tid = threadIdx.x;
-  const float* rin = k == 0 ? rhs : r;
-  const float* pin = k == 0 ? rhs : p;
-  double rr;
-  if (k == 0) {
-    double s = 0.0;
-    for (int j = tid; j < d; j += kThreads) s += (double)rhs[j] * (double)rhs[j];
-    rr = block_sum(s, sred);
-  } else {
-    rr = *rr_slot;
-  }
-  double den = 0.0;
-  for (int b = 0; b < nden; ++b) den += denpart[b];
-  const float alpha = (float)rr / (float)den;
-  double rn2 = 0.0;
-  for (int j = tid; j < d; j += kThreads) {
-    const float t = alpha * Hp[j];
-    const float rn = rin[j] - t;
-    rn2 += (double)rn * (double)rn;
-  }
-  rn2 = block_sum(rn2, sred);
-  const float beta = (float)rn2 / (float)rr;
-  for (int j = tid; j < d; j += kThreads) {
-    const float pj = pin[j];
-    const float t = alpha * Hp[j];
-    const float rn = rin[j] - t;
-    const float ap = alpha * pj;
-    float xn = (k == 0 ? 0.f : x[j]) + ap;
-    const float bp = beta * pj;
-    if (last) {
-      if (out_scale != 0.f) xn = out_scale * xn;
-      out[j] = xn;
-      if (coeff) coeff[j] = w[j] * xn;
-    } else {
-      x[j] = xn;
-      r[j] = rn;
-      p[j] = rn + bp;
-    }
-  }
-  if (tid == 0) *rr_slot = rn2;
+  strip_cg_update_body<kThreads, true>(rhs, w, Hp, denpart, nden, rr_slot, x, r, p, out, coeff, d, k, last, out_scale);
 }
 
-// Neumann launch 2 (one wave per 64 columns): Hv = sum_g part[g] + fl(lam v); v' = v - fl(alpha Hv); p' = v' + p.  Iteration 0 reads
-// v = p = rhs.  The last iteration writes out / coeff.
 __global__ __launch_bounds__(kColBlock) void k_logreg_strip_neumann_update(const float* __restrict__ part, const int G,
                                                                            const float* __restrict__ lam, const float* __restrict__ w,
                                                                            const float* vin, const float* pin, float* v, float* p,
                                                                            float* __restrict__ out, float* __restrict__ coeff, const int d,
                                                                            const float alpha, const int last, const float out_scale) {
-  const int j = blockIdx.x * kColBlock + threadIdx.x;
-  if (j >= d) return;
-  const float vj = vin[j];
-  const float lv = lam[j] * vj;
-  const float hv = (float)strip_sum(part, G, d, j) + lv;
-  const float t = alpha * hv;
-  const float vn = vj - t;
-  float pn = vn + pin[j];
-  if (last) {
-    if (out_scale != 0.f) pn = out_scale * pn;
-    out[j] = pn;
-    if (coeff) coeff[j] = w[j] * pn;
-  } else {
-    v[j] = vn;
-    p[j] = pn;
-  }
+  strip_neumann_update_body(part, G, lam, w, vin, pin, v, p, out, coeff, d, alpha, last, out_scale);
 }
 
-// K == 0: x = 0 (CG) | p = rhs (Neumann), scaled.
 __global__ __launch_bounds__(kThreads) void k_logreg_solve_k0(const float* __restrict__ rhs, const float* __restrict__ w,
                                                               float* __restrict__ out, float* __restrict__ coeff, const int d,
                                                               const int cg, const float out_scale) {
-  const int j = blockIdx.x * kThreads + threadIdx.x;
-  if (j >= d) return;
-  float o = cg ? 0.f : rhs[j];
-  if (out_scale != 0.f) o = out_scale * o;
-  out[j] = o;
-  if (coeff) coeff[j] = w[j] * o;
+  solve_k0_body(rhs, w, out, coeff, d, cg, out_scale);
 }
 
-// ---- host ------------------------------------------------------------------------------------------------------------------------
-enum { kFormNone = -1, kFormAuto = 0, kFormSingle = 1, kFormStrips = 2 };
-struct Plan {
-  int form;   // kFormNone | kFormSingle | kFormStrips
-  int G;      // strips
-  int rps;    // rows per strip
-};
+const StripKernels kStripKernels = {k_logreg_strip_hp, k_logreg_strip_cg_update, kThreads, k_logreg_strip_neumann_update};
 
+// ---- host ------------------------------------------------------------------------------------------------------------------------
 bool single_admits(int n, int d) { return d <= kSingleMaxD && (int64_t)n * d <= kSingleMaxElems; }
 bool strips_admits(int /*n*/, int d) { return d <= kStripsMaxD; }
 
 // BHG_OK and the plan, or BHG_ERR_ARG with the error set (a forced form the shape does not admit is an error, not a fallback)
 int make_plan(const char* fn, int n, int d, int form, int strips, Plan* out) {
-  if (n <= 0 || d <= 0) { set_error("%s: empty problem", fn); return BHG_ERR_ARG; }
-  if (n > (1 << 30)) { set_error("%s: more than 2^30 rows", fn); return BHG_ERR_ARG; }
-  if (form < kFormAuto || form > kFormStrips) { set_error("%s: form must be 0 (auto), 1 (single) or 2 (strips)", fn); return BHG_ERR_ARG; }
-  if (strips < 0 || strips > kMaxStrips) { set_error("%s: strips must be 0 (auto) .. %d", fn, kMaxStrips); return BHG_ERR_ARG; }
-  int f = form;
-  if (f == kFormAuto) f = single_admits(n, d) ? kFormSingle : strips_admits(n, d) ? kFormStrips : kFormNone;
+  int f;
+  const int rc = plan_form(fn, n <= 0 || d <= 0, n, form, strips, single_admits(n, d), strips_admits(n, d), &f);
+  if (rc != BHG_OK) return rc;
   if (f == kFormSingle && !single_admits(n, d)) {
     set_error("%s: the single form takes d <= %d and n * d <= %lld", fn, kSingleMaxD, (long long)kSingleMaxElems);
     return BHG_ERR_ARG;
   }
   if (f == kFormStrips && !strips_admits(n, d)) { set_error("%s: the strips form takes d <= %d", fn, kStripsMaxD); return BHG_ERR_ARG; }
-  out->form = f;
-  out->G = out->rps = 0;
-  if (f == kFormStrips) {
-    int G = strips;
-    if (G == 0) {
-      const int64_t want = ((int64_t)n + kRowsPerStrip - 1) / kRowsPerStrip;
-      G = (int)(want < kMaxStrips ? want : kMaxStrips);
-    }
-    out->G = G;
-    out->rps = (int)(((int64_t)n + G - 1) / G);
-  }
+  const int64_t want = ((int64_t)n + kRowsPerStrip - 1) / kRowsPerStrip;   // auto
+  *out = plan_of(f, n, strips, (int)(want < kMaxStrips ? want : kMaxStrips));
   return BHG_OK;
 }
 
@@ -477,28 +350,9 @@ int solve(const char* fn, const float* X, const float* w, const float* lam, cons
     BHG_HIP_CHECK(hipGetLastError());
     return BHG_OK;
   }
-  char* base = static_cast<char*>(ws);
-  double* rr = reinterpret_cast<double*>(base + kWsRr);
-  double* den = reinterpret_cast<double*>(base + kWsDen);
-  float* vecs = reinterpret_cast<float*>(base + kWsVec);
-  const size_t dp = dpad(d);
-  float *Hp = vecs, *sx = vecs + dp, *sr = vecs + 2 * dp, *sp = vecs + 3 * dp;
-  float* part = reinterpret_cast<float*>(base + ws_part_off(d));
-  const int cb = (d + kColBlock - 1) / kColBlock;
-  for (int k = 0; k < K; ++k) {
-    const int last = k == K - 1;
-    if (CG) {
-      launch_pass(st, pl, X, w, k == 0 ? rhs : sp, part, n, d, vec);
-      hipLaunchKernelGGL(k_logreg_strip_hp, dim3(cb), dim3(kColBlock), 0, st, (const float*)part, pl.G, lam, k == 0 ? rhs : (const float*)sp, Hp,
-                         den, d, a);
-      hipLaunchKernelGGL(k_logreg_strip_cg_update, dim3(1), dim3(kThreads), 0, st, rhs, w, (const float*)Hp, (const double*)den, cb, rr, sx,
-                         sr, sp, out, coeff, d, k, last, out_scale);
-    } else {
-      launch_pass(st, pl, X, w, k == 0 ? rhs : sr, part, n, d, vec);
-      hipLaunchKernelGGL(k_logreg_strip_neumann_update, dim3(cb), dim3(kColBlock), 0, st, (const float*)part, pl.G, lam, w,
-                         k == 0 ? rhs : (const float*)sr, k == 0 ? rhs : (const float*)sp, sr, sp, out, coeff, d, a, last, out_scale);
-    }
-  }
+  run_strips<CG>(st, kStripKernels, strips_ws(ws, kWsVec, d), pl.G,
+                 [&](const float* dir, float* part) { launch_pass(st, pl, X, w, dir, part, n, d, vec); }, lam, w, rhs, out, coeff, d, K, a,
+                 out_scale);
   BHG_HIP_CHECK(hipGetLastError());
   return BHG_OK;
 }
@@ -515,18 +369,13 @@ int bhg_logreg_solve_plan(int n, int d, int form, int strips, char* buf, size_t 
   Plan pl;
   const int rc = make_plan(__func__, n, d, form, strips, &pl);
   if (rc != BHG_OK) return rc;
-  if (pl.form == kFormSingle)
-    snprintf(buf, buf_bytes, "single: 1 launch per solve");
-  else if (pl.form == kFormStrips)
-    snprintf(buf, buf_bytes, "strips G=%d: %d rows per strip, 3 launches per cg iteration, 2 per neumann iteration", pl.G, pl.rps);
-  else
-    snprintf(buf, buf_bytes, "none");
+  plan_line(pl, buf, buf_bytes);
   return BHG_OK;
 }
 
 size_t bhg_logreg_solve_ws_bytes(int n, int d) {
   if (n <= 0 || d <= 0 || d > kStripsMaxD) return 0;
-  return ws_part_off(d) + sizeof(float) * (size_t)kMaxStrips * (size_t)d;
+  return strips_ws(nullptr, kWsVec, d).bytes;
 }
 
 int bhg_logreg_cg_solve(const float* X, const float* w, const float* lam, const float* rhs, float* out, float* coeff, void* ws, int n,

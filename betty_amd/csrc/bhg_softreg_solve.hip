@@ -34,7 +34,7 @@
 // into the last iteration).
 #include <float.h>
 
-#include "bhg_common.hpp"
+#include "bhg_linear_solve.hpp"
 
 namespace bhg {
 namespace {
@@ -53,20 +53,13 @@ constexpr int kSingleMaxN = 4096;
 constexpr int64_t kSingleMaxElems = (int64_t)1 << 18;
 constexpr int kSinglePer = kSingleMaxN / kT;  // state elements per thread of the single form
 constexpr int kSingleSlots = kSingleMaxN / 2 / (64 * kW);   // ... and in the single form: C >= 2, so d <= kSingleMaxN / 2
-constexpr int kMaxStrips = 512;
 constexpr int kAutoRowsPerStrip = 64;
 constexpr size_t kAutoPartBytes = (size_t)16 << 20;   // auto: G N floats stay under this
-constexpr int kColBlock = 64;                 // columns per workgroup (one wave) of the partial-summing launches
 constexpr int kMaxColBlocks = kMaxN / kColBlock;
+constexpr size_t kWsVec = 8192;               // byte offset of the vectors of the workspace (strips_ws), past the den partials
 static_assert(kSlots * 64 * kW == kMaxD && kSingleSlots * 64 * kW * 2 == kSingleMaxN, "the waves' column chunks cover the widest row");
 static_assert(kMaxColBlocks <= kT, "the CG update sums the den partials one per thread");
-
-// workspace (strips form), byte offsets: [0] rr (fp64) | [64] den partials (kMaxColBlocks fp64) | [8192] Hp, x, r, p (CG) or
-// -, -, v, p (Neumann): 4 x npad floats | partials [G][N]
-constexpr size_t kWsRr = 0, kWsDen = 64, kWsVec = 8192;
 static_assert(kWsDen + 8 * kMaxColBlocks <= kWsVec, "the den partials end before the vectors of the workspace");
-inline size_t npad(int N) { return ((size_t)N + 3) & ~(size_t)3; }
-inline size_t ws_part_off(int N) { return kWsVec + 4 * sizeof(float) * npad(N); }
 
 // ---- the pass over X -------------------------------------------------------------------------------------------------
 // Four consecutive floats of a row from column c, zero from column `d` on.  VEC: one 16-byte load (d % 4 == 0 and 16-byte aligned
@@ -260,19 +253,6 @@ __device__ __forceinline__ void store_acc(float* dst, const int d, const int C, 
   }
 }
 
-template <int WV>
-__device__ __forceinline__ double block_sum_w(double v, double* red) {
-  v = wave_sum(v);
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  __syncthreads();  // protect `red` against the previous use
-  if (lane == 0) red[w] = v;
-  __syncthreads();
-  double s = 0.0;
-#pragma unroll
-  for (int i = 0; i < WV; ++i) s += red[i];
-  return s;
-}
-
 // ---- single: the whole solve in one workgroup ---------------------------------------------------------------------------------
 // CG: x, r in registers, sdir = p.  Neumann: sdir = v (the direction), x = the accumulator p.  `a`: cg_alpha | alpha.  A thread owns
 // the flat elements {tid, tid + kT, ...}.
@@ -436,148 +416,60 @@ __global__ __launch_bounds__(kT) void k_wsoftreg_mixed(const float* __restrict__
   pass_rows<VEC, 1, kPassMixed>(X, W, dir, RowArgs{nullptr, y, c}, nullptr, d, C, st, n - st < kSuper ? n : st + kSuper, (float)n, acc);
 }
 
-// sum over the strips, in strip order, of flat element j (eight loads in flight)
-__device__ __forceinline__ double strip_sum(const float* __restrict__ part, const int G, const int N, const int j) {
-  double acc = 0.0;
-  int g = 0;
-  for (; g + 8 <= G; g += 8) {
-    float v[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) v[u] = part[(int64_t)(g + u) * N + j];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) acc += (double)v[u];
-  }
-  for (; g < G; ++g) acc += (double)part[(int64_t)g * N + j];
-  return acc;
-}
-
-// CG launch 2 (one wave per 64 elements): Hp = sum_g part[g] + fl(lam p), den partial of dot(fl(cg_alpha Hp), p) per workgroup.
+// The launches after the pass: thin wrappers of the shared bodies (bhg_linear_solve.hpp), N = C d; the sample-weighted problem runs
+// them too.  The CG update takes the den partials one per thread through block_sum_w.
 __global__ __launch_bounds__(kColBlock) void k_softreg_strip_hp(const float* __restrict__ part, const int G,
                                                                 const float* __restrict__ lam, const float* __restrict__ p,
                                                                 float* __restrict__ Hp, double* __restrict__ denpart, const int N,
                                                                 const float cg_alpha) {
-  const int j = blockIdx.x * kColBlock + threadIdx.x;
-  double t = 0.0;
-  if (j < N) {
-    const float pj = p[j];
-    const float lp = lam[j] * pj;
-    const float hp = (float)strip_sum(part, G, N, j) + lp;
-    Hp[j] = hp;
-    const float ahp = cg_alpha * hp;
-    t = (double)ahp * (double)pj;
-  }
-  t = wave_sum(t);
-  if (threadIdx.x == 0) denpart[blockIdx.x] = t;
+  strip_hp_body(part, G, lam, p, Hp, denpart, N, cg_alpha);
 }
 
-// CG launch 3 (ONE workgroup): both step lengths from fp64 sums in a fixed order, then x, r, p.  Iteration 0 takes x = 0,
-// r = p = rhs and r.r from rhs itself; rr travels to the next iteration in the workspace.  The last iteration writes out / coeff.
 __global__ __launch_bounds__(kT) void k_softreg_strip_cg_update(const float* __restrict__ rhs, const float* __restrict__ W,
                                                                 const float* __restrict__ Hp, const double* __restrict__ denpart,
                                                                 const int nden, double* __restrict__ rr_slot, float* __restrict__ x,
                                                                 float* __restrict__ r, float* __restrict__ p, float* __restrict__ out,
                                                                 float* __restrict__ coeff, const int N, const int k, const int last,
                                                                 const float out_scale) {
-  __shared__ double sred[kW];
-  const int tid = threadIdx.x;
-  const float* rin = k == 0 ? rhs : r;
-  const float* pin = k == 0 ? rhs : p;
-  double rr;
-  if (k == 0) {
-    double s = 0.0;
-    for (int j = tid; j < N; j += kT) s += (double)rhs[j] * (double)rhs[j];
-    rr = block_sum_w<kW>(s, sred);
-  } else {
-    rr = *rr_slot;
-  }
-  const double den = block_sum_w<kW>(tid < nden ? denpart[tid] : 0.0, sred);   // nden <= kMaxColBlocks <= kT
-  const float alpha = (float)rr / (float)den;
-  double rn2 = 0.0;
-  for (int j = tid; j < N; j += kT) {
-    const float t = alpha * Hp[j];
-    const float rn = rin[j] - t;
-    rn2 += (double)rn * (double)rn;
-  }
-  rn2 = block_sum_w<kW>(rn2, sred);
-  const float beta = (float)rn2 / (float)rr;
-  for (int j = tid; j < N; j += kT) {
-    const float pj = pin[j];
-    const float t = alpha * Hp[j];
-    const float rn = rin[j] - t;
-    const float ap = alpha * pj;
-    float xn = (k == 0 ? 0.f : x[j]) + ap;
-    const float bp = beta * pj;
-    if (last) {
-      if (out_scale != 0.f) xn = out_scale * xn;
-      out[j] = xn;
-      if (coeff) coeff[j] = W[j] * xn;
-    } else {
-      x[j] = xn;
-      r[j] = rn;
-      p[j] = rn + bp;
-    }
-  }
-  if (tid == 0) *rr_slot = rn2;
+  strip_cg_update_body<kT, false>(rhs, W, Hp, denpart, nden, rr_slot, x, r, p, out, coeff, N, k, last, out_scale);
 }
 
-// Neumann launch 2 (one wave per 64 elements): Hv = sum_g part[g] + fl(lam v); v' = v - fl(alpha Hv); p' = v' + p.  Iteration 0
-// reads v = p = rhs.  The last iteration writes out / coeff.
 __global__ __launch_bounds__(kColBlock) void k_softreg_strip_neumann_update(const float* __restrict__ part, const int G,
                                                                             const float* __restrict__ lam, const float* __restrict__ W,
                                                                             const float* vin, const float* pin, float* v, float* p,
                                                                             float* __restrict__ out, float* __restrict__ coeff, const int N,
                                                                             const float alpha, const int last, const float out_scale) {
-  const int j = blockIdx.x * kColBlock + threadIdx.x;
-  if (j >= N) return;
-  const float vj = vin[j];
-  const float lv = lam[j] * vj;
-  const float hv = (float)strip_sum(part, G, N, j) + lv;
-  const float t = alpha * hv;
-  const float vn = vj - t;
-  float pn = vn + pin[j];
-  if (last) {
-    if (out_scale != 0.f) pn = out_scale * pn;
-    out[j] = pn;
-    if (coeff) coeff[j] = W[j] * pn;
-  } else {
-    v[j] = vn;
-    p[j] = pn;
-  }
+  strip_neumann_update_body(part, G, lam, W, vin, pin, v, p, out, coeff, N, alpha, last, out_scale);
 }
 
-// K == 0: x = 0 (CG) | p = rhs (Neumann), scaled.
 __global__ __launch_bounds__(kThreads) void k_softreg_solve_k0(const float* __restrict__ rhs, const float* __restrict__ W,
                                                                float* __restrict__ out, float* __restrict__ coeff, const int N,
                                                                const int cg, const float out_scale) {
-  const int j = blockIdx.x * kThreads + threadIdx.x;
-  if (j >= N) return;
-  float o = cg ? 0.f : rhs[j];
-  if (out_scale != 0.f) o = out_scale * o;
-  out[j] = o;
-  if (coeff) coeff[j] = W[j] * o;
+  solve_k0_body(rhs, W, out, coeff, N, cg, out_scale);
 }
 
-// ---- host ------------------------------------------------------------------------------------------------------------------------
-enum { kFormNone = -1, kFormAuto = 0, kFormSingle = 1, kFormStrips = 2 };
-struct Plan {
-  int form;   // kFormNone | kFormSingle | kFormStrips
-  int G;      // strips
-  int rps;    // rows per strip
-};
+const StripKernels kStripKernels = {k_softreg_strip_hp, k_softreg_strip_cg_update, kT, k_softreg_strip_neumann_update};
 
+// ---- host ------------------------------------------------------------------------------------------------------------------------
 bool family_admits(int d, int C) { return C >= 2 && C <= kMaxC && d >= 1 && d <= kMaxD && (int64_t)C * d <= kMaxN; }
 bool single_admits(int n, int d, int C) {
   return family_admits(d, C) && C * d <= kSingleMaxN && (int64_t)n * d <= kSingleMaxElems;
 }
 
+// auto: kAutoRowsPerStrip rows per strip, as many strips as the partial buffer's cap and kMaxStrips allow
+int auto_strips(int n, int d, int C) {
+  int64_t want = ((int64_t)n + kAutoRowsPerStrip - 1) / kAutoRowsPerStrip;
+  const int64_t cap = (int64_t)(kAutoPartBytes / (sizeof(float) * (size_t)C * (size_t)d));
+  if (want > cap) want = cap;
+  if (want > kMaxStrips) want = kMaxStrips;
+  return (int)(want < 1 ? 1 : want);
+}
+
 // BHG_OK and the plan, or BHG_ERR_ARG with the error set (a forced form the shape does not admit is an error, not a fallback)
 int make_plan(const char* fn, int n, int d, int C, int form, int strips, Plan* out) {
-  if (n <= 0 || d <= 0 || C <= 0) { set_error("%s: empty problem", fn); return BHG_ERR_ARG; }
-  if (n > (1 << 30)) { set_error("%s: more than 2^30 rows", fn); return BHG_ERR_ARG; }
-  if (form < kFormAuto || form > kFormStrips) { set_error("%s: form must be 0 (auto), 1 (single) or 2 (strips)", fn); return BHG_ERR_ARG; }
-  if (strips < 0 || strips > kMaxStrips) { set_error("%s: strips must be 0 (auto) .. %d", fn, kMaxStrips); return BHG_ERR_ARG; }
-  int f = form;
-  if (f == kFormAuto) f = single_admits(n, d, C) ? kFormSingle : family_admits(d, C) ? kFormStrips : kFormNone;
+  int f;
+  const int rc = plan_form(fn, n <= 0 || d <= 0 || C <= 0, n, form, strips, single_admits(n, d, C), family_admits(d, C), &f);
+  if (rc != BHG_OK) return rc;
   if (f == kFormSingle && !single_admits(n, d, C)) {
     set_error("%s: the single form takes 2 <= C <= %d, C * d <= %d and n * d <= %lld", fn, kMaxC, kSingleMaxN, (long long)kSingleMaxElems);
     return BHG_ERR_ARG;
@@ -586,21 +478,7 @@ int make_plan(const char* fn, int n, int d, int C, int form, int strips, Plan* o
     set_error("%s: the strips form takes 2 <= C <= %d, d <= %d and C * d <= %d", fn, kMaxC, kMaxD, kMaxN);
     return BHG_ERR_ARG;
   }
-  out->form = f;
-  out->G = out->rps = 0;
-  if (f == kFormStrips) {
-    int G = strips;
-    if (G == 0) {
-      // auto: kAutoRowsPerStrip rows per strip, as many strips as the partial buffer's cap and kMaxStrips allow
-      int64_t want = ((int64_t)n + kAutoRowsPerStrip - 1) / kAutoRowsPerStrip;
-      const int64_t cap = (int64_t)(kAutoPartBytes / (sizeof(float) * (size_t)C * (size_t)d));
-      if (want > cap) want = cap;
-      if (want > kMaxStrips) want = kMaxStrips;
-      G = (int)(want < 1 ? 1 : want);
-    }
-    out->G = G;
-    out->rps = (int)(((int64_t)n + G - 1) / G);
-  }
+  *out = plan_of(f, n, strips, f == kFormStrips ? auto_strips(n, d, C) : 0);
   return BHG_OK;
 }
 
@@ -657,28 +535,9 @@ int solve(const char* fn, const float* X, const float* W, const float* lam, cons
     BHG_HIP_CHECK(hipGetLastError());
     return BHG_OK;
   }
-  char* base = static_cast<char*>(ws);
-  double* rr = reinterpret_cast<double*>(base + kWsRr);
-  double* den = reinterpret_cast<double*>(base + kWsDen);
-  float* vecs = reinterpret_cast<float*>(base + kWsVec);
-  const size_t np = npad(N);
-  float *Hp = vecs, *sx = vecs + np, *sr = vecs + 2 * np, *sp = vecs + 3 * np;
-  float* part = reinterpret_cast<float*>(base + ws_part_off(N));
-  const int cb = (N + kColBlock - 1) / kColBlock;
-  for (int k = 0; k < K; ++k) {
-    const int last = k == K - 1;
-    if (CG) {
-      launch_pass(st, pl, X, W, k == 0 ? rhs : sp, aw, part, n, d, C, vec);
-      hipLaunchKernelGGL(k_softreg_strip_hp, dim3(cb), dim3(kColBlock), 0, st, (const float*)part, pl.G, lam, k == 0 ? rhs : (const float*)sp,
-                         Hp, den, N, a);
-      hipLaunchKernelGGL(k_softreg_strip_cg_update, dim3(1), dim3(kT), 0, st, rhs, W, (const float*)Hp, (const double*)den, cb, rr, sx, sr,
-                         sp, out, coeff, N, k, last, out_scale);
-    } else {
-      launch_pass(st, pl, X, W, k == 0 ? rhs : sr, aw, part, n, d, C, vec);
-      hipLaunchKernelGGL(k_softreg_strip_neumann_update, dim3(cb), dim3(kColBlock), 0, st, (const float*)part, pl.G, lam, W,
-                         k == 0 ? rhs : (const float*)sr, k == 0 ? rhs : (const float*)sp, sr, sp, out, coeff, N, a, last, out_scale);
-    }
-  }
+  run_strips<CG>(st, kStripKernels, strips_ws(ws, kWsVec, N), pl.G,
+                 [&](const float* dir, float* part) { launch_pass(st, pl, X, W, dir, aw, part, n, d, C, vec); }, lam, W, rhs, out, coeff, N,
+                 K, a, out_scale);
   BHG_HIP_CHECK(hipGetLastError());
   return BHG_OK;
 }
@@ -695,18 +554,13 @@ int bhg_softreg_solve_plan(int n, int d, int C, int form, int strips, char* buf,
   Plan pl;
   const int rc = make_plan(__func__, n, d, C, form, strips, &pl);
   if (rc != BHG_OK) return rc;
-  if (pl.form == kFormSingle)
-    snprintf(buf, buf_bytes, "single: 1 launch per solve");
-  else if (pl.form == kFormStrips)
-    snprintf(buf, buf_bytes, "strips G=%d: %d rows per strip, 3 launches per cg iteration, 2 per neumann iteration", pl.G, pl.rps);
-  else
-    snprintf(buf, buf_bytes, "none");
+  plan_line(pl, buf, buf_bytes);
   return BHG_OK;
 }
 
 size_t bhg_softreg_solve_ws_bytes(int n, int d, int C) {
   if (n <= 0 || !family_admits(d, C)) return 0;
-  return ws_part_off(C * d) + sizeof(float) * (size_t)kMaxStrips * (size_t)C * (size_t)d;
+  return strips_ws(nullptr, kWsVec, (size_t)C * d).bytes;
 }
 
 int bhg_softreg_cg_solve(const float* X, const float* W, const float* lam, const float* rhs, float* out, float* coeff, void* ws, int n,

@@ -786,13 +786,48 @@ class _QuadraticFD:
                 o.add_(r) if accumulate else o.copy_(r)
 
 
+def _native_f32(t) -> bool:
+    """Can a native solver read / write ``t`` in place: a contiguous 16-byte aligned fp32 CUDA tensor."""
+    return t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.data_ptr() % 16 == 0
+
+
 class _NativeSolveFront:
     """The front of a provider's own solver (``fused_cg`` / ``fused_neumann``) for the linear models whose whole K loop runs in native
-    launches.  A subclass sets ``_SOLVE_STATS`` / ``_SOLVERS`` and has ``_fused_solve_ready(K, *state)`` and
-    ``_fused_solve(method, rhs, out, K, step)``."""
+    launches, and its one gate.  A subclass sets ``_SOLVE_STATS`` / ``_SOLVERS`` / ``_PLAN`` (/ ``_X_IN_PLACE``) and has
+    ``_solve_operands()`` -> ((tensor, its element count), ...), what the solver reads after ``prepare()``, the flat weights first;
+    ``_solve_shape()`` -> the arguments of the plan function; and ``_fused_solve(method, rhs, out, K, step)``."""
 
     _SOLVE_STATS: dict = {}
     _SOLVERS = ("", "")   # the backend's cg / neumann solve methods
+    _PLAN = ""            # betty_amd.backend's plan function: its line for _solve_shape() starts with "none" when no form takes the shape
+    _X_IN_PLACE = False   # the solver reads the user's X itself: prepare() must not have had to copy it (``self._x_in_place``)
+    _PLANS: dict = {}     # (plan function, shape) -> the library's plan line
+
+    def _tensors_native(self, *state) -> bool:
+        """The operands have their sizes, ``state`` (the caller's flat vectors) holds the solution, and all of them are _native_f32."""
+        ops = self._solve_operands()
+        for t, m in ops:
+            if t.numel() != m or not _native_f32(t):
+                return False
+        for t in state:
+            if t.numel() < ops[0][1] or not _native_f32(t):
+                return False
+        return True
+
+    def _fused_solve_ready(self, K: int, *state) -> bool:
+        from .. import backend  # noqa: PLC0415
+
+        if not (K > 0 and (self.impl or "hip") == "hip") or finite_difference_wanted(self.curr):
+            return False
+        if getattr(self, "X", None) is None or (self._X_IN_PLACE and not self._x_in_place):
+            return False
+        if not hasattr(backend.get_backend(), self._SOLVERS[0]) or not self._tensors_native(*state):
+            return False
+        key = (self._PLAN, self._solve_shape())
+        plan = _NativeSolveFront._PLANS.get(key)
+        if plan is None:
+            plan = _NativeSolveFront._PLANS[key] = getattr(backend, self._PLAN)(*key[1])
+        return not plan.startswith("none")
 
     def fused_cg_ready(self, layout, K: int) -> bool:
         return layout.T == 1 and self._fused_solve_ready(K)
@@ -927,25 +962,13 @@ class LogisticRegressionL2(_PerWeightL2):
         return [self.out.view(self.weight.shape)]
 
     # ---- the provider's own solver: all K iterations in native launches (csrc/bhg_logreg_solve.hip) ----
-    _PLANS = {}   # (n, d) -> the library's plan line
-    _SOLVE_STATS, _SOLVERS = LOGREG_SOLVE_STATS, ("logreg_cg_solve", "logreg_neumann_solve")
+    _SOLVE_STATS, _SOLVERS, _PLAN = LOGREG_SOLVE_STATS, ("logreg_cg_solve", "logreg_neumann_solve"), "logreg_solve_plan"
 
-    def _fused_solve_ready(self, K: int, *state) -> bool:
-        from ..backend import get_backend, logreg_solve_plan  # noqa: PLC0415
+    def _solve_operands(self):
+        return (self.w, self.d), (self.lam_d, self.d), (self.X, self.n * self.d)
 
-        if not (K > 0 and (self.impl or "hip") == "hip") or finite_difference_wanted(self.curr):
-            return False
-        if getattr(self, "X", None) is None or not hasattr(get_backend(), "logreg_cg_solve"):
-            return False
-        if self.lam_d.numel() != self.d or self.w.numel() != self.d or any(t.numel() < self.d for t in state):
-            return False
-        for t in (self.X, self.w, self.lam_d) + state:
-            if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.data_ptr() % 16 == 0):
-                return False
-        plan = self._PLANS.get((self.n, self.d))
-        if plan is None:
-            plan = self._PLANS[(self.n, self.d)] = logreg_solve_plan(self.n, self.d)
-        return not plan.startswith("none")
+    def _solve_shape(self):
+        return self.n, self.d
 
     def _fused_solve(self, method: str, rhs, out, K: int, step: float) -> bool:
         from ..backend import get_backend  # noqa: PLC0415
@@ -960,7 +983,98 @@ class LogisticRegressionL2(_PerWeightL2):
         return True
 
 
-class SoftmaxRegressionL2(_PerWeightL2):
+class _SoftmaxLinear(_NativeSolveFront):
+    """What SoftmaxRegressionL2 and WeightedSoftmaxRegression share: the model is ``nn.Linear(d, C, bias=False)`` under cross-entropy on
+    a batch ``(X, y)``, the native solver is csrc/bhg_softreg_solve.hip's (one plan function, ``X`` read in place), and the first-use
+    check compares gradient, H v and mixed derivative with the problem's real training_step.  A subclass states the closed-form terms
+    of that check: ``_gradient_terms(onehot)`` -> (data term, penalty term), ``_mixed_along(v)`` -> (the tensor that carries the graph
+    to ``prev``'s parameters, its cotangent along ``v``), and the sentence ``_TYPICAL_CAUSES``."""
+
+    _PLAN, _X_IN_PLACE = "softreg_solve_plan", True
+    _VERDICT = _TYPICAL_CAUSES = ""   # the structure's name in the key of the cached verdict | the last sentence of the refusal
+
+    def _init_model(self, curr, prev, weight, batch, impl, verify):
+        self.curr, self.prev, self.weight, self.batch, self.impl, self.verify = curr, prev, weight, batch, impl, bool(verify)
+        name, params = type(self).__name__, list(curr.parameters())
+        if weight.dim() != 2:
+            raise ValueError(f"{name}: weight must be the 2-D [classes, features] matrix of the linear classifier")
+        if len(params) == 2 and params[0] is weight and params[1].dim() == 1 and params[1].shape[0] == weight.shape[0]:
+            raise ValueError(f"{name}: the model has a bias, which this closed form does not cover — use "
+                             "nn.Linear(d, C, bias=False) and append a column of ones to X")
+        if len(params) != 1 or params[0] is not weight:
+            raise ValueError(f"{name}: curr.parameters() must be [weight] (no bias: append a column of ones to X)")
+
+    def _prepare_model(self):
+        """X, n, d, C, w and P of this step; returns (y, the dtype of the closed form)."""
+        from .. import _native  # noqa: PLC0415
+
+        x, y = self.batch if self.batch is not None else self.curr.cur_batch
+        impl = self.impl or "hip"
+        if impl not in ("hip", "torch"):
+            raise ValueError(f"unknown impl {impl!r}")
+        if impl == "hip" and not x.is_cuda:
+            raise _native.NativeLibraryError(f"{type(self).__name__} needs CUDA/HIP tensors; there is no CPU fallback")
+        dt = torch.float32 if impl == "hip" else self.weight.dtype
+        # the native solve reads the user's X in place: a copy made here (another dtype, a strided view) keeps the loop
+        self._x_in_place = x.dtype == torch.float32 and x.is_contiguous()
+        self.X = x.detach().reshape(x.shape[0], -1).to(dt).contiguous()
+        self.n, self.d = self.X.shape
+        self.C = int(self.weight.shape[0])
+        if self.weight.shape[1] != self.d:
+            raise ValueError(f"{type(self).__name__}: weight is {tuple(self.weight.shape)} but X has {self.d} features")
+        self.w = self.weight.detach().to(dt).contiguous()
+        self.P = torch.softmax(self.X @ self.w.t(), dim=1)   # (the row maximum is subtracted inside)
+        return y, dt
+
+    def _solve_shape(self):
+        return self.n, self.d, self.C
+
+    def _verify_cache(self):
+        """(key, verified keys): the verdict is cached on the problem object, keyed by the shape, the batch size and ``_VERDICT``."""
+        key = (tuple(self.weight.shape), int(self.n), self._VERDICT)
+        return key, self.curr.__dict__.setdefault("_bhg_structure_verified", set()) if hasattr(self.curr, "__dict__") else set()
+
+    def _verify_against_autograd(self, y):
+        """See VERIFY_STRUCTURE."""
+        key, done = self._verify_cache()
+        if key in done:
+            return
+        weight, upper = self.weight, list(self.prev.trainable_parameters())
+        gen = torch.Generator(device="cpu").manual_seed(20240926)
+        v = torch.randn(weight.shape, generator=gen).to(device=weight.device, dtype=weight.dtype)
+        # the extra training_step of the check must not be seen by the run: the RNG streams are forked around it
+        devs = [weight.device] if weight.is_cuda else []
+        with torch.random.fork_rng(devices=devs), torch.enable_grad():
+            loss = self.curr.training_step_exec(self.batch if self.batch is not None else self.curr.cur_batch)
+            (g_auto,) = torch.autograd.grad(loss, [weight], create_graph=True)
+            second = torch.autograd.grad((g_auto * v).sum(), [weight] + upper, allow_unused=True)
+        hv_auto, mixed_auto = second[0], second[1:]
+        g_data, g_pen = self._gradient_terms(F.one_hot(y.reshape(-1).long(), self.C).to(self.P.dtype))
+        (hv,) = self.hvp([v])
+        carrier, cotangent = self._mixed_along(v)
+        mixed = torch.autograd.grad(carrier, upper, grad_outputs=cotangent, retain_graph=True, allow_unused=True)
+
+        def rel(got, want):
+            num = sum(float((((a.double() if a is not None else 0.0) - (b.double() if b is not None else 0.0)) ** 2).sum())
+                      for a, b in zip(got, want) if not (a is None and b is None)) ** 0.5
+            den = sum(float((b.double() ** 2).sum()) for b in want if b is not None) ** 0.5
+            return num / den if den > 0 else num
+
+        # the gradient's two terms cancel at the inner optimum: its error is measured against THEIR size, not the (vanishing) sum's
+        e_g = float((g_data + g_pen - g_auto.detach()).double().norm() / (g_data.double().norm() + g_pen.double().norm()).clamp_min(1e-300))
+        e_hvp, e_mix = rel([hv], [hv_auto]), rel(list(mixed), list(mixed_auto))
+        tol = VERIFY_RTOL
+        if precision_of(self.curr) in ("fp16", "bf16"):   # the autograd side ran under autocast: its own error
+            tol = max(tol, 5e-2)
+        if not (e_g <= tol and e_hvp <= tol and e_mix <= tol):
+            raise StructureMismatchError(
+                f"hypergradient_structure of problem {getattr(self.curr, 'name', '?')!r} declares {type(self).__name__}, but its "
+                f"training_step disagrees with that closed form: gradient off by {e_g:.2e}, Hessian-vector product on a random direction "
+                f"by {e_hvp:.2e}, mixed second derivative by {e_mix:.2e} (tolerance {tol:g}).  {self._TYPICAL_CAUSES}")
+        done.add(key)
+
+
+class SoftmaxRegressionL2(_SoftmaxLinear, _PerWeightL2):
     """Softmax (multi-class logistic) regression with a per-weight L2 penalty — the reference's logistic-regression HPO example on
     multi-class data: the inner model is ``nn.Linear(d, C, bias=False)`` under cross-entropy,
 
@@ -996,42 +1110,17 @@ class SoftmaxRegressionL2(_PerWeightL2):
 
     def __init__(self, curr, prev, weight: torch.nn.Parameter, lam_fn: Callable, batch=None, impl: Optional[str] = None,
                  closed_form_fd: Optional[bool] = None, verify: bool = True):
-        self.curr, self.prev, self.weight, self.lam_fn, self.batch = curr, prev, weight, lam_fn, batch
-        self.impl, self.closed_form_fd, self.verify = impl, closed_form_fd, bool(verify)
-        params = list(curr.parameters())
-        if weight.dim() != 2:
-            raise ValueError("SoftmaxRegressionL2: weight must be the 2-D [classes, features] matrix of the linear classifier")
-        if len(params) == 2 and params[0] is weight and params[1].dim() == 1 and params[1].shape[0] == weight.shape[0]:
-            raise ValueError("SoftmaxRegressionL2: the model has a bias, which this closed form does not cover — use "
-                             "nn.Linear(d, C, bias=False) and append a column of ones to X")
-        if len(params) != 1 or params[0] is not weight:
-            raise ValueError("SoftmaxRegressionL2: curr.parameters() must be [weight] (no bias: append a column of ones to X)")
+        self._init_model(curr, prev, weight, batch, impl, verify)
+        self.lam_fn, self.closed_form_fd = lam_fn, closed_form_fd
 
     def _lam_tensor(self):
         lam = self.lam_fn()
         return torch.broadcast_to(lam, self.weight.shape) if torch.is_tensor(lam) and lam.shape != self.weight.shape else lam
 
     def prepare(self):
-        from .. import _native  # noqa: PLC0415
-
-        x, y = self.batch if self.batch is not None else self.curr.cur_batch
-        impl = self.impl or "hip"
-        if impl not in ("hip", "torch"):
-            raise ValueError(f"unknown impl {impl!r}")
-        if impl == "hip" and not x.is_cuda:
-            raise _native.NativeLibraryError("SoftmaxRegressionL2 needs CUDA/HIP tensors; there is no CPU fallback")
-        dt = torch.float32 if impl == "hip" else self.weight.dtype
-        # the native solve reads the user's X in place: a copy made here (another dtype, a strided view) keeps the loop
-        self._x_in_place = x.dtype == torch.float32 and x.is_contiguous()
-        self.X = x.detach().reshape(x.shape[0], -1).to(dt).contiguous()
-        self.n, self.d = self.X.shape
-        self.C = int(self.weight.shape[0])
-        if self.weight.shape[1] != self.d:
-            raise ValueError(f"SoftmaxRegressionL2: weight is {tuple(self.weight.shape)} but X has {self.d} features")
+        y, dt = self._prepare_model()
         self.lam = self._lam_tensor()   # keeps the graph to prev's parameters
         self.lam_d = self.lam.detach().to(dt).contiguous()
-        self.w = self.weight.detach().to(dt).contiguous()
-        self.P = torch.softmax(self.X @ self.w.t(), dim=1)   # (the row maximum is subtracted inside)
         self._coeff = None
         if self.verify and VERIFY_STRUCTURE:
             self._verify_against_autograd(y)
@@ -1044,70 +1133,22 @@ class SoftmaxRegressionL2(_PerWeightL2):
         U = (PZ - self.P * PZ.sum(dim=1, keepdim=True)) / self.n
         return [(U.t() @ self.X + self.lam_d * V).view(self.weight.shape)]
 
-    def _verify_against_autograd(self, y):
-        """See VERIFY_STRUCTURE.  The verdict is cached on the problem object, keyed by the shape and the batch size."""
-        key = (tuple(self.weight.shape), int(self.n), "SoftmaxRegressionL2")
-        done = self.curr.__dict__.setdefault("_bhg_structure_verified", set()) if hasattr(self.curr, "__dict__") else set()
-        if key in done:
-            return
-        weight, upper = self.weight, list(self.prev.trainable_parameters())
-        gen = torch.Generator(device="cpu").manual_seed(20240926)
-        v = torch.randn(weight.shape, generator=gen).to(device=weight.device, dtype=weight.dtype)
-        # the extra training_step of the check must not be seen by the run: the RNG streams are forked around it
-        devs = [weight.device] if weight.is_cuda else []
-        with torch.random.fork_rng(devices=devs), torch.enable_grad():
-            loss = self.curr.training_step_exec(self.batch if self.batch is not None else self.curr.cur_batch)
-            (g_auto,) = torch.autograd.grad(loss, [weight], create_graph=True)
-            second = torch.autograd.grad((g_auto * v).sum(), [weight] + upper, allow_unused=True)
-        hv_auto, mixed_auto = second[0], second[1:]
-        onehot = F.one_hot(y.reshape(-1).long(), self.C).to(self.P.dtype)
-        g_data, g_pen = (self.P - onehot).t() @ self.X / self.n, self.lam_d * self.w
-        (hv,) = self.hvp([v])
-        mixed = torch.autograd.grad(self.lam, upper, grad_outputs=(self.w * v.to(self.w.dtype)).to(self.lam.dtype), retain_graph=True,
-                                    allow_unused=True)
+    _VERDICT = "SoftmaxRegressionL2"
+    _TYPICAL_CAUSES = ("Typical causes: label smoothing, a reduction other than the batch mean, a penalty that is not "
+                       "`1/2 sum(lam * W^2)`, a bias or another layer in the model.")
 
-        def rel(got, want):
-            num = sum(float((((a.double() if a is not None else 0.0) - (b.double() if b is not None else 0.0)) ** 2).sum())
-                      for a, b in zip(got, want) if not (a is None and b is None)) ** 0.5
-            den = sum(float((b.double() ** 2).sum()) for b in want if b is not None) ** 0.5
-            return num / den if den > 0 else num
+    def _gradient_terms(self, onehot):
+        return (self.P - onehot).t() @ self.X / self.n, self.lam_d * self.w
 
-        # the gradient's two terms cancel at the inner optimum: its error is measured against THEIR size, not the (vanishing) sum's
-        e_g = float((g_data + g_pen - g_auto.detach()).double().norm() / (g_data.double().norm() + g_pen.double().norm()).clamp_min(1e-300))
-        e_hvp, e_mix = rel([hv], [hv_auto]), rel(list(mixed), list(mixed_auto))
-        tol = VERIFY_RTOL
-        if precision_of(self.curr) in ("fp16", "bf16"):   # the autograd side ran under autocast: its own error
-            tol = max(tol, 5e-2)
-        if not (e_g <= tol and e_hvp <= tol and e_mix <= tol):
-            raise StructureMismatchError(
-                f"hypergradient_structure of problem {getattr(self.curr, 'name', '?')!r} declares {type(self).__name__}, but its "
-                f"training_step disagrees with that closed form: gradient off by {e_g:.2e}, Hessian-vector product on a random direction "
-                f"by {e_hvp:.2e}, mixed second derivative by {e_mix:.2e} (tolerance {tol:g}).  Typical causes: label smoothing, a "
-                f"reduction other than the batch mean, a penalty that is not `1/2 sum(lam * W^2)`, a bias or another layer in the model.")
-        done.add(key)
+    def _mixed_along(self, v):
+        return self.lam, (self.w * v.to(self.w.dtype)).to(self.lam.dtype)
 
     # ---- the provider's own solver: all K iterations in native launches (csrc/bhg_softreg_solve.hip) ----
-    _PLANS = {}   # (n, d, C) -> the library's plan line
     _SOLVE_STATS, _SOLVERS = SOFTREG_SOLVE_STATS, ("softreg_cg_solve", "softreg_neumann_solve")
 
-    def _fused_solve_ready(self, K: int, *state) -> bool:
-        from ..backend import get_backend, softreg_solve_plan  # noqa: PLC0415
-
-        if not (K > 0 and (self.impl or "hip") == "hip") or finite_difference_wanted(self.curr):
-            return False
-        if getattr(self, "X", None) is None or not self._x_in_place or not hasattr(get_backend(), "softreg_cg_solve"):
-            return False
+    def _solve_operands(self):
         N = self.C * self.d
-        if self.lam_d.shape != self.w.shape or self.w.numel() != N or any(t.numel() < N for t in state):
-            return False
-        for t in (self.X, self.w, self.lam_d) + state:
-            if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.data_ptr() % 16 == 0):
-                return False
-        key = (self.n, self.d, self.C)
-        plan = self._PLANS.get(key)
-        if plan is None:
-            plan = self._PLANS[key] = softreg_solve_plan(*key)
-        return not plan.startswith("none")
+        return (self.w, N), (self.lam_d, N), (self.X, self.n * self.d)
 
     def _fused_solve(self, method: str, rhs, out, K: int, step: float) -> bool:
         from ..backend import get_backend  # noqa: PLC0415
@@ -1122,7 +1163,7 @@ class SoftmaxRegressionL2(_PerWeightL2):
         return True
 
 
-class WeightedSoftmaxRegression(_NativeSolveFront):
+class WeightedSoftmaxRegression(_SoftmaxLinear):
     """Softmax regression whose upper variable is ONE WEIGHT PER TRAINING SAMPLE — data hyper-cleaning, example reweighting on a frozen
     backbone: the inner model is ``nn.Linear(d, C, bias=False)`` on fixed features,
 
@@ -1158,16 +1199,8 @@ class WeightedSoftmaxRegression(_NativeSolveFront):
 
     def __init__(self, curr, prev, weight: torch.nn.Parameter, weight_fn: Callable, reg, batch=None, impl: Optional[str] = None,
                  verify: bool = True):
-        self.curr, self.prev, self.weight, self.weight_fn, self.reg, self.batch = curr, prev, weight, weight_fn, reg, batch
-        self.impl, self.verify = impl, bool(verify)
-        params = list(curr.parameters())
-        if weight.dim() != 2:
-            raise ValueError("WeightedSoftmaxRegression: weight must be the 2-D [classes, features] matrix of the linear classifier")
-        if len(params) == 2 and params[0] is weight and params[1].dim() == 1 and params[1].shape[0] == weight.shape[0]:
-            raise ValueError("WeightedSoftmaxRegression: the model has a bias, which this closed form does not cover — use "
-                             "nn.Linear(d, C, bias=False) and append a column of ones to X")
-        if len(params) != 1 or params[0] is not weight:
-            raise ValueError("WeightedSoftmaxRegression: curr.parameters() must be [weight] (no bias: append a column of ones to X)")
+        self._init_model(curr, prev, weight, batch, impl, verify)
+        self.weight_fn, self.reg = weight_fn, reg
         if torch.is_tensor(reg):
             if reg.requires_grad:
                 raise ValueError("WeightedSoftmaxRegression: reg is a constant here and must not require grad — a learned per-weight "
@@ -1178,36 +1211,19 @@ class WeightedSoftmaxRegression(_NativeSolveFront):
             self.reg = float(reg)
 
     def prepare(self):
-        from .. import _native  # noqa: PLC0415
-
-        x, y = self.batch if self.batch is not None else self.curr.cur_batch
-        impl = self.impl or "hip"
-        if impl not in ("hip", "torch"):
-            raise ValueError(f"unknown impl {impl!r}")
-        if impl == "hip" and not x.is_cuda:
-            raise _native.NativeLibraryError("WeightedSoftmaxRegression needs CUDA/HIP tensors; there is no CPU fallback")
-        dt = torch.float32 if impl == "hip" else self.weight.dtype
-        # the native solve reads the user's X in place: a copy made here (another dtype, a strided view) keeps the loop
-        self._x_in_place = x.dtype == torch.float32 and x.is_contiguous()
-        self.X = x.detach().reshape(x.shape[0], -1).to(dt).contiguous()
-        self.n, self.d = self.X.shape
-        self.C = int(self.weight.shape[0])
-        if self.weight.shape[1] != self.d:
-            raise ValueError(f"WeightedSoftmaxRegression: weight is {tuple(self.weight.shape)} but X has {self.d} features")
+        y, dt = self._prepare_model()
         self.y = y.detach().reshape(-1).to(torch.int64).contiguous()
         self.a = self.weight_fn()   # keeps the graph to prev's parameters
         if not torch.is_tensor(self.a) or self.a.numel() != self.n:
             raise ValueError(f"WeightedSoftmaxRegression: weight_fn() must return one weight per row of X ({self.n})")
         self.a_d = self.a.detach().reshape(-1).to(dt).contiguous()
-        self.w = self.weight.detach().to(dt).contiguous()
         if torch.is_tensor(self.reg):
             self.reg_d = self.reg.detach().to(device=self.w.device, dtype=dt).contiguous()
         else:
             self.reg_d = torch.full_like(self.w, self.reg)
-        self.P = torch.softmax(self.X @ self.w.t(), dim=1)   # (the row maximum is subtracted inside)
         self._solved = False
         if self.verify and VERIFY_STRUCTURE:
-            self._verify_against_autograd()
+            self._verify_against_autograd(self.y)
         return self.hvp
 
     def hvp(self, direction_views):
@@ -1241,80 +1257,34 @@ class WeightedSoftmaxRegression(_NativeSolveFront):
             return None
         return list(torch.autograd.grad(self.a, upper, grad_outputs=c))
 
-    def _verify_against_autograd(self):
-        """See VERIFY_STRUCTURE.  The verdict is cached on the problem object, keyed by the shape and the batch size."""
-        key = (tuple(self.weight.shape), int(self.n), "WeightedSoftmaxRegression")
-        done = self.curr.__dict__.setdefault("_bhg_structure_verified", set()) if hasattr(self.curr, "__dict__") else set()
+    _VERDICT = "WeightedSoftmaxRegression"
+    _TYPICAL_CAUSES = ("Typical causes: label smoothing, a reduction other than the sum over the batch divided by n (`sum`, or weights "
+                       "normalised by their own sum), a penalty that is not `1/2 sum(reg * W^2)`, a bias or another layer in the model.")
+
+    def _verify_against_autograd(self, y):
+        key, done = self._verify_cache()
         if key in done:
             return
-        name = getattr(self.curr, "name", "?")
         # before the training_step runs: cross_entropy itself fails on such labels, on a GPU with a device-side assertion; and
         # ignore_index rows are not part of this closed form
-        if self.n > 0 and (int(self.y.min()) < 0 or int(self.y.max()) >= self.C):
+        if self.n > 0 and (int(y.min()) < 0 or int(y.max()) >= self.C):
             raise StructureMismatchError(
-                f"hypergradient_structure of problem {name!r} declares {type(self).__name__} with {self.C} classes, but the batch holds "
-                f"labels outside [0, {self.C}) (min {int(self.y.min())}, max {int(self.y.max())}).")
-        weight, upper = self.weight, list(self.prev.trainable_parameters())
-        gen = torch.Generator(device="cpu").manual_seed(20240926)
-        v = torch.randn(weight.shape, generator=gen).to(device=weight.device, dtype=weight.dtype)
-        # the extra training_step of the check must not be seen by the run: the RNG streams are forked around it
-        devs = [weight.device] if weight.is_cuda else []
-        with torch.random.fork_rng(devices=devs), torch.enable_grad():
-            loss = self.curr.training_step_exec(self.batch if self.batch is not None else self.curr.cur_batch)
-            (g_auto,) = torch.autograd.grad(loss, [weight], create_graph=True)
-            second = torch.autograd.grad((g_auto * v).sum(), [weight] + upper, allow_unused=True)
-        hv_auto, mixed_auto = second[0], second[1:]
-        onehot = F.one_hot(self.y, self.C).to(self.P.dtype)
-        g_data, g_pen = ((self.P - onehot) * self.a_d.unsqueeze(1)).t() @ self.X / self.n, self.reg_d * self.w
-        (hv,) = self.hvp([v])
-        c = self._mixed_coeff_aten(v).to(self.a.dtype).reshape(self.a.shape)
-        mixed = torch.autograd.grad(self.a, upper, grad_outputs=c, retain_graph=True, allow_unused=True)
+                f"hypergradient_structure of problem {getattr(self.curr, 'name', '?')!r} declares {type(self).__name__} with {self.C} "
+                f"classes, but the batch holds labels outside [0, {self.C}) (min {int(y.min())}, max {int(y.max())}).")
+        super()._verify_against_autograd(y)
 
-        def rel(got, want):
-            num = sum(float((((a.double() if a is not None else 0.0) - (b.double() if b is not None else 0.0)) ** 2).sum())
-                      for a, b in zip(got, want) if not (a is None and b is None)) ** 0.5
-            den = sum(float((b.double() ** 2).sum()) for b in want if b is not None) ** 0.5
-            return num / den if den > 0 else num
+    def _gradient_terms(self, onehot):
+        return ((self.P - onehot) * self.a_d.unsqueeze(1)).t() @ self.X / self.n, self.reg_d * self.w
 
-        # the gradient's two terms cancel at the inner optimum: its error is measured against THEIR size, not the (vanishing) sum's
-        e_g = float((g_data + g_pen - g_auto.detach()).double().norm() / (g_data.double().norm() + g_pen.double().norm()).clamp_min(1e-300))
-        e_hvp, e_mix = rel([hv], [hv_auto]), rel(list(mixed), list(mixed_auto))
-        tol = VERIFY_RTOL
-        if precision_of(self.curr) in ("fp16", "bf16"):   # the autograd side ran under autocast: its own error
-            tol = max(tol, 5e-2)
-        if not (e_g <= tol and e_hvp <= tol and e_mix <= tol):
-            raise StructureMismatchError(
-                f"hypergradient_structure of problem {name!r} declares {type(self).__name__}, but its training_step disagrees with that "
-                f"closed form: gradient off by {e_g:.2e}, Hessian-vector product on a random direction by {e_hvp:.2e}, mixed second "
-                f"derivative by {e_mix:.2e} (tolerance {tol:g}).  Typical causes: label smoothing, a reduction other than the sum over "
-                f"the batch divided by n (`sum`, or weights normalised by their own sum), a penalty that is not `1/2 sum(reg * W^2)`, a "
-                f"bias or another layer in the model.")
-        done.add(key)
+    def _mixed_along(self, v):
+        return self.a, self._mixed_coeff_aten(v).to(self.a.dtype).reshape(self.a.shape)
 
     # ---- the provider's own solver: all K iterations in native launches (csrc/bhg_softreg_solve.hip, the row-weighted kernels) ----
     _SOLVE_STATS, _SOLVERS = WSOFTREG_SOLVE_STATS, ("wsoftreg_cg_solve", "wsoftreg_neumann_solve")
 
-    def _tensors_native(self, *state) -> bool:
+    def _solve_operands(self):
         N = self.C * self.d
-        if self.reg_d.shape != self.w.shape or self.w.numel() != N or self.a_d.numel() != self.n or any(t.numel() < N for t in state):
-            return False
-        return all(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.data_ptr() % 16 == 0
-                   for t in (self.X, self.w, self.reg_d, self.a_d) + state)
-
-    def _fused_solve_ready(self, K: int, *state) -> bool:
-        from ..backend import get_backend, softreg_solve_plan  # noqa: PLC0415
-
-        if not (K > 0 and (self.impl or "hip") == "hip") or finite_difference_wanted(self.curr):
-            return False
-        if getattr(self, "X", None) is None or not self._x_in_place or not hasattr(get_backend(), "wsoftreg_cg_solve"):
-            return False
-        if not self._tensors_native(*state):
-            return False
-        key = (self.n, self.d, self.C)
-        plan = SoftmaxRegressionL2._PLANS.get(key)   # (one plan function serves both structures)
-        if plan is None:
-            plan = SoftmaxRegressionL2._PLANS[key] = softreg_solve_plan(*key)
-        return not plan.startswith("none")
+        return (self.w, N), (self.reg_d, N), (self.a_d, self.n), (self.X, self.n * self.d)
 
     def _fused_solve(self, method: str, rhs, out, K: int, step: float) -> bool:
         from ..backend import get_backend  # noqa: PLC0415
