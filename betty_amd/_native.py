@@ -251,6 +251,13 @@ SYMBOLS = {
         [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
          c_void_p, c_void_p, c_size_t, c_void_p],
     ),
+    "bhg_layernorm_ws_bytes": (c_size_t, [c_int]),
+    "bhg_layernorm_plan": (c_int, [ctypes.c_longlong, c_int, c_char_p, c_size_t]),
+    "bhg_layernorm_backward_vjp": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_longlong, c_int, c_void_p, c_void_p,
+         c_void_p, c_void_p, c_size_t, c_void_p],
+    ),
 }
 
 _libs = {}          # path -> bound CDLL

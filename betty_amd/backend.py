@@ -485,6 +485,16 @@ def dwconv_plan(N: int, C: int, H: int, W: int, k: int, stride: int = 1, pad: in
     return {k_: int(v) for k_, v in re.findall(r"(\w+)=(-?\d+)", buf.value.decode())}
 
 
+def layernorm_plan(M: int, D: int) -> dict:
+    """The launch geometry bhg_layernorm_backward_vjp takes for M rows of D elements, as a dict: ``vec`` (4: 16-byte accesses, 1: scalar),
+    ``tpr`` threads per row, ``rows`` rows side by side (one row group), ``nv`` vectors per thread (``inst``: of the kernel instance),
+    ``groups`` row groups in ``slices`` slices of ``gps`` groups (<= ``max_slices``), ``ws`` bytes of workspace written (include/bhg.h:
+    bhg_layernorm_plan — host logic only: works on a box without a GPU).  A shape the launch refuses raises."""
+    buf = ctypes.create_string_buffer(256)
+    _native.check(_native.load().bhg_layernorm_plan(int(M), int(D), buf, 256), "bhg_layernorm_plan")
+    return {k: int(v) for k, v in re.findall(r"(\w+)=(-?\d+)", buf.value.decode())}
+
+
 _backend = None
 _override = None
 

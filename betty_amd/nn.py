@@ -17,7 +17,9 @@ other dtypes, channels-last — it IS ``nn.BatchNorm2d``.  Third derivatives are
 ``once_differentiable``): implicit differentiation needs second order only.
 
 ``PointwiseConv2d`` and ``DepthwiseConv2d`` (further down) declare the other two layers of a DARTS / MobileNet-style block,
-ReLU -> depthwise k x k -> 1 x 1 -> BatchNorm2d; ``declare_layers_(module, depthwise=True)`` applies all three.
+ReLU -> depthwise k x k -> 1 x 1 -> BatchNorm2d; ``declare_layers_(module, depthwise=True)`` applies all three.  ``FusedLayerNorm``
+(at the end) is the same declaration for ``nn.LayerNorm`` — the normalisation of a transformer block;
+``declare_layers_(module, layernorm=True)`` applies it.
 """
 from __future__ import annotations
 
@@ -29,7 +31,7 @@ from torch.autograd.function import once_differentiable
 from . import _native
 
 __all__ = ["FusedBatchNorm2d", "fuse_batchnorm_", "fused_batchnorm_calls", "PointwiseConv2d", "declare_pointwise_convs_", "DepthwiseConv2d",
-           "declare_depthwise_convs_", "depthwise_conv_calls", "declare_layers_"]
+           "declare_depthwise_convs_", "depthwise_conv_calls", "FusedLayerNorm", "fuse_layernorm_", "fused_layernorm_calls", "declare_layers_"]
 
 _CALLS = {"forward": 0, "backward": 0, "backward_vjp": 0}   # test / measurement hook: which nodes ran
 
@@ -326,10 +328,141 @@ def declare_depthwise_convs_(module: torch.nn.Module) -> int:
     return n
 
 
-def declare_layers_(module: torch.nn.Module, depthwise: bool = False) -> dict:
-    """Every layer declaration this module offers, in place: ``{"batchnorm": n, "pointwise_conv": m}``, and with ``depthwise=True``
-    also ``"depthwise_conv": k``."""
+# ---- FusedLayerNorm: the normalisation of a transformer block -------------------------------------------------------------------------------
+# ATen differentiates native_layer_norm_backward by decomposition, as it does for batch norm: 216 ATen operator calls per layer and
+# product on a 64 x 768 input, most of them activation-sized streaming passes.  Declared, the layer's forward and first backward stay
+# ATen's own kernels (native_layer_norm / native_layer_norm_backward), tied into the graph as two autograd.Function nodes as for batch
+# norm, and the backward OF the backward node is one bhg_layernorm_backward_vjp call (csrc/bhg_layernorm.hip): at most two launches.
+_LN_CALLS = {"forward": 0, "backward": 0, "backward_vjp": 0}   # test / measurement hook: which nodes ran
+_LN_MAX_D = 8192                                               # the family bhg_layernorm_backward_vjp takes: rows of at most 8192 elements
+
+
+def fused_layernorm_calls() -> dict:
+    return dict(_LN_CALLS)
+
+
+_LN_WS = {}   # (device, stream) -> scratch for the per-slice sums of dgamma
+
+
+def _ln_workspace(device, D, lib):
+    key = (str(device), int(torch.cuda.current_stream(device).cuda_stream))
+    n = int(lib.bhg_layernorm_ws_bytes(int(D)))
+    ws = _LN_WS.get(key)
+    if ws is None or ws.numel() < n:
+        ws = _LN_WS[key] = torch.empty(max(n, 1 << 16), dtype=torch.uint8, device=device)
+    return ws
+
+
+def _ln_vjp_hip(x, gy, a, gamma, mean, rstd, b, c):
+    """(dx, dgy, dgamma) through bhg_layernorm_backward_vjp; dgamma is None when gamma is.  The product's only implementation: it raises
+    when the HIP extension is missing or the tensors are not on the GPU."""
+    if not x.is_cuda:
+        raise _native.NativeLibraryError("FusedLayerNorm's double backward needs CUDA/HIP tensors; there is no CPU fallback")
+    lib = _native.load()
+    M = mean.numel()
+    D = x.numel() // M
+
+    def prep(t):
+        if t is None:
+            return None
+        t = t.detach()
+        return t if (t.dtype == torch.float32 and t.is_contiguous() and t.data_ptr() % 16 == 0) else t.to(torch.float32).contiguous().clone()
+
+    x, gy, a, gamma, mean, rstd, b, c = (prep(t) for t in (x, gy, a, gamma, mean, rstd, b, c))
+    dx, dgy = torch.empty_like(x), torch.empty_like(x)
+    dgamma = torch.empty_like(gamma) if gamma is not None else None
+    ws = _ln_workspace(x.device, D, lib)
+    ptr = lambda t: None if t is None else t.data_ptr()   # noqa: E731
+    _native.check(
+        lib.bhg_layernorm_backward_vjp(x.data_ptr(), gy.data_ptr(), ptr(a), ptr(gamma), mean.data_ptr(), rstd.data_ptr(), ptr(b), ptr(c),
+                                       int(M), int(D), dx.data_ptr(), dgy.data_ptr(), ptr(dgamma), ws.data_ptr(), ws.numel(), _stream()),
+        "bhg_layernorm_backward_vjp")
+    return dx, dgy, dgamma
+
+
+_LN_VJP_IMPL = [_ln_vjp_hip]   # TEST HOOK ONLY (tests/test_fused_layernorm.py swaps in the float64 restatement to check the graph plumbing on CPU)
+
+
+class _LNBackward(torch.autograd.Function):
+    """(x, gy, gamma) -> (gx, ggamma, gbeta): layer norm's backward as a graph node whose own backward is ONE fused call."""
+
+    @staticmethod
+    def forward(ctx, x, gy, gamma, beta, mean, rstd, normalized_shape, need_dx):
+        _LN_CALLS["backward"] += 1
+        gy = gy.contiguous()
+        # the backward nn.LayerNorm itself would have run: the same kernels as an undeclared layer
+        gx, gg, gb = torch.ops.aten.native_layer_norm_backward(gy, x, normalized_shape, mean, rstd, gamma, beta,
+                                                               [bool(need_dx), gamma is not None, beta is not None])
+        ctx.save_for_backward(x, gy, gamma, mean, rstd)
+        ctx.set_materialize_grads(False)
+        return (gx if need_dx else None), (gg if gamma is not None else None), (gb if beta is not None else None)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, a, b, c):
+        x, gy, gamma, mean, rstd = ctx.saved_tensors
+        _LN_CALLS["backward_vjp"] += 1
+        dx, dgy, dgamma = _LN_VJP_IMPL[0](x, gy, a, gamma, mean, rstd, b, c)
+        return dx, dgy, dgamma, None, None, None, None, None
+
+
+class _LNForward(torch.autograd.Function):
+    """Layer norm on ATen's own kernel; its backward is the node above (so create_graph=True records THAT node)."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, normalized_shape, eps):
+        _LN_CALLS["forward"] += 1
+        y, mean, rstd = torch.native_layer_norm(x, normalized_shape, gamma, beta, eps)
+        ctx.save_for_backward(x, gamma, beta, mean, rstd)
+        ctx.normalized_shape = normalized_shape
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, gamma, beta, mean, rstd = ctx.saved_tensors
+        gx, gg, gb = _LNBackward.apply(x, gy, gamma, beta, mean, rstd, ctx.normalized_shape, ctx.needs_input_grad[0])
+        return gx, gg, gb, None, None
+
+
+class FusedLayerNorm(torch.nn.LayerNorm):
+    """``nn.LayerNorm`` whose double backward is fused (comment above).  Same parameters and ``state_dict``
+    (``elementwise_affine=False`` and ``bias=False`` included); an input outside the declared family — not CUDA fp32 contiguous and
+    16-byte aligned, more than 8192 normalised elements, grad disabled — IS ``nn.LayerNorm``.  Third derivatives are not provided."""
+
+    def _declared(self, x) -> bool:
+        ns = tuple(self.normalized_shape)
+        D = 1
+        for v in ns:
+            D *= v
+        if not (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.data_ptr() % 16 == 0 and x.numel() > 0):
+            return False
+        if not (1 <= D <= _LN_MAX_D and x.dim() >= len(ns) and tuple(x.shape[x.dim() - len(ns):]) == ns):
+            return False                  # a shape mismatch: nn.LayerNorm's own error
+        return all(p is None or (p.dtype == torch.float32 and p.is_contiguous() and p.device == x.device) for p in (self.weight, self.bias))
+
+    def forward(self, x):
+        if not torch.is_grad_enabled() or not self._declared(x):
+            return super().forward(x)
+        return _LNForward.apply(x, self.weight, self.bias, list(self.normalized_shape), self.eps)
+
+
+def fuse_layernorm_(module: torch.nn.Module) -> int:
+    """Declare every ``nn.LayerNorm`` of ``module`` (exact class; subclasses are left alone) as :class:`FusedLayerNorm`, in place: same
+    parameters and hooks, only the class changes.  Returns how many layers were declared."""
+    n = 0
+    for m in module.modules():
+        if type(m) is torch.nn.LayerNorm:
+            m.__class__ = FusedLayerNorm
+            n += 1
+    return n
+
+
+def declare_layers_(module: torch.nn.Module, depthwise: bool = False, layernorm: bool = False) -> dict:
+    """Every layer declaration this module offers, in place: ``{"batchnorm": n, "pointwise_conv": m}``, with ``depthwise=True`` also
+    ``"depthwise_conv": k``, and with ``layernorm=True`` also ``"layernorm": l``."""
     out = {"batchnorm": fuse_batchnorm_(module), "pointwise_conv": declare_pointwise_convs_(module)}
     if depthwise:
         out["depthwise_conv"] = declare_depthwise_convs_(module)
+    if layernorm:
+        out["layernorm"] = fuse_layernorm_(module)
     return out

@@ -598,6 +598,37 @@ int bhg_dwconv_backward_vjp(const float* x, const float* w, const float* gy, con
                             int k, int stride, int pad, int dil, float* dx, float* dw, float* dgy, void* ws, size_t ws_bytes,
                             void* stream);
 
+/* ---- layer normalisation inside an opaque Hessian-vector product (csrc/bhg_layernorm.hip) ------------------------------------------------
+ * ATen differentiates native_layer_norm_backward by decomposition, as it does for batch norm: 216 ATen operator calls per nn.LayerNorm
+ * layer and product on a 64 x 768 input.  This entry point is that derivative in at most two launches.  The layer: M rows of D
+ * contiguous fp32 elements, xh = (x - mean) * rstd, y = gamma * xh + beta; its first backward is
+ *     F : (x, gy, gamma) -> (gx, ggamma, gbeta)      g = gamma * gy, gx = rstd * (g - mean_j g - xh * mean_j (g * xh))
+ * and for cotangents a (of gx, shaped like x; may be NULL = zero), b (of ggamma, [D]; may be NULL), c (of gbeta, [D]; may be NULL):
+ *     dx, dgy (shaped like x, overwritten), dgamma ([D], overwritten; may be NULL)  =  d( <a, gx> + <b, ggamma> + <c, gbeta> ) / d(x, gy, gamma)
+ * with mean / rstd ([M], what the forward saved) treated as the functions of x they are.  gamma may be NULL (elementwise_affine =
+ * False: gamma = 1).  Every non-NULL output is overwritten in full (dgamma with zeros when a is absent; with gamma NULL and dgamma
+ * given, dgamma is the derivative at gamma = 1).  1 <= D <= 8192 (a row is held in registers between its row sums and its outputs: x,
+ * gy, a are read once), M >= 1.  x, gy, a, dx, dgy must be 16-byte aligned when D % 4 == 0 (16-byte accesses; scalar accesses otherwise);
+ * mean, rstd, gamma, b, c, dgamma need their natural 4-byte alignment only.
+ * `ws`: bhg_layernorm_ws_bytes(D) bytes of scratch (0 for D outside 1 .. 8192), 8-byte aligned — the per-slice fp64 sums of dgamma, at
+ * most 64 slices of the rows.  Refused with -1 and a message, before any device access: non-positive sizes, D > 8192, NULL x / gy /
+ * mean / rstd / dx / dgy / ws, a workspace that is too small or not 8-byte aligned, a row tensor that is not 16-byte aligned where that
+ * is required.  Deterministic (row sums and dgamma in fp64, fixed order; no atomics), asynchronous on `stream`, no host
+ * synchronisation; 20 algorithmic bytes per element.
+ *
+ * bhg_layernorm_plan is host logic only (no launch, no device access): the geometry the launches take for a shape, from the very
+ * function the launch path calls (closed form: nothing is searched), as one line of `key=value` pairs in buf: vec (4: 16-byte accesses,
+ * D % 4 == 0; 1: scalar), tpr (threads per row, a power of two in [1, 256]), rows (256 / tpr rows side by side: one row group), nv
+ * (vectors per thread and row) and inst (the vectors per thread of the kernel instance that runs: 2, 4, 8 resp. 2, 8, 32), groups (row
+ * groups), gps (row groups per slice), slices (workgroups of the row pass, <= max_slices = 64, none empty: slice s is the rows
+ * [s gps rows, min(M, (s + 1) gps rows))), ws (bytes of the workspace the call writes: slices * D * 8).  A shape that
+ * bhg_layernorm_backward_vjp refuses is refused here with the same message.                                                             */
+size_t bhg_layernorm_ws_bytes(int D);
+int bhg_layernorm_plan(long long M, int D, char* buf, size_t buf_bytes);
+int bhg_layernorm_backward_vjp(const float* x, const float* gy, const float* a, const float* gamma, const float* mean,
+                               const float* rstd, const float* b, const float* c, long long M, int D, float* dx, float* dgy,
+                               float* dgamma, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- finite-difference hypergradient of a ReLU-MLP inner problem (darts, SAMA; csrc/bhg_fd.hip) ------------------------------------
  * betty/hypergradient/darts.py:29-67 (sama.py:25-59 alike) for L_in = (1/B) sum_i s_lam(CE_i.detach()) * CE_i(w) (+ a ridge without lam):
  *   bhg_mlp_fd_forward  evaluates the network y = (... relu(x W_1^T + b_1) ...) W_L^T + b_L at w+ = w + eps v and w- = w+ - 2 eps v and
