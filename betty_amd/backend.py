@@ -495,6 +495,17 @@ def layernorm_plan(M: int, D: int) -> dict:
     return {k: int(v) for k, v in re.findall(r"(\w+)=(-?\d+)", buf.value.decode())}
 
 
+def attention_plan(B: int, H: int, L: int, S: int, d: int, vec_ok: bool = True) -> dict:
+    """What bhg_attention_backward_vjp takes for B x H heads of L queries, S keys and d elements, as a dict: ``vec`` (4: 16-byte accesses —
+    d % 4 == 0 and ``vec_ok``, the caller's statement that every stride is a multiple of 4 —, 1: scalar), ``ps`` / ``pd`` (padded row
+    pitches of the score matrices and the operand slots in the LDS), ``rows``, ``slots``, ``phases``, ``grid`` and ``lds`` (bytes of dynamic
+    LDS, <= ``max_lds``) (include/bhg.h: bhg_attention_plan — host logic only: works on a box without a GPU).  A shape the launch refuses
+    raises."""
+    buf = ctypes.create_string_buffer(256)
+    _native.check(_native.load().bhg_attention_plan(int(B), int(H), int(L), int(S), int(d), 1 if vec_ok else 0, buf, 256), "bhg_attention_plan")
+    return {k: int(v) for k, v in re.findall(r"(\w+)=(-?\d+)", buf.value.decode())}
+
+
 _backend = None
 _override = None
 

@@ -19,11 +19,14 @@ other dtypes, channels-last — it IS ``nn.BatchNorm2d``.  Third derivatives are
 ``PointwiseConv2d`` and ``DepthwiseConv2d`` (further down) declare the other two layers of a DARTS / MobileNet-style block,
 ReLU -> depthwise k x k -> 1 x 1 -> BatchNorm2d; ``declare_layers_(module, depthwise=True)`` applies all three.  ``FusedLayerNorm``
 (at the end) is the same declaration for ``nn.LayerNorm`` — the normalisation of a transformer block;
-``declare_layers_(module, layernorm=True)`` applies it.
+``declare_layers_(module, layernorm=True)`` applies it.  ``scaled_dot_product_attention`` / ``declared_attention()`` (last) declare the
+attention core for short sequences: a function and a context manager, because attention is not a module.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
+import math
 
 import torch
 from torch.autograd.function import once_differentiable
@@ -31,7 +34,8 @@ from torch.autograd.function import once_differentiable
 from . import _native
 
 __all__ = ["FusedBatchNorm2d", "fuse_batchnorm_", "fused_batchnorm_calls", "PointwiseConv2d", "declare_pointwise_convs_", "DepthwiseConv2d",
-           "declare_depthwise_convs_", "depthwise_conv_calls", "FusedLayerNorm", "fuse_layernorm_", "fused_layernorm_calls", "declare_layers_"]
+           "declare_depthwise_convs_", "depthwise_conv_calls", "FusedLayerNorm", "fuse_layernorm_", "fused_layernorm_calls", "declare_layers_",
+           "scaled_dot_product_attention", "declared_attention", "declared_attention_calls"]
 
 _CALLS = {"forward": 0, "backward": 0, "backward_vjp": 0}   # test / measurement hook: which nodes ran
 
@@ -466,3 +470,168 @@ def declare_layers_(module: torch.nn.Module, depthwise: bool = False, layernorm:
     if layernorm:
         out["layernorm"] = fuse_layernorm_(module)
     return out
+
+
+# ---- declared attention: the core of a transformer block, short sequences -------------------------------------------------------------------
+# The fused SDPA kernels have no double backward, and on the math path ATen differentiates bmm -> softmax -> bmm by decomposition, per
+# head batch and per product.  Declared, the forward is the math path on ATen's kernels, the first backward is written out in torch
+# operations, both tied into the graph as two autograd.Function nodes as for layer norm, and the backward OF the backward node is one
+# bhg_attention_backward_vjp call (csrc/bhg_attention.hip): ONE launch, one workgroup per (batch, head), no workspace.
+_ATTN_CALLS = {"forward": 0, "backward": 0, "backward_vjp": 0}   # test / measurement hook: which nodes ran
+_ATTN_MAX = 64                                                   # the family bhg_attention_backward_vjp takes: L, S, d <= 64
+_TORCH_SDPA = torch.nn.functional.scaled_dot_product_attention   # what anything outside the family IS
+
+
+def declared_attention_calls() -> dict:
+    return dict(_ATTN_CALLS)
+
+
+def _attn_vjp_hip(q, k, v, go, aq, ak, av, mask, causal, scale, need):
+    """(dq, dk, dv, dgo) through bhg_attention_backward_vjp; ``need`` says which of the four are wanted (the others are None).  Strided
+    views are handed in as they are.  The product's only implementation: it raises when the HIP extension is missing or the tensors are
+    not on the GPU."""
+    if not q.is_cuda:
+        raise _native.NativeLibraryError("declared attention's double backward needs CUDA/HIP tensors; there is no CPU fallback")
+    lib = _native.load()
+    B, H, L, d = q.shape
+    S = k.shape[2]
+
+    def prep(t, shape):
+        if t is None:
+            return None
+        t = t.detach()
+        if t.dtype != torch.float32:
+            t = t.to(torch.float32)
+        if tuple(t.shape) != shape:
+            t = t.expand(shape)
+        if (d > 1 and t.stride(3) != 1) or t.data_ptr() % 16 != 0:
+            t = t.contiguous() if not t.is_contiguous() else t.clone()
+        return t
+
+    lshape, sshape = (B, H, L, d), (B, H, S, d)
+    ins = [prep(t, sh) for t, sh in zip((q, k, v, go, aq, ak, av), (lshape, sshape, sshape, lshape, lshape, sshape, sshape))]
+    strides = (ctypes.c_longlong * 28)()
+    for i, t in enumerate(ins):
+        if t is not None:
+            strides[4 * i:4 * i + 4] = list(t.stride())
+    mstrides = None
+    if mask is not None:
+        mask = mask.detach()
+        mstrides = (ctypes.c_longlong * 4)(*mask.stride())
+    outs = [torch.empty(sh, dtype=torch.float32, device=q.device) if on else None for on, sh in zip(need, (lshape, sshape, sshape, lshape))]
+    ptr = lambda t: None if t is None else t.data_ptr()   # noqa: E731
+    with torch.cuda.device(q.device):
+        _native.check(
+            lib.bhg_attention_backward_vjp(*(ptr(t) for t in ins), strides, ptr(mask), mstrides, 1 if causal else 0, float(scale), B, H, L, S, d,
+                                           *(ptr(t) for t in outs), _stream()),
+            "bhg_attention_backward_vjp")
+    return tuple(outs)
+
+
+_ATTN_VJP_IMPL = [_attn_vjp_hip]   # TEST HOOK ONLY (tests/test_declared_attention.py swaps in the float64 restatement to check the graph plumbing on CPU)
+
+
+class _AttnBackward(torch.autograd.Function):
+    """(q, k, v, go) -> (gq, gk, gv): attention's first backward as a graph node whose own backward is ONE fused call.  P is what the
+    forward computed; its dependence on q and k is part of the fused call."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, go, P, mask, causal, scale):
+        _ATTN_CALLS["backward"] += 1
+        gP = go @ v.transpose(-1, -2)
+        gS = P * (gP - (P * gP).sum(-1, keepdim=True))
+        gq, gk, gv = (gS @ k) * scale, (gS.transpose(-1, -2) @ q) * scale, P.transpose(-1, -2) @ go
+        ctx.save_for_backward(q, k, v, go, mask)
+        ctx.causal, ctx.scale = causal, scale
+        ctx.set_materialize_grads(False)
+        return gq, gk, gv
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, aq, ak, av):
+        q, k, v, go, mask = ctx.saved_tensors
+        if aq is None and ak is None and av is None:
+            return (None,) * 8
+        _ATTN_CALLS["backward_vjp"] += 1
+        dq, dk, dv, dgo = _ATTN_VJP_IMPL[0](q, k, v, go, aq, ak, av, mask, ctx.causal, ctx.scale, tuple(ctx.needs_input_grad[:4]))
+        return dq, dk, dv, dgo, None, None, None, None
+
+
+class _AttnForward(torch.autograd.Function):
+    """The math-path attention on ATen's own kernels; its backward is the node above (so create_graph=True records THAT node)."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, mask, causal, scale):
+        _ATTN_CALLS["forward"] += 1
+        sc = (q @ k.transpose(-1, -2)) * scale
+        if mask is not None:
+            sc = sc + mask
+        if causal:
+            sc = sc.masked_fill(torch.ones(sc.shape[-2:], dtype=torch.bool, device=sc.device).triu(1), float("-inf"))
+        P = torch.softmax(sc, dim=-1)
+        ctx.save_for_backward(q, k, v, P, mask)
+        ctx.causal, ctx.scale = causal, scale
+        return P @ v
+
+    @staticmethod
+    def backward(ctx, go):
+        q, k, v, P, mask = ctx.saved_tensors
+        gq, gk, gv = _AttnBackward.apply(q, k, v, go, P, mask, ctx.causal, ctx.scale)
+        return gq, gk, gv, None, None, None
+
+
+def _declared_mask(q, k, v, attn_mask, dropout_p, is_causal, kw):
+    """False when the call is outside the declared family; otherwise the additive fp32 mask as a (B, H, L, S) view, or None."""
+    if kw.pop("enable_gqa", False) or kw:
+        return False
+    if not (torch.is_grad_enabled() and dropout_p == 0.0 and all(torch.is_tensor(t) for t in (q, k, v))):
+        return False
+    if not all(t.is_cuda and t.dtype == torch.float32 and t.dim() == 4 and t.device == q.device and not t.is_nested for t in (q, k, v)):
+        return False
+    B, H, L, d = q.shape
+    S = k.shape[2]
+    if not (tuple(k.shape) == (B, H, S, d) and tuple(v.shape) == (B, H, S, d) and B >= 1 and H >= 1 and B * H < 2 ** 31):
+        return False
+    if not (1 <= L <= _ATTN_MAX and 1 <= S <= _ATTN_MAX and 1 <= d <= _ATTN_MAX):
+        return False
+    if d > 1 and not all(t.stride(3) == 1 for t in (q, k, v)):
+        return False
+    if attn_mask is None:
+        return None
+    if is_causal or not torch.is_tensor(attn_mask) or attn_mask.requires_grad or attn_mask.device != q.device or attn_mask.dim() > 4:
+        return False   # (a mask AND is_causal: the torch function's own error)
+    if attn_mask.dtype == torch.bool:
+        attn_mask = torch.zeros(attn_mask.shape, dtype=torch.float32, device=q.device).masked_fill_(~attn_mask, float("-inf"))   # once
+    elif attn_mask.dtype != torch.float32:
+        return False
+    try:
+        return attn_mask.expand(B, H, L, S)
+    except RuntimeError:
+        return False
+
+
+def scaled_dot_product_attention(query, key, value, attn_mask=None, dropout_p=0.0, is_causal=False, scale=None, **kw):
+    """``torch.nn.functional.scaled_dot_product_attention`` whose double backward is fused (comment above), for CUDA fp32 4-D inputs with
+    a unit last stride, at most 64 queries, 64 keys and 64 elements per head, grad enabled, no dropout, no ``enable_gqa``, and a mask
+    that is absent, bool or fp32 and does not require grad.  Anything else IS the torch function with the caller's arguments, errors
+    included.  Third derivatives are not provided."""
+    mask = _declared_mask(query, key, value, attn_mask, dropout_p, is_causal, dict(kw))
+    if mask is False:
+        return _TORCH_SDPA(query, key, value, attn_mask=attn_mask, dropout_p=dropout_p, is_causal=is_causal, scale=scale, **kw)
+    s = 1.0 / math.sqrt(query.shape[-1]) if scale is None else float(scale)
+    return _AttnForward.apply(query, key, value, mask, bool(is_causal), s)
+
+
+@contextlib.contextmanager
+def declared_attention():
+    """Inside the context ``torch.nn.functional.scaled_dot_product_attention`` is the function above: ``nn.MultiheadAttention``,
+    ``nn.TransformerEncoder`` and model code that calls the torch function reach the declaration without being rewritten, and
+    ``sdpa_kernel(MATH)`` is not needed for shapes in the family.  Only the forward that records the graph has to run inside; the
+    solve's double backward runs wherever it runs.  Restored on exit, exceptions included; nesting is safe."""
+    F = torch.nn.functional
+    previous = F.scaled_dot_product_attention
+    F.scaled_dot_product_attention = scaled_dot_product_attention
+    try:
+        yield
+    finally:
+        F.scaled_dot_product_attention = previous

@@ -629,6 +629,43 @@ int bhg_layernorm_backward_vjp(const float* x, const float* gy, const float* a, 
                                const float* rstd, const float* b, const float* c, long long M, int D, float* dx, float* dgy,
                                float* dgamma, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- the attention core inside an opaque Hessian-vector product, short sequences (csrc/bhg_attention.hip) -----------------------------
+ * The fused SDPA kernels have no double backward; on the math path ATen differentiates bmm -> softmax -> bmm by decomposition.  This
+ * entry point is the vector-Jacobian product of attention's first backward in ONE launch with no workspace: one workgroup of 256 threads
+ * per (batch, head), everything in the LDS of its CU.  Per (b, h): Q, gO, aQ are L x d, K, V, aK, aV are S x d, m an additive L x S mask
+ * that is not differentiated, s = scale:
+ *     P = softmax_rows(s Q K^T + m)     gP = gO V^T     D = rowsum(P * gP)     gS = P * (gP - D)
+ *     first backward  F : (Q, K, V, gO) -> (gQ, gK, gV) = (s gS K, s gS^T Q, P^T gO)
+ * and for cotangents aq, ak, av of gQ, gK, gV (each may be NULL = zero, not all three):
+ *     dq, dk, dv, dgo  =  d( <aq, gQ> + <ak, gK> + <av, gV> ) / d(q, k, v, go)
+ *     T = s (aQ K^T + Q aK^T)   E = rowsum(P * T)   bgP = P * (T - E)   bP = T * (gP - D) - gP * E + gO aV^T   bS = P * (bP - rowsum(P * bP))
+ *     dgO = bgP V + P aV        dV = bgP^T gO       dQ = s (bS K + gS aK)       dK = s (bS^T Q + gS^T aQ)
+ * (float64 restatement held to autograd: tests/attention_ref.py).
+ * Inputs q, k, v, go, aq, ak, av: fp32, logical shape (B, H, L | S, d).  `strides` is a HOST array of 7 x 4 element strides in that order
+ * (batch, head, row, last), read before the launch; the last stride must be 1, the others may be anything >= 0 (transposed and
+ * broadcast views are read in place; the entries of a NULL input are ignored, and a stride whose extent is 1 is ignored).  `mask`: NULL,
+ * or fp32 additive with the four HOST element strides `mask_strides` (batch, head, row, column), any of which may be 0: a (B, 1, 1, S)
+ * key-padding mask is read in place.  -inf entries are allowed; a fully masked row gives NaN, as on the math path.  `causal` != 0 masks
+ * j > i as well.  Outputs dq, dgo (B, H, L, d) and dk, dv (B, H, S, d): contiguous, each may be NULL (its products are skipped, not all
+ * four); every non-NULL output is overwritten in full.
+ * Family: 1 <= L, S, d <= 64; B, H >= 1.  vec = 4 (16-byte accesses) when d % 4 == 0 and every batch / head / row stride of a given input
+ * is a multiple of 4 — all eleven pointers must then be 16-byte aligned; otherwise every access is scalar.
+ * Refused with -1 and a message, before any device access: sizes <= 0; L, S or d above 64; NULL q / k / v / go / strides; all three
+ * cotangents NULL; all four outputs NULL; a last stride other than 1; a negative stride; a pointer that is not 16-byte aligned on the
+ * vector path.  Products in fp32 with explicit fused multiply-adds, the softmax denominator and the three row sums in fp64, the row
+ * maximum subtracted before exp.  Deterministic (no atomics), asynchronous on `stream`, no host synchronisation.
+ *
+ * bhg_attention_plan is host logic only (no launch, no device access): what the launch takes for a shape, from the very function the
+ * launch path calls, as one line of `key=value` pairs in buf: vec (4 when d % 4 == 0 and vec_ok != 0 — the caller's statement that the
+ * strides are multiples of 4 —, else 1), ps and pd (row pitches, in floats, of the four L x S score matrices and of the operand slots,
+ * padded against bank conflicts), rows (rows of a slot: max(L, S)), slots (4) and phases (5: the seven operands are staged through the
+ * slots, never all held), grid (B H), lds (bytes of dynamic LDS: 4 (4 L ps + 4 rows pd) <= max_lds = 163840).  A shape that
+ * bhg_attention_backward_vjp refuses is refused here with the same message.                                                              */
+int bhg_attention_plan(int B, int H, int L, int S, int d, int vec_ok, char* buf, size_t buf_bytes);
+int bhg_attention_backward_vjp(const float* q, const float* k, const float* v, const float* go, const float* aq, const float* ak,
+                               const float* av, const long long* strides, const float* mask, const long long* mask_strides, int causal,
+                               float scale, int B, int H, int L, int S, int d, float* dq, float* dk, float* dv, float* dgo, void* stream);
+
 /* ---- finite-difference hypergradient of a ReLU-MLP inner problem (darts, SAMA; csrc/bhg_fd.hip) ------------------------------------
  * betty/hypergradient/darts.py:29-67 (sama.py:25-59 alike) for L_in = (1/B) sum_i s_lam(CE_i.detach()) * CE_i(w) (+ a ridge without lam):
  *   bhg_mlp_fd_forward  evaluates the network y = (... relu(x W_1^T + b_1) ...) W_L^T + b_L at w+ = w + eps v and w- = w+ - 2 eps v and
