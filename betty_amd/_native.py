@@ -264,6 +264,14 @@ SYMBOLS = {
         [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(ctypes.c_longlong), c_void_p,
          POINTER(ctypes.c_longlong), c_int, c_float, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     ),
+    "bhg_attention_tiled_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "bhg_attention_tiled_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_char_p, c_size_t]),
+    "bhg_attention_tiled_backward_vjp": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(ctypes.c_longlong), c_void_p,
+         POINTER(ctypes.c_longlong), c_int, c_float, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+         c_size_t, c_void_p],
+    ),
 }
 
 _libs = {}          # path -> bound CDLL

@@ -506,6 +506,18 @@ def attention_plan(B: int, H: int, L: int, S: int, d: int, vec_ok: bool = True) 
     return {k: int(v) for k, v in re.findall(r"(\w+)=(-?\d+)", buf.value.decode())}
 
 
+def attention_tiled_plan(B: int, H: int, L: int, S: int, d: int, vec_ok: bool = True) -> dict:
+    """What bhg_attention_tiled_backward_vjp takes for B x H heads of L <= 512 queries, S <= 512 keys and d <= 64 elements, as a dict:
+    ``vec``, ``bm`` x ``bn`` (queries x keys of a score tile), ``dp`` (d rounded up to 16), ``pd`` / ``ps`` (row pitches of operand and
+    score tiles in the LDS), ``grid_q`` / ``grid_k`` and ``lds_q`` / ``lds_k`` (workgroups and bytes of dynamic LDS of the two launches,
+    <= ``max_lds``) and ``ws`` (bytes of workspace) (include/bhg.h: bhg_attention_tiled_plan — host logic only).  A shape the launch
+    refuses raises."""
+    buf = ctypes.create_string_buffer(256)
+    _native.check(_native.load().bhg_attention_tiled_plan(int(B), int(H), int(L), int(S), int(d), 1 if vec_ok else 0, buf, 256),
+                  "bhg_attention_tiled_plan")
+    return {k: int(v) for k, v in re.findall(r"(\w+)=(-?\d+)", buf.value.decode())}
+
+
 _backend = None
 _override = None
 

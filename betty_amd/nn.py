@@ -20,7 +20,8 @@ other dtypes, channels-last — it IS ``nn.BatchNorm2d``.  Third derivatives are
 ReLU -> depthwise k x k -> 1 x 1 -> BatchNorm2d; ``declare_layers_(module, depthwise=True)`` applies all three.  ``FusedLayerNorm``
 (at the end) is the same declaration for ``nn.LayerNorm`` — the normalisation of a transformer block;
 ``declare_layers_(module, layernorm=True)`` applies it.  ``scaled_dot_product_attention`` / ``declared_attention()`` (last) declare the
-attention core for short sequences: a function and a context manager, because attention is not a module.
+attention core for short sequences: a function and a context manager, because attention is not a module;
+``tiled_scaled_dot_product_attention`` / ``declared_attention(tiled=True)`` extend it to 512 tokens (opt-in).
 """
 from __future__ import annotations
 
@@ -35,7 +36,8 @@ from . import _native
 
 __all__ = ["FusedBatchNorm2d", "fuse_batchnorm_", "fused_batchnorm_calls", "PointwiseConv2d", "declare_pointwise_convs_", "DepthwiseConv2d",
            "declare_depthwise_convs_", "depthwise_conv_calls", "FusedLayerNorm", "fuse_layernorm_", "fused_layernorm_calls", "declare_layers_",
-           "scaled_dot_product_attention", "declared_attention", "declared_attention_calls"]
+           "scaled_dot_product_attention", "declared_attention", "declared_attention_calls", "tiled_scaled_dot_product_attention",
+           "declared_attention_tiled_calls"]
 
 _CALLS = {"forward": 0, "backward": 0, "backward_vjp": 0}   # test / measurement hook: which nodes ran
 
@@ -486,10 +488,30 @@ def declared_attention_calls() -> dict:
     return dict(_ATTN_CALLS)
 
 
+_ATTN_TILED_WS = {}   # (device, stream) -> the tiled kernels' row statistics
+
+
+def _attn_tiled_workspace(device, n):
+    key = (str(device), int(torch.cuda.current_stream(device).cuda_stream))
+    ws = _ATTN_TILED_WS.get(key)
+    if ws is None or ws.numel() < n:
+        ws = _ATTN_TILED_WS[key] = torch.empty(max(n, 1 << 16), dtype=torch.uint8, device=device)
+    return ws
+
+
 def _attn_vjp_hip(q, k, v, go, aq, ak, av, mask, causal, scale, need):
     """(dq, dk, dv, dgo) through bhg_attention_backward_vjp; ``need`` says which of the four are wanted (the others are None).  Strided
     views are handed in as they are.  The product's only implementation: it raises when the HIP extension is missing or the tensors are
     not on the GPU."""
+    return _attn_vjp_launch(q, k, v, go, aq, ak, av, mask, causal, scale, need, False)
+
+
+def _attn_tiled_vjp_hip(q, k, v, go, aq, ak, av, mask, causal, scale, need):
+    """The same through bhg_attention_tiled_backward_vjp (L, S <= 512): two launches and a workspace cached per (device, stream)."""
+    return _attn_vjp_launch(q, k, v, go, aq, ak, av, mask, causal, scale, need, True)
+
+
+def _attn_vjp_launch(q, k, v, go, aq, ak, av, mask, causal, scale, need, tiled):
     if not q.is_cuda:
         raise _native.NativeLibraryError("declared attention's double backward needs CUDA/HIP tensors; there is no CPU fallback")
     lib = _native.load()
@@ -521,14 +543,54 @@ def _attn_vjp_hip(q, k, v, go, aq, ak, av, mask, causal, scale, need):
     outs = [torch.empty(sh, dtype=torch.float32, device=q.device) if on else None for on, sh in zip(need, (lshape, sshape, sshape, lshape))]
     ptr = lambda t: None if t is None else t.data_ptr()   # noqa: E731
     with torch.cuda.device(q.device):
-        _native.check(
-            lib.bhg_attention_backward_vjp(*(ptr(t) for t in ins), strides, ptr(mask), mstrides, 1 if causal else 0, float(scale), B, H, L, S, d,
-                                           *(ptr(t) for t in outs), _stream()),
-            "bhg_attention_backward_vjp")
+        if tiled:
+            ws = _attn_tiled_workspace(q.device, int(lib.bhg_attention_tiled_ws_bytes(B, H, L)))
+            _native.check(
+                lib.bhg_attention_tiled_backward_vjp(*(ptr(t) for t in ins), strides, ptr(mask), mstrides, 1 if causal else 0, float(scale),
+                                                     B, H, L, S, d, *(ptr(t) for t in outs), ws.data_ptr(), ws.numel(), _stream()),
+                "bhg_attention_tiled_backward_vjp")
+        else:
+            _native.check(
+                lib.bhg_attention_backward_vjp(*(ptr(t) for t in ins), strides, ptr(mask), mstrides, 1 if causal else 0, float(scale), B, H, L,
+                                               S, d, *(ptr(t) for t in outs), _stream()),
+                "bhg_attention_backward_vjp")
     return tuple(outs)
 
 
 _ATTN_VJP_IMPL = [_attn_vjp_hip]   # TEST HOOK ONLY (tests/test_declared_attention.py swaps in the float64 restatement to check the graph plumbing on CPU)
+
+
+def _attn_first_backward(ctx, calls, q, k, v, go, P, mask, causal, scale):
+    calls["backward"] += 1
+    gP = go @ v.transpose(-1, -2)
+    gS = P * (gP - (P * gP).sum(-1, keepdim=True))
+    gq, gk, gv = (gS @ k) * scale, (gS.transpose(-1, -2) @ q) * scale, P.transpose(-1, -2) @ go
+    ctx.save_for_backward(q, k, v, go, mask)
+    ctx.causal, ctx.scale = causal, scale
+    ctx.set_materialize_grads(False)
+    return gq, gk, gv
+
+
+def _attn_double_backward(ctx, calls, impl, aq, ak, av):
+    q, k, v, go, mask = ctx.saved_tensors
+    if aq is None and ak is None and av is None:
+        return (None,) * 8
+    calls["backward_vjp"] += 1
+    dq, dk, dv, dgo = impl[0](q, k, v, go, aq, ak, av, mask, ctx.causal, ctx.scale, tuple(ctx.needs_input_grad[:4]))
+    return dq, dk, dv, dgo, None, None, None, None
+
+
+def _attn_forward(ctx, calls, q, k, v, mask, causal, scale):
+    calls["forward"] += 1
+    sc = (q @ k.transpose(-1, -2)) * scale
+    if mask is not None:
+        sc = sc + mask
+    if causal:
+        sc = sc.masked_fill(torch.ones(sc.shape[-2:], dtype=torch.bool, device=sc.device).triu(1), float("-inf"))
+    P = torch.softmax(sc, dim=-1)
+    ctx.save_for_backward(q, k, v, P, mask)
+    ctx.causal, ctx.scale = causal, scale
+    return P @ v
 
 
 class _AttnBackward(torch.autograd.Function):
@@ -537,24 +599,12 @@ class _AttnBackward(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, q, k, v, go, P, mask, causal, scale):
-        _ATTN_CALLS["backward"] += 1
-        gP = go @ v.transpose(-1, -2)
-        gS = P * (gP - (P * gP).sum(-1, keepdim=True))
-        gq, gk, gv = (gS @ k) * scale, (gS.transpose(-1, -2) @ q) * scale, P.transpose(-1, -2) @ go
-        ctx.save_for_backward(q, k, v, go, mask)
-        ctx.causal, ctx.scale = causal, scale
-        ctx.set_materialize_grads(False)
-        return gq, gk, gv
+        return _attn_first_backward(ctx, _ATTN_CALLS, q, k, v, go, P, mask, causal, scale)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, aq, ak, av):
-        q, k, v, go, mask = ctx.saved_tensors
-        if aq is None and ak is None and av is None:
-            return (None,) * 8
-        _ATTN_CALLS["backward_vjp"] += 1
-        dq, dk, dv, dgo = _ATTN_VJP_IMPL[0](q, k, v, go, aq, ak, av, mask, ctx.causal, ctx.scale, tuple(ctx.needs_input_grad[:4]))
-        return dq, dk, dv, dgo, None, None, None, None
+        return _attn_double_backward(ctx, _ATTN_CALLS, _ATTN_VJP_IMPL, aq, ak, av)
 
 
 class _AttnForward(torch.autograd.Function):
@@ -562,16 +612,7 @@ class _AttnForward(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, q, k, v, mask, causal, scale):
-        _ATTN_CALLS["forward"] += 1
-        sc = (q @ k.transpose(-1, -2)) * scale
-        if mask is not None:
-            sc = sc + mask
-        if causal:
-            sc = sc.masked_fill(torch.ones(sc.shape[-2:], dtype=torch.bool, device=sc.device).triu(1), float("-inf"))
-        P = torch.softmax(sc, dim=-1)
-        ctx.save_for_backward(q, k, v, P, mask)
-        ctx.causal, ctx.scale = causal, scale
-        return P @ v
+        return _attn_forward(ctx, _ATTN_CALLS, q, k, v, mask, causal, scale)
 
     @staticmethod
     def backward(ctx, go):
@@ -580,8 +621,44 @@ class _AttnForward(torch.autograd.Function):
         return gq, gk, gv, None, None, None
 
 
-def _declared_mask(q, k, v, attn_mask, dropout_p, is_causal, kw):
-    """False when the call is outside the declared family; otherwise the additive fp32 mask as a (B, H, L, S) view, or None."""
+# Beyond 64 tokens (opt-in): the same two nodes, counted apart, whose double backward is ONE bhg_attention_tiled_backward_vjp call
+# (csrc/bhg_attention_tiled.hip: two launches over 64 x 32 score tiles and a workspace for the row statistics).  The forward still
+# materialises and saves P.
+_ATTN_TILED_CALLS = {"forward": 0, "backward": 0, "backward_vjp": 0}
+_ATTN_TILED_MAX = 512   # the largest measured length up to which no measured shape is slower declared (profiles/attention_tiled_double_backward.txt)
+_ATTN_TILED_VJP_IMPL = [_attn_tiled_vjp_hip]   # TEST HOOK ONLY (tests/test_declared_attention_tiled.py swaps in the float64 restatement)
+
+
+def declared_attention_tiled_calls() -> dict:
+    return dict(_ATTN_TILED_CALLS)
+
+
+class _AttnTiledBackward(_AttnBackward):
+    @staticmethod
+    def forward(ctx, q, k, v, go, P, mask, causal, scale):
+        return _attn_first_backward(ctx, _ATTN_TILED_CALLS, q, k, v, go, P, mask, causal, scale)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, aq, ak, av):
+        return _attn_double_backward(ctx, _ATTN_TILED_CALLS, _ATTN_TILED_VJP_IMPL, aq, ak, av)
+
+
+class _AttnTiledForward(_AttnForward):
+    @staticmethod
+    def forward(ctx, q, k, v, mask, causal, scale):
+        return _attn_forward(ctx, _ATTN_TILED_CALLS, q, k, v, mask, causal, scale)
+
+    @staticmethod
+    def backward(ctx, go):
+        q, k, v, P, mask = ctx.saved_tensors
+        gq, gk, gv = _AttnTiledBackward.apply(q, k, v, go, P, mask, ctx.causal, ctx.scale)
+        return gq, gk, gv, None, None, None
+
+
+def _declared_mask(q, k, v, attn_mask, dropout_p, is_causal, kw, max_len=_ATTN_MAX):
+    """False when the call is outside the declared family (at most ``max_len`` queries and keys); otherwise the additive fp32 mask as a
+    (B, H, L, S) view, or None."""
     if kw.pop("enable_gqa", False) or kw:
         return False
     if not (torch.is_grad_enabled() and dropout_p == 0.0 and all(torch.is_tensor(t) for t in (q, k, v))):
@@ -592,7 +669,7 @@ def _declared_mask(q, k, v, attn_mask, dropout_p, is_causal, kw):
     S = k.shape[2]
     if not (tuple(k.shape) == (B, H, S, d) and tuple(v.shape) == (B, H, S, d) and B >= 1 and H >= 1 and B * H < 2 ** 31):
         return False
-    if not (1 <= L <= _ATTN_MAX and 1 <= S <= _ATTN_MAX and 1 <= d <= _ATTN_MAX):
+    if not (1 <= L <= max_len and 1 <= S <= max_len and 1 <= d <= _ATTN_MAX):
         return False
     if d > 1 and not all(t.stride(3) == 1 for t in (q, k, v)):
         return False
@@ -622,15 +699,29 @@ def scaled_dot_product_attention(query, key, value, attn_mask=None, dropout_p=0.
     return _AttnForward.apply(query, key, value, mask, bool(is_causal), s)
 
 
+def tiled_scaled_dot_product_attention(query, key, value, attn_mask=None, dropout_p=0.0, is_causal=False, scale=None, **kw):
+    """``scaled_dot_product_attention`` above, whose declared family also takes more than 64 and at most ``_ATTN_TILED_MAX`` queries and
+    keys (d <= 64 and every other condition as above).  With at most 64 of both it IS the function above: the same nodes, the same
+    counters.  Longer, the double backward is one bhg_attention_tiled_backward_vjp call, counted by ``declared_attention_tiled_calls()``.
+    Anything else IS the torch function with the caller's arguments, errors included."""
+    mask = _declared_mask(query, key, value, attn_mask, dropout_p, is_causal, dict(kw), max(_ATTN_MAX, _ATTN_TILED_MAX))
+    if mask is False:
+        return _TORCH_SDPA(query, key, value, attn_mask=attn_mask, dropout_p=dropout_p, is_causal=is_causal, scale=scale, **kw)
+    s = 1.0 / math.sqrt(query.shape[-1]) if scale is None else float(scale)
+    node = _AttnForward if max(query.shape[2], key.shape[2]) <= _ATTN_MAX else _AttnTiledForward
+    return node.apply(query, key, value, mask, bool(is_causal), s)
+
+
 @contextlib.contextmanager
-def declared_attention():
+def declared_attention(tiled: bool = False):
     """Inside the context ``torch.nn.functional.scaled_dot_product_attention`` is the function above: ``nn.MultiheadAttention``,
     ``nn.TransformerEncoder`` and model code that calls the torch function reach the declaration without being rewritten, and
-    ``sdpa_kernel(MATH)`` is not needed for shapes in the family.  Only the forward that records the graph has to run inside; the
+    ``sdpa_kernel(MATH)`` is not needed for shapes in the family.  ``tiled=True`` installs ``tiled_scaled_dot_product_attention``
+    instead (sequences of up to ``_ATTN_TILED_MAX`` tokens).  Only the forward that records the graph has to run inside; the
     solve's double backward runs wherever it runs.  Restored on exit, exceptions included; nesting is safe."""
     F = torch.nn.functional
     previous = F.scaled_dot_product_attention
-    F.scaled_dot_product_attention = scaled_dot_product_attention
+    F.scaled_dot_product_attention = tiled_scaled_dot_product_attention if tiled else scaled_dot_product_attention
     try:
         yield
     finally:

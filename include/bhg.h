@@ -666,6 +666,37 @@ int bhg_attention_backward_vjp(const float* q, const float* k, const float* v, c
                                const float* av, const long long* strides, const float* mask, const long long* mask_strides, int causal,
                                float scale, int B, int H, int L, int S, int d, float* dq, float* dk, float* dv, float* dgo, void* stream);
 
+/* ---- the attention core beyond 64 tokens: the tiled sibling (csrc/bhg_attention_tiled.hip) ---------------------------------------------
+ * The same vector-Jacobian product, the same quantities and the same arguments as bhg_attention_backward_vjp, plus a workspace, for
+ * 1 <= L, S <= 512 and 1 <= d <= 64.  The score matrices exist one 64 x 32 tile (bm queries x bn keys) at a time.  TWO launches:
+ *   1  grid B H ceil(L / 64), 64 query rows per workgroup: (a) ONE online pass over the key tiles (running row maximum, the sums rescaled
+ *      by exp(m_old - m_new)) gives the row maximum m, the softmax denominator l, D = rowsum(P * gP), E = rowsum(P * T) and
+ *      R = rowsum(P * bP) = rowsum(P * T * gP) - 2 D E + rowsum(P * (gO aV^T)); (b) a second sweep accumulates dq and dgo (skipped when
+ *      both are NULL);
+ *   2  grid B H ceil(S / 32), 32 keys per workgroup: sweeps the query tiles with the statistics of launch 1 and accumulates dk and dv
+ *      (not launched when both are NULL).
+ * Under `causal` the tiles wholly above the diagonal are skipped.  A key tile that is masked out entirely does not disturb rows with
+ * live keys elsewhere; a fully masked row gives NaN, as on the math path.  Every product on the fp32-input MFMA (exact fp32); the five
+ * row statistics accumulate in fp64.  No atomics, no grid barrier: deterministic.  Asynchronous on `stream`, no host synchronisation.
+ * Workspace `ws`: bhg_attention_tiled_ws_bytes(B, H, L) bytes, 8-byte aligned, written by launch 1 and read by launch 2 — the row
+ * statistics only: (B, H, L) rows of five doubles [m, l, D, E, R], 40 bytes per query row (0 for sizes <= 0).  Nothing is kept between calls.
+ * Refused with -1 and a message, before any device access: everything bhg_attention_backward_vjp refuses (with its words, except that
+ * the limits are 512 queries, 512 keys, 64 elements per head), a NULL, short or misaligned workspace, and a grid of more than 2^31 - 1
+ * workgroups.  (The HIP runtime itself rejects a launch of 2^24 or more workgroups of 256 threads — gridDim.x * blockDim.x >= 2^32; such a
+ * shape passes the plan and fails at the launch with -1 and the runtime's error, without a fault.)
+ *
+ * bhg_attention_tiled_plan is host logic only, answered by the very function the launch calls, one line of `key=value` pairs: vec (as
+ * for the sibling: 16-byte global reads or scalar ones; the LDS image is the same), bm = 64, bn = 32, dp (d rounded up to 16: operand
+ * tiles are zero-padded to it), pd = dp + 4 and ps = 36 (row pitches, in floats, of operand and score tiles), grid_q and grid_k, lds_q =
+ * 4 ((3 bm + 4 bn) pd + 4 bm ps) and lds_k = 4 ((3 bm + 4 bn) pd + 3 bm ps) (bytes of dynamic LDS of the two launches, <= max_lds =
+ * 163840), ws (bytes).                                                                                                                    */
+size_t bhg_attention_tiled_ws_bytes(int B, int H, int L);
+int bhg_attention_tiled_plan(int B, int H, int L, int S, int d, int vec_ok, char* buf, size_t buf_bytes);
+int bhg_attention_tiled_backward_vjp(const float* q, const float* k, const float* v, const float* go, const float* aq, const float* ak,
+                                     const float* av, const long long* strides, const float* mask, const long long* mask_strides,
+                                     int causal, float scale, int B, int H, int L, int S, int d, float* dq, float* dk, float* dv,
+                                     float* dgo, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- finite-difference hypergradient of a ReLU-MLP inner problem (darts, SAMA; csrc/bhg_fd.hip) ------------------------------------
  * betty/hypergradient/darts.py:29-67 (sama.py:25-59 alike) for L_in = (1/B) sum_i s_lam(CE_i.detach()) * CE_i(w) (+ a ridge without lam):
  *   bhg_mlp_fd_forward  evaluates the network y = (... relu(x W_1^T + b_1) ...) W_L^T + b_L at w+ = w + eps v and w- = w+ - 2 eps v and
