@@ -205,6 +205,7 @@ SYMBOLS = {
     "bhg_mlp_cg_mixed_coeff": (c_int, [POINTER(Mlp), c_void_p, c_void_p, c_float, c_void_p, c_size_t, c_void_p]),
     "bhg_mlp_timeout_flag_dev": (c_void_p, [POINTER(Mlp), c_void_p]),
     "bhg_mlp_head_j_dev": (c_void_p, [POINTER(Mlp), c_void_p, POINTER(c_int), POINTER(c_int)]),
+    "bhg_mlp_head_j_t2h_dev": (c_void_p, [POINTER(Mlp), c_void_p, POINTER(c_int)]),
     "bhg_mlp_stage_batch": (c_int, [POINTER(Mlp), c_void_p, c_void_p, c_void_p, c_void_p]),
     "bhg_mlp_supports_packed_prepare": (c_int, [POINTER(Mlp)]),
     "bhg_mlp_forward_packed": (c_int, [POINTER(Mlp), _PP, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),

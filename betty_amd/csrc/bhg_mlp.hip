@@ -596,6 +596,9 @@ struct FusedWs {
   // head_j (bhg_mlp_headj.hpp): J = W_3 diag(mask_2) W_2 per sample, [round32(Bp C)][d_2], built once per solve from the packed
   // operand hj_Ap [d_3 / 16][round32(B C)][16]; nT2j: T2h partials of the head launch's tiles, appended to partT2 (0: the form cannot apply)
   float* hj_J; float* hj_Ap; int nT2j;
+  // ... with 16 x 16 tiles T2h arrives by pairs of tiles instead: two buffers of Bp doubles, one per iteration parity (adjacent: one
+  // memset clears both, once per solve); the tiles of iteration k add into hj_t2h[k & 1], its head rows clear the other one
+  double* hj_t2h[2];
   size_t bytes;
 };
 // The shapes the head_j form takes — where lin_head applies (plan_solve adds the solver's own conditions): L = 4, <= 12 classes, last
@@ -604,6 +607,12 @@ inline bool headj_shape_ok(const bhg_mlp* m, const HoistPlan& hp) {
   return hp.ok && hp.lin_ok && m->L == 4 && m->dims[m->L] <= 12 && m->dims[m->L - 1] <= 512 && m->Bp == 128;
 }
 inline int headj_rows(int rows_valid, int C) { return (rows_valid * C + 31) & ~31; }
+// The tiles' shape in the head launch (headj_tile_shape: 16 x 16 where their pairs fit the B slots of T2h, else 32 x 16).  Key
+// head_j_tile: 0 / 1 force the coarser shapes; 2, the default, is the plan's choice — which falls back to 32 x 16 by itself.
+inline int head_j_tile(const bhg_mlp* m) {
+  const int want = dbg(DBG_head_j_tile, 2);
+  return (want == 0 || want == 1) ? want : headj_tile_shape(m->Bp, m->dims[m->L - 1], m->B);
+}
 void carve_fused_ws(const bhg_mlp* m, void* base, FusedWs* w) {
   memset(w, 0, sizeof(*w));
   const bool head = use_head(m);
@@ -653,6 +662,8 @@ void carve_fused_ws(const bhg_mlp* m, void* base, FusedWs* w) {
     const size_t rj = (size_t)headj_rows(m->Bp, m->dims[m->L]);
     w->hj_J = static_cast<float*>(take(sizeof(float) * rj * m->dims[m->L - 2]));
     w->hj_Ap = static_cast<float*>(take(sizeof(float) * rj * m->dims[m->L - 1]));
+    w->hj_t2h[0] = static_cast<double*>(take(sizeof(double) * 2 * m->Bp));
+    w->hj_t2h[1] = w->hj_t2h[0] ? w->hj_t2h[0] + m->Bp : nullptr;
   }
   w->bytes = off;
 }
@@ -708,6 +719,8 @@ int build_head_j(const bhg_mlp* m, const FusedWs& w, hipStream_t st) {
   wb.add(q);
   wb.launch(st);
   BHG_HIP_CHECK(hipGetLastError());
+  // both parities of the pair slots of T2h start a solve at zero (bhg_mlp_headj.hpp: t2pair)
+  if (head_j_tile(m) == 2) BHG_HIP_CHECK(hipMemsetAsync(w.hj_t2h[0], 0, sizeof(double) * 2 * m->Bp, st));
   return BHG_OK;
 }
 
@@ -1044,10 +1057,14 @@ int hoist_head(const bhg_mlp* m, const void* const* dir, const ChainMode& cm, co
     a.Rh1p = cm.ws->Rhp[l - 2]; a.W2p = cm.ws->Wf[l - 1]; a.rh_out = m->Rh[l - 1];
     // T2h partials, one per tile: where the head rows' went (partT2h, B slots summed) when they fit — the step length's one-round-trip
     // form takes a bounded number of T2 partials (alpha_begin) — else behind the layers' own in partT2
-    a.tile_shape = dbg(DBG_head_j_tile, kHeadjTile);
+    // 16 x 16 tiles: one slot per pair of tiles in the buffer of this iteration's parity (B slots summed; at most B pairs)
+    a.tile_shape = head_j_tile(m);
+    a.stages4 = dbg(DBG_head_j_stages4, 0); a.tiles_first = dbg(DBG_head_j_tiles_first, 1);
     const int nt = headj_tiles(Bp, K, a.tile_shape);
-    if (nt <= B) { a.partT2 = cm.ws->partT2h; a.t2n = B; cs->head_j_nt = 0; }
-    else { a.partT2 = cm.ws->partT2 + cm.ws->nT2; a.t2n = nt; cs->head_j_nt = nt; }
+    a.partT2 = cm.ws->partT2 + cm.ws->nT2; a.t2n = nt;   // (shape 2 writes none of them)
+    if (a.tile_shape == 2) { a.t2pair = cm.ws->hj_t2h[cm.kpar]; a.t2clear = cm.ws->hj_t2h[cm.kpar ^ 1]; cs->head_j_nt = 0; cs->head_j_t2h = a.t2pair; }
+    else if (nt <= B) { a.partT2 = cm.ws->partT2h; a.t2n = B; cs->head_j_nt = 0; }
+    else cs->head_j_nt = nt;
     a.ps = &cs->lin_ps; a.ps_bytes = sizeof(cs->lin_ps); a.nu = cs->lin_ps.h.update_blocks;
     if (int rc = launch_headj(a, st)) return rc;
     cs->lin_update_pending = false;
@@ -1640,6 +1657,7 @@ int run_chain(const bhg_mlp* m, const void* const* dir, const ChainMode& cm, hip
     od.aa.partT2h = nullptr;
     od.aa.nT2 = cm.ws->nT2 + cs.head_j_nt;
   }
+  if (cs.head_j && cs.head_j_t2h) od.aa.partT2h = cs.head_j_t2h;   // ... or by pairs of 16 x 16 tiles in this parity's B slots
   if (pl.do_chain && !pl.hp)
     if (int rc = chain_backward(m, dir, cm, pl, st)) return rc;
 
@@ -1768,6 +1786,15 @@ const float* bhg_mlp_head_j_dev(const bhg_mlp* m, void* fws, int* rows, int* col
   if (rows) *rows = headj_rows(m->B, m->dims[m->L]);
   if (cols) *cols = m->dims[m->L - 2];
   return w.hj_J;
+}
+
+double* bhg_mlp_head_j_t2h_dev(const bhg_mlp* m, void* fws, int* doubles) {
+  if (!mlp_desc_ok(m) || !fws) return nullptr;
+  FusedWs w;
+  carve_fused_ws(m, fws, &w);
+  if (w.nT2j == 0) return nullptr;
+  if (doubles) *doubles = 2 * m->Bp;
+  return w.hj_t2h[0];
 }
 
 size_t bhg_mlp_fused_ws_bytes(const bhg_mlp* m) {
@@ -2430,14 +2457,14 @@ int bhg_mlp_plan_describe(const bhg_mlp* m, int algo, int keep_solution, char* b
   const int n = snprintf(buf, buf_bytes,
                          "algo=%s keep_solution=%d fused=%d form=\"%s\" hoist=%d proj_level=%d lin=%d lin_head=%d upd_first=%d closing=%s "
                          "plan_ok=%d proj_ok=%d lin_ok=%d hoist_products=%d hoist_wgs=%d gram_floats=%zu fused_ws_bytes=%zu narrow_head=%d packed_prepare=%d "
-                         "global_form=%s fx_slab_bytes=%zu fx_ws_bytes_world8=%zu head_j=%d",
+                         "global_form=%s fx_slab_bytes=%zu fx_ws_bytes_world8=%zu head_j=%d head_j_tile=%d",
                          algo == 0 ? "cg" : "neumann", keep_solution ? 1 : 0, fused ? 1 : 0, form, hoist, proj_level, lin, lin_head, upd_first, closing,
                          hp.ok ? 1 : 0, hp.proj_ok ? 1 : 0, hp.lin_ok ? 1 : 0, hp.n, hp.ok ? hp.blk0[hp.n] : 0, gram,
                          fused ? bhg_mlp_fused_ws_bytes(m) : (size_t)0, narrow_head(m) ? 1 : 0, bhg_mlp_supports_packed_prepare(m),
                          // Config(type="cg_global"): the form of the global-batch solve (round 6: factor exchange whenever the projected plan is
                          // taken and the caller does not ask for x; else the one-pass form; without a fused solver the sharded form)
                          (algo == 0 && !keep_solution && bhg_mlp_fx_supported(m, 1)) ? "factor-exchange" : (fused ? "one-pass" : "sharded"),
-                         sizeof(float) * bhg_mlp_fx_slab_floats(m), bhg_mlp_fx_ws_bytes(m, 8), head_j);
+                         sizeof(float) * bhg_mlp_fx_slab_floats(m), bhg_mlp_fx_ws_bytes(m, 8), head_j, sp.head_j_tile);
   BHG_REQUIRE(n > 0 && (size_t)n < buf_bytes, "output buffer too small");
   return BHG_OK;
 }

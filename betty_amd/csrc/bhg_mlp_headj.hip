@@ -4,10 +4,12 @@
 // here a second time, inside this unit's own anonymous namespace.
 //
 // k_headj: three block classes, none of which reads what another one writes.
+// (16 x 16 tiles: the tiles come first, [0, nt), and the head rows follow them, [nt, nt + rows) — see k_headj.)
 //   [0, rows)            head rows     k_headu's rows (mlp/head_body.inc with BHG_HEAD_J): rz through J_b and the staged row of Rh_1;
 //                                      they write Rd_{L-1}, Rz, partT1, Rd_{L-2} (row-major and packed) — not Rh_{L-2}, not T2h
-//   [rows, rows + nt)    pre-head tiles Rh_{L-2} = mask (Rh_1 W_2^T + Gf(r') + beta Gf(p) + c_2) on packed operands, 32 x 16 per workgroup,
-//                                      the whole K inside it (no slabs); each emits its share of T2h = 2 <delta_top V, Rh_{L-2}> in fp64
+//   [rows, rows + nt)    pre-head tiles Rh_{L-2} = mask (Rh_1 W_2^T + Gf(r') + beta Gf(p) + c_2) on packed operands, 16 x 16 or 32 x 16 per
+//                                      workgroup, the whole K inside it (no slabs); each emits its share of T2h = 2 <delta_top V, Rh_{L-2}>
+//                                      in fp64.  A tile whose rows hold no sample (m0 >= B) loads nothing and stores its zeros.
 //   [rows + nt, ...)     update blocks pstep_body, as in k_headu
 // The head rows and the tiles read the OLD slot of Gf_{L-2}(p) (the update blocks write the other one) and beta from the granules.
 #include <stdlib.h>
@@ -43,6 +45,7 @@ struct HeadjArgs {
   const float* Rh1p; const float* W2p; double* partT2;
   int nt, nu;                           // tiles, update blocks
   int t2n;                              // slots of partT2 the consumer sums (>= nt: the tiles clear the rest)
+  double* t2clear;                      // 16 x 16 tiles: partT2 is the pair buffer of this parity; head row b clears slot b of the other one
   alignas(64) PstepArgs ps;             // (pstep_body reads them from the kernarg segment at this offset)
 };
 static_assert(offsetof(HeadjArgs, ps) % 64 == 0 && sizeof(HeadjArgs) <= 3900, "kernel arguments of k_headj");
@@ -51,7 +54,12 @@ constexpr int kHjC = 12;   // classes the form takes (the head's prefetching ins
 
 // One (16 RBLK) x (16 CBLK) tile of Rh_{L-2}: wskp_tile's K loop (two register stages), the four waves' partial tiles met in LDS in fixed
 // order, then the head kernel's combine — (sum + (Gf(r') + beta Gf(p))) + c, times the mask — and the tile's share of T2h.
-template <int RBLK, int CBLK>
+// Every element is the sum of the same four per-wave partials over the same K ranges whatever the tile shape: Rh_{L-2} has the same bits.
+// T2h partials.  PAIR = false: one slot of partT2 per tile; slots [nt, t2n) are cleared here, because the consumer sums t2n of them
+// (t2n = B where the tiles took over the head rows' slots, nt behind the layers' own partials otherwise).  PAIR = true (16 x 16): the
+// step length's one-round-trip sum takes no more partials than that, so the two row-adjacent tiles of a column tile share a slot of a
+// buffer that is zero when the launch starts and add to it with one fp64 atomic each; slots the tiles do not reach stay zero.
+template <int RBLK, int CBLK, int D, bool PAIR>
 __device__ __forceinline__ void headj_tile(const HeadjArgs& g, const int t, float* __restrict__ sPf, float* __restrict__ sD,
                                            float* __restrict__ sV, double* __restrict__ red) {
   constexpr int TR = 16 * RBLK, TC = 16 * CBLK, TCP = TC + 1;
@@ -63,6 +71,12 @@ __device__ __forceinline__ void headj_tile(const HeadjArgs& g, const int t, floa
   int tm = t % ntm, tn = t / ntm;
   if ((ntn & 7) == 0) { const int j = t >> 3; tm = j % ntm; tn = (j / ntm) * 8 + (t & 7); }
   const int m0 = TR * tm, n0 = TC * tn;
+  if (m0 >= B) {   // (workgroup-uniform) no sample in these rows: their outputs are zero, T2h gets nothing from them
+    for (int e = threadIdx.x; e < TR * TC; e += 64 * kWskpWaves) g.fz.rh_out[(int64_t)(m0 + e / TC) * RB + n0 + (e % TC)] = 0.f;
+    if (!PAIR && threadIdx.x == 0)
+      for (int z = t; z < g.t2n; z += g.nt) g.partT2[z] = 0.0;
+    return;
+  }
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int li = lane & 15, lk = lane >> 4;
@@ -101,7 +115,7 @@ __device__ __forceinline__ void headj_tile(const HeadjArgs& g, const int t, floa
     const int64_t sA = (int64_t)16 * RA, sB = (int64_t)16 * RB;
     const float* gA = g.Rh1p + (int64_t)(2 * c0) * sA + (m0 + li) * 16 + 4 * lk;
     const float* gB = g.W2p + (int64_t)(2 * c0) * sB + (n0 + li) * 16 + 4 * lk;
-    wskp_loop<2, RBLK, CBLK>(gA, gB, sA, sB, nch_w, acc);
+    wskp_loop<D, RBLK, CBLK>(gA, gB, sA, sB, nch_w, acc);
   }
   // C/D layout of v_mfma_f32_16x16x4_f32: col = lane & 15, row = 4 * (lane >> 4) + reg
   float* sW = sPf + wave * (TR * TCP);
@@ -140,26 +154,38 @@ __device__ __forceinline__ void headj_tile(const HeadjArgs& g, const int t, floa
     double s = 0.0;
 #pragma unroll
     for (int w = 0; w < kWskpWaves; ++w) s += red[w];
-    g.partT2[t] = 2.0 * s;
-    for (int z = t + g.nt; z < g.t2n; z += g.nt) g.partT2[z] = 0.0;   // (the consumer sums t2n slots)
+    if constexpr (PAIR) {
+      atomicAdd(g.partT2 + tn * (ntm / 2) + (tm >> 1), 2.0 * s);   // (result unused: no return value asked of the memory side)
+    } else {
+      g.partT2[t] = 2.0 * s;
+      for (int z = t + g.nt; z < g.t2n; z += g.nt) g.partT2[z] = 0.0;   // (the consumer sums t2n slots)
+    }
   }
 }
 
 // TS: the tiles' shape — 0: 32 x 32 (48 workgroups at cfg 2: 5 us of MFMAs each, the launch 17.9 us); 1: 32 x 16 (96 workgroups: the
-// launch 11 us; four register stages instead of two: 1 us slower).  Same-box arms, profiles/head_j_ab.txt.
-template <int U, int TS>
+// launch 11 us; four register stages instead of two: 1 us slower); 2: 16 x 16, T2h by pairs (192 workgroups, 24 of them without a
+// sample at B = 100).  Same-box arms, profiles/head_j_ab.txt and profiles/head_j_tiles_ab.txt.
+// D: register stages of the tiles' K loop (four with 16 x 16 tiles: 0.15 us slower than two, not kept).  TF: the tiles take the launch's
+// first workgroups and the head rows follow them — the 16 x 16 shape's default: the tiles are the launch's critical path, and dispatched
+// first they gain 0.6 us per iteration over rows first (same-box arms, profiles/head_j_tiles_ab.txt); the coarser shapes stay rows first.
+template <int U, int TS, int D, bool TF>
 __global__ __launch_bounds__(256) void k_headj(HeadjArgs g) {
   static_assert(64 * kWskpWaves == 256, "the tiles run in the head launch's workgroups");
   const int bx = (int)blockIdx.x;
   if (bx >= g.rows + g.nt) { pstep_body<U, (int)offsetof(HeadjArgs, ps), false>(bx - g.rows - g.nt); return; }
-  if (bx >= g.rows) {
+  if (TF ? bx < g.nt : bx >= g.rows) {
     __shared__ float sPf[kWskpLds];
     __shared__ float sD[32 * kHjC], sV[kHjC * 32];
     __shared__ double red[kWskpWaves];
-    if constexpr (TS == 0) headj_tile<2, 2>(g, bx - g.rows, sPf, sD, sV, red);
-    else headj_tile<2, 1>(g, bx - g.rows, sPf, sD, sV, red);
+    const int t = TF ? bx : bx - g.rows;
+    if constexpr (TS == 0) headj_tile<2, 2, D, false>(g, t, sPf, sD, sV, red);
+    else if constexpr (TS == 1) headj_tile<2, 1, D, false>(g, t, sPf, sD, sV, red);
+    else headj_tile<1, 1, D, true>(g, t, sPf, sD, sV, red);
     return;
   }
+  const int hrow = TF ? bx - g.nt : bx;   // this workgroup's head row
+  if (TS == 2 && threadIdx.x == 0) g.t2clear[hrow] = 0.0;   // (its consumer, the closing launch of the iteration before, is long done)
   const float* __restrict__ Rh = nullptr; const float* __restrict__ h = g.h; const float* __restrict__ W = g.W;
   const float* __restrict__ V = g.V; const float* __restrict__ cb = g.cb; const float* __restrict__ prob = g.prob;
   const float* __restrict__ sd = g.sd; float* __restrict__ rd = g.rd;
@@ -176,7 +202,7 @@ __global__ __launch_bounds__(256) void k_headj(HeadjArgs g) {
   constexpr bool HAS_RH = true, FUSED = true, PF = true;
   constexpr int JMAX = 3;
   (void)Rh; (void)labels; (void)aux; (void)rzx_acc; (void)rzx_first;
-#define BHG_HEAD_B (bx)
+#define BHG_HEAD_B (hrow)
 #define BHG_HEAD_ROWS (g.rows)
 #define BHG_HEAD_LAZY 1
 #define BHG_HEAD_J 1
@@ -209,7 +235,7 @@ __global__ __launch_bounds__(256) void k_headj_pack(const float* __restrict__ W3
 }
 }  // namespace
 
-int headj_tiles(int rows, int K, int shape) { return (rows / 32) * (K / (shape == 0 ? 32 : 16)); }
+int headj_tiles(int rows, int K, int shape) { return (rows / (shape == 2 ? 16 : 32)) * (K / (shape == 0 ? 32 : 16)); }
 
 int launch_headj(const HeadjLaunch& a, hipStream_t st) {
   BHG_REQUIRE(a.C >= 1 && a.C <= kHjC && a.K >= 32 && a.K <= 512 && a.K % 32 == 0 && a.K1 >= 32 && a.K1 % 32 == 0 && a.rows % 32 == 0 &&
@@ -225,14 +251,24 @@ int launch_headj(const HeadjLaunch& a, hipStream_t st) {
   g.partT1 = a.partT1; g.rz_out = a.rz_out; g.addend2 = a.addend2; g.gran = a.gran;
   g.J = a.J; g.Rh1 = a.Rh1; g.K1 = a.K1; g.Rh1p = a.Rh1p; g.W2p = a.W2p; g.partT2 = a.partT2;
   g.nt = headj_tiles(a.rows, a.K, a.tile_shape); g.nu = a.nu; g.t2n = a.t2n;
-  BHG_REQUIRE(a.t2n >= g.nt, "fewer T2h slots than tiles");
+  BHG_REQUIRE(a.tile_shape >= 0 && a.tile_shape <= 2, "unknown tile shape");
+  if (a.tile_shape == 2) {
+    BHG_REQUIRE(a.t2pair && a.t2clear && a.t2pair != a.t2clear && g.nt / 2 <= a.B, "16 x 16 tiles: one T2h slot per pair, in a buffer per parity");
+    g.partT2 = a.t2pair; g.t2clear = a.t2clear;
+  } else {
+    BHG_REQUIRE(a.t2n >= g.nt, "fewer T2h slots than tiles");
+  }
   memcpy(&g.ps, a.ps, sizeof(PstepArgs));
   const dim3 grid(a.rows + g.nt + g.nu);
   const size_t lds = (size_t)a.K * sizeof(float);
-#ifdef BHG_AB   // (debug key head_j_tile)
-  if (a.tile_shape == 0) hipLaunchKernelGGL((k_headj<4, 0>), grid, dim3(256), lds, st, g); else
+#ifdef BHG_AB   // (debug keys head_j_tile, head_j_stages4, head_j_tiles_first: the arms of the 16 x 16 shape)
+  if (a.tile_shape == 0) hipLaunchKernelGGL((k_headj<4, 0, 2, false>), grid, dim3(256), lds, st, g);
+  else if (a.tile_shape == 2 && a.stages4) hipLaunchKernelGGL((k_headj<4, 2, 4, false>), grid, dim3(256), lds, st, g);
+  else if (a.tile_shape == 2 && !a.tiles_first) hipLaunchKernelGGL((k_headj<4, 2, 2, false>), grid, dim3(256), lds, st, g);
+  else
 #endif
-  hipLaunchKernelGGL((k_headj<4, 1>), grid, dim3(256), lds, st, g);
+  if (a.tile_shape == 2) hipLaunchKernelGGL((k_headj<4, 2, 2, true>), grid, dim3(256), lds, st, g);
+  else hipLaunchKernelGGL((k_headj<4, 1, 2, false>), grid, dim3(256), lds, st, g);
   return BHG_OK;
 }
 

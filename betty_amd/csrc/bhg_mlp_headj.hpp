@@ -31,12 +31,25 @@ struct HeadjLaunch {
   const float* Rh1p; const float* W2p;      // packed operands [K1 / 16][rows][16], [K1 / 16][K][16]
   float* rh_out;                            // Rh_2 [rows][K] row-major
   double* partT2; int t2n;                  // one fp64 partial of T2h per tile; the consumer sums t2n >= tiles slots (the rest cleared)
-  int tile_shape;                           // kHeadjTile, or the measurement build's debug key head_j_tile
+  // ... or, with 16 x 16 tiles (shape 2), one slot per PAIR of row-adjacent tiles: t2pair != NULL is a buffer of `rows` doubles that is
+  // zero when the launch starts; both tiles of a pair add their partial to slot `pair` (two addends onto an exact zero: the sum does
+  // not depend on their order).  t2clear: the buffer of the other iteration parity, whose slot b head row b clears for the next launch.
+  double* t2pair; double* t2clear;
+  int tile_shape;                           // headj_tile_shape(), or the measurement build's debug key head_j_tile
+  int stages4;                              // measurement build only (key head_j_stages4): four register stages, rows first
+  int tiles_first;                          // 16 x 16 tiles: dispatched ahead of the head rows (default; key head_j_tiles_first = 0: behind them)
   // ---- update blocks: a PstepArgs (mlp/pstep.inc), copied as bytes
   const void* ps; size_t ps_bytes; int nu;
 };
-constexpr int kHeadjTile = 1;               // 32 x 16 tiles (0: 32 x 32)
-int headj_tiles(int rows, int K, int shape);   // workgroups (= T2h partials) of the tile class
+constexpr int kHeadjTile = 1;               // 32 x 16 tiles (0: 32 x 32; 2: 16 x 16, T2h by pairs)
+constexpr int kHeadjFineMax = 192;          // the most 16 x 16 tiles the plan asks for (d_3 = 384 at 128 rows: the count it was measured at)
+int headj_tiles(int rows, int K, int shape);   // workgroups of the tile class (shapes 0 and 1: = T2h partials; shape 2: two per partial)
+// The shape the plan picks: 16 x 16 where their pairs fit the B slots the step length's sum reads (and no more than kHeadjFineMax
+// tiles), else 32 x 16 as before
+inline int headj_tile_shape(int rows, int K, int B) {
+  const int nt = (rows / 16) * (K / 16);
+  return (nt / 2 <= B && nt <= kHeadjFineMax) ? 2 : kHeadjTile;
+}
 int launch_headj(const HeadjLaunch& a, hipStream_t st);
 
 // A[b C + c][k] = W_3[c][k] mask_2[b][k], packed [K / 16][RA][16] (RA = round32(B C); rows >= B C zero) for J = A W_2

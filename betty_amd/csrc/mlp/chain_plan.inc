@@ -84,6 +84,7 @@ struct ChainState {
   bool sd_in_chain = false;           // first iteration: S_l, D_l rode in the first chain launch as well
   bool head_j = false;                // this pass skipped the pre-head launch: the head launch is k_headj, T2h arrives as tile partials
   int head_j_nt = 0;                  // ... behind the layers' own in partT2 (0: in partT2h's slots)
+  double* head_j_t2h = nullptr;       // ... or, 16 x 16 tiles, by pairs of tiles in this buffer of B slots, which the step length sums as partT2h
 };
 
 int plan_chain(const bhg_mlp* m, const ChainMode& cm, ChainPlan* p) {

@@ -33,6 +33,7 @@ struct SolvePlan {
   // pre-head product through J (k_headj): no pre-head launch, its tiles ride in the head launch of every iteration but the first |
   // upd_first: deeper than four layers, the update blocks stay in k_wskpl behind the publisher of beta
   bool lin, lin_head, head_j, upd_first;
+  int head_j_tile;              // head_j: the shape of the pre-head tiles in the head launch (head_j_tile(): 1 = 32 x 16, 2 = 16 x 16); else -1
   const char* closing;          // the launch that closes a projected iteration: k_outer_all | k_graw | k_grawk | k_hoist+k_proj_update
 };
 
@@ -43,6 +44,7 @@ struct SolvePlan {
 void plan_solve(const bhg_mlp* m, int algo, bool keep_solution, bool global, SolvePlan* sp) {
   memset(sp, 0, sizeof(*sp));
   sp->closing = "k_outer_all";
+  sp->head_j_tile = -1;
   sp->fused = bhg_mlp_supports_fused_solve(m) != 0;
   if (!sp->fused) return;
   HoistPlan& hp = sp->hp;
@@ -77,6 +79,7 @@ void plan_solve(const bhg_mlp* m, int algo, bool keep_solution, bool global, Sol
                  m->dims[m->L] <= 12 && m->dims[m->L - 1] <= 512 && dbg(DBG_head_no_prefetch, 0) == 0;
   // head_j: J = W_3 diag(mask_2) W_2 is built once per solve, the pre-head launch leaves the dependency chain (bhg_mlp_headj.hip)
   sp->head_j = sp->lin_head && headj_shape_ok(m, hp) && dbg(DBG_head_j, 1) != 0;
+  sp->head_j_tile = sp->head_j ? head_j_tile(m) : -1;
   sp->upd_first = sp->lin && m->L > 4;
   if (sp->proj_level >= 1) sp->closing = graw_batch_ok(m->Bp) ? (m->Bp == 128 ? "k_graw" : "k_grawk") : "k_hoist+k_proj_update";
 }

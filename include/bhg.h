@@ -510,6 +510,10 @@ void* bhg_mlp_timeout_flag_dev(const bhg_mlp* m, void* fws);
  * of >= 2 iterations: row-major, *rows = B C rounded up to 32 (rows >= B C are zero), *cols = dims[2].  NULL where the form does not
  * apply.  For tests; reads nothing on the device.                                                                                    */
 const float* bhg_mlp_head_j_dev(const bhg_mlp* m, void* fws, int* rows, int* cols);
+/* Where the head launch runs 16 x 16 pre-head tiles (plan key head_j_tile = 2) the head layer's second-order share of p.Hp arrives by
+ * pairs of tiles in two buffers of Bp doubles inside `fws`, one per iteration parity, which every solve clears before its first use.
+ * Device address of the first (the second follows it), *doubles = 2 Bp.  NULL where the head_j form does not apply.  For tests.      */
+double* bhg_mlp_head_j_t2h_dev(const bhg_mlp* m, void* fws, int* doubles);
 
 /* ---- closed-form meta-weight-net (round 5; csrc/bhg_mwn.hip) --------------------------------------------------------------------
  * The UPPER problem of data reweighting (examples/learning_to_reweight/model.py:98-111 `MLP(hidden_size, num_layers = 1)`, called at
