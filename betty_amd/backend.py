@@ -495,6 +495,19 @@ def layernorm_plan(M: int, D: int) -> dict:
     return {k: int(v) for k, v in re.findall(r"(\w+)=(-?\d+)", buf.value.decode())}
 
 
+def groupnorm_plan(N: int, C: int, HW: int, G: int) -> dict:
+    """The launch geometry bhg_groupnorm_backward_vjp takes for an [N, C, *spatial] input with HW spatial positions and G groups, as a
+    dict: ``regime`` ("resident": rows of D <= 8192 elements held in registers, or "streamed"), ``D``, ``vec`` (4: 16-byte accesses, 1:
+    scalar), ``tpr`` threads per row, ``rows`` rows side by side (one row group = one workgroup), ``nv`` vectors per thread (``inst``: of
+    the kernel instance resp. per tile), ``tile``, ``groups`` = ``grid`` workgroups, ``ws`` bytes of workspace written when dgamma is
+    wanted (include/bhg.h: bhg_groupnorm_plan — host logic only: works on a box without a GPU).  A shape the launch refuses raises."""
+    buf = ctypes.create_string_buffer(256)
+    _native.check(_native.load().bhg_groupnorm_plan(int(N), int(C), int(HW), int(G), buf, 256), "bhg_groupnorm_plan")
+    out = {k: int(v) for k, v in re.findall(r"(\w+)=(-?\d+)", buf.value.decode())}
+    out["regime"] = "streamed" if out["regime"] else "resident"
+    return out
+
+
 def attention_plan(B: int, H: int, L: int, S: int, d: int, vec_ok: bool = True) -> dict:
     """What bhg_attention_backward_vjp takes for B x H heads of L queries, S keys and d elements, as a dict: ``vec`` (4: 16-byte accesses —
     d % 4 == 0 and ``vec_ok``, the caller's statement that every stride is a multiple of 4 —, 1: scalar), ``ps`` / ``pd`` (padded row

@@ -19,7 +19,8 @@ other dtypes, channels-last — it IS ``nn.BatchNorm2d``.  Third derivatives are
 ``PointwiseConv2d`` and ``DepthwiseConv2d`` (further down) declare the other two layers of a DARTS / MobileNet-style block,
 ReLU -> depthwise k x k -> 1 x 1 -> BatchNorm2d; ``declare_layers_(module, depthwise=True)`` applies all three.  ``FusedLayerNorm``
 (at the end) is the same declaration for ``nn.LayerNorm`` — the normalisation of a transformer block;
-``declare_layers_(module, layernorm=True)`` applies it.  ``scaled_dot_product_attention`` / ``declared_attention()`` (last) declare the
+``declare_layers_(module, layernorm=True)`` applies it; ``FusedGroupNorm`` / ``declare_layers_(module, groupnorm=True)`` do the same for
+``nn.GroupNorm``.  ``scaled_dot_product_attention`` / ``declared_attention()`` (last) declare the
 attention core for short sequences: a function and a context manager, because attention is not a module;
 ``tiled_scaled_dot_product_attention`` / ``declared_attention(tiled=True)`` extend it to 512 tokens (opt-in).
 """
@@ -35,7 +36,8 @@ from torch.autograd.function import once_differentiable
 from . import _native
 
 __all__ = ["FusedBatchNorm2d", "fuse_batchnorm_", "fused_batchnorm_calls", "PointwiseConv2d", "declare_pointwise_convs_", "DepthwiseConv2d",
-           "declare_depthwise_convs_", "depthwise_conv_calls", "FusedLayerNorm", "fuse_layernorm_", "fused_layernorm_calls", "declare_layers_",
+           "declare_depthwise_convs_", "depthwise_conv_calls", "FusedLayerNorm", "fuse_layernorm_", "fused_layernorm_calls", "FusedGroupNorm", "fuse_groupnorm_",
+           "fused_groupnorm_calls", "declare_layers_",
            "scaled_dot_product_attention", "declared_attention", "declared_attention_calls", "tiled_scaled_dot_product_attention",
            "declared_attention_tiled_calls"]
 
@@ -463,14 +465,151 @@ def fuse_layernorm_(module: torch.nn.Module) -> int:
     return n
 
 
-def declare_layers_(module: torch.nn.Module, depthwise: bool = False, layernorm: bool = False) -> dict:
+# ---- FusedGroupNorm: the normalisation of a ResNet whose batches are too small for batch norm ------------------------------------------------
+# ATen's derivative formula for native_group_norm switches to infinitely_differentiable_native_group_norm_backward as soon as grad mode
+# is on: under create_graph=True even the first backward is a chain of element-wise operators, and the double backward a longer one.
+# Declared, the layer's forward and first backward are ATen's single kernels (native_group_norm / native_group_norm_backward), tied into
+# the graph as two autograd.Function nodes as for layer norm, and the backward OF the backward node is one bhg_groupnorm_backward_vjp
+# call (csrc/bhg_groupnorm.hip): at most two launches.
+_GN_CALLS = {"forward": 0, "backward": 0, "backward_vjp": 0}   # test / measurement hook: which nodes ran
+_GN_MAX_D = 1 << 20                                            # the family bhg_groupnorm_backward_vjp takes: rows of at most 2^20 elements
+
+
+def fused_groupnorm_calls() -> dict:
+    return dict(_GN_CALLS)
+
+
+_GN_WS = {}   # (device, stream) -> scratch for the per-sample sums of dgamma
+
+
+def _gn_workspace(device, N, C, lib):
+    key = (str(device), int(torch.cuda.current_stream(device).cuda_stream))
+    n = int(lib.bhg_groupnorm_ws_bytes(int(N), int(C)))
+    ws = _GN_WS.get(key)
+    if ws is None or ws.numel() < n:
+        ws = _GN_WS[key] = torch.empty(max(n, 1 << 16), dtype=torch.uint8, device=device)
+    return ws
+
+
+def _gn_vjp_hip(x, gy, a, gamma, mean, rstd, b, c, G):
+    """(dx, dgy, dgamma) through bhg_groupnorm_backward_vjp; dgamma is None when gamma is.  The product's only implementation: it raises
+    when the HIP extension is missing or the tensors are not on the GPU."""
+    if not x.is_cuda:
+        raise _native.NativeLibraryError("FusedGroupNorm's double backward needs CUDA/HIP tensors; there is no CPU fallback")
+    lib = _native.load()
+    N, C = int(x.shape[0]), int(x.shape[1])
+    HW = x.numel() // (N * C)
+
+    def prep(t):
+        if t is None:
+            return None
+        t = t.detach()
+        return t if (t.dtype == torch.float32 and t.is_contiguous() and t.data_ptr() % 16 == 0) else t.to(torch.float32).contiguous().clone()
+
+    x, gy, a, gamma, mean, rstd, b, c = (prep(t) for t in (x, gy, a, gamma, mean, rstd, b, c))
+    dx, dgy = torch.empty_like(x), torch.empty_like(x)
+    dgamma = torch.empty_like(gamma) if gamma is not None else None
+    ws = _gn_workspace(x.device, N, C, lib) if gamma is not None else None
+    ptr = lambda t: None if t is None else t.data_ptr()   # noqa: E731
+    _native.check(
+        lib.bhg_groupnorm_backward_vjp(x.data_ptr(), gy.data_ptr(), ptr(a), ptr(gamma), mean.data_ptr(), rstd.data_ptr(), ptr(b), ptr(c),
+                                       N, C, int(HW), int(G), dx.data_ptr(), dgy.data_ptr(), ptr(dgamma), ptr(ws),
+                                       0 if ws is None else ws.numel(), _stream()),
+        "bhg_groupnorm_backward_vjp")
+    return dx, dgy, dgamma
+
+
+_GN_VJP_IMPL = [_gn_vjp_hip]   # TEST HOOK ONLY (tests/test_fused_groupnorm.py swaps in the float64 restatement to check the graph plumbing on CPU)
+
+
+class _GNBackward(torch.autograd.Function):
+    """(x, gy, gamma) -> (gx, ggamma, gbeta): group norm's backward as a graph node whose own backward is ONE fused call."""
+
+    @staticmethod
+    def forward(ctx, x, gy, gamma, beta, mean, rstd, G, need_dx):
+        _GN_CALLS["backward"] += 1
+        gy = gy.contiguous()
+        N, C = x.shape[0], x.shape[1]
+        # the backward nn.GroupNorm itself runs without create_graph: one kernel, not the decomposition
+        gx, gg, gb = torch.ops.aten.native_group_norm_backward(gy, x, mean, rstd, gamma, N, C, x.numel() // (N * C), G,
+                                                               [bool(need_dx), gamma is not None, beta is not None])
+        ctx.save_for_backward(x, gy, gamma, mean, rstd)
+        ctx.G = G
+        ctx.set_materialize_grads(False)
+        return (gx if need_dx else None), (gg if gamma is not None else None), (gb if beta is not None else None)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, a, b, c):
+        x, gy, gamma, mean, rstd = ctx.saved_tensors
+        _GN_CALLS["backward_vjp"] += 1
+        dx, dgy, dgamma = _GN_VJP_IMPL[0](x, gy, a, gamma, mean, rstd, b, c, ctx.G)
+        return dx, dgy, dgamma, None, None, None, None, None
+
+
+class _GNForward(torch.autograd.Function):
+    """Group norm on ATen's own kernel; its backward is the node above (so create_graph=True records THAT node)."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, G, eps):
+        _GN_CALLS["forward"] += 1
+        N, C = x.shape[0], x.shape[1]
+        y, mean, rstd = torch.native_group_norm(x, gamma, beta, N, C, x.numel() // (N * C), G, eps)
+        ctx.save_for_backward(x, gamma, beta, mean, rstd)
+        ctx.G = G
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, gamma, beta, mean, rstd = ctx.saved_tensors
+        gx, gg, gb = _GNBackward.apply(x, gy, gamma, beta, mean, rstd, ctx.G, ctx.needs_input_grad[0])
+        return gx, gg, gb, None, None
+
+
+class FusedGroupNorm(torch.nn.GroupNorm):
+    """``nn.GroupNorm`` whose double backward is fused (comment above).  Same parameters and ``state_dict`` (``affine=False``
+    included); an input outside the declared family — not CUDA fp32 contiguous and 16-byte aligned, fewer than 2 dimensions, more than
+    2^20 elements per (sample, group) row, a shape ``nn.GroupNorm`` itself refuses, grad disabled — IS ``nn.GroupNorm``, with its bits and
+    its errors.  Third derivatives are not provided."""
+
+    def _declared(self, x) -> bool:
+        if not (x.is_cuda and x.dtype == torch.float32 and x.dim() >= 2 and x.is_contiguous() and x.data_ptr() % 16 == 0 and x.numel() > 0):
+            return False
+        N, C, G = x.shape[0], x.shape[1], self.num_groups
+        if C != self.num_channels or G <= 0 or C % G != 0:
+            return False                  # nn.GroupNorm's own error
+        D = x.numel() // (N * G)
+        if not (D <= _GN_MAX_D and N * D > 1 and N * G < 2 ** 31):   # N * D == 1: F.group_norm refuses a single value per group
+            return False
+        return all(p is None or (p.dtype == torch.float32 and p.is_contiguous() and p.device == x.device) for p in (self.weight, self.bias))
+
+    def forward(self, x):
+        if not torch.is_grad_enabled() or not self._declared(x):
+            return super().forward(x)
+        return _GNForward.apply(x, self.weight, self.bias, self.num_groups, self.eps)
+
+
+def fuse_groupnorm_(module: torch.nn.Module) -> int:
+    """Declare every ``nn.GroupNorm`` of ``module`` (exact class; subclasses are left alone) as :class:`FusedGroupNorm`, in place: same
+    parameters and hooks, only the class changes.  Returns how many layers were declared."""
+    n = 0
+    for m in module.modules():
+        if type(m) is torch.nn.GroupNorm:
+            m.__class__ = FusedGroupNorm
+            n += 1
+    return n
+
+
+def declare_layers_(module: torch.nn.Module, depthwise: bool = False, layernorm: bool = False, groupnorm: bool = False) -> dict:
     """Every layer declaration this module offers, in place: ``{"batchnorm": n, "pointwise_conv": m}``, with ``depthwise=True`` also
-    ``"depthwise_conv": k``, and with ``layernorm=True`` also ``"layernorm": l``."""
+    ``"depthwise_conv": k``, with ``layernorm=True`` also ``"layernorm": l``, and with ``groupnorm=True`` also ``"groupnorm": g``."""
     out = {"batchnorm": fuse_batchnorm_(module), "pointwise_conv": declare_pointwise_convs_(module)}
     if depthwise:
         out["depthwise_conv"] = declare_depthwise_convs_(module)
     if layernorm:
         out["layernorm"] = fuse_layernorm_(module)
+    if groupnorm:
+        out["groupnorm"] = fuse_groupnorm_(module)
     return out
 
 

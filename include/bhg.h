@@ -633,6 +633,40 @@ int bhg_layernorm_backward_vjp(const float* x, const float* gy, const float* a, 
                                const float* rstd, const float* b, const float* c, long long M, int D, float* dx, float* dgy,
                                float* dgamma, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- group normalisation inside an opaque Hessian-vector product (csrc/bhg_groupnorm.hip) ----------------------------------------------
+ * ATen's derivative formula for native_group_norm switches to infinitely_differentiable_native_group_norm_backward as soon as grad mode is
+ * on: under create_graph=True the first backward is a chain of element-wise operators and the double backward a longer one.  This entry
+ * point is the double backward in at most two launches.  The layer: x is [N, C, *spatial] contiguous fp32, HW = prod(spatial) >= 1, G | C,
+ * Cg = C / G; row (n, g) is the D = Cg * HW contiguous elements of the channels g * Cg .. g * Cg + Cg - 1, xh = (x - mean_ng) * rstd_ng,
+ * y = gamma_ch * xh + beta_ch.  Its first backward is
+ *     F : (x, gy, gamma) -> (gx, ggamma, gbeta)      g = gamma_ch * gy, gx = rstd * (g - mean_j g - xh * mean_j (g * xh))
+ * and for cotangents a (of gx, shaped like x; may be NULL = zero), b (of ggamma, [C]; may be NULL), c (of gbeta, [C]; may be NULL):
+ *     dx, dgy (shaped like x, overwritten), dgamma ([C], overwritten; may be NULL)  =  d( <a, gx> + <b, ggamma> + <c, gbeta> ) / d(x, gy, gamma)
+ * with mean / rstd ([N, G], what native_group_norm saved) treated as the functions of x they are.  gamma may be NULL (affine = False:
+ * gamma = 1).  Every non-NULL output is overwritten in full.  N, C, HW, G >= 1, C % G == 0, D <= 2^20, N * G <= 2^31 - 1.  Rows of up to
+ * 8192 elements are held in registers between their row sums and their outputs (x, gy, a read once: 20 algorithmic bytes per element);
+ * longer rows are streamed by one workgroup each in two rounds (32 bytes per element).  x, gy, a, dx, dgy must be 16-byte aligned when
+ * D % 4 == 0 (16-byte accesses; scalar accesses otherwise); mean, rstd, gamma, b, c, dgamma need their natural 4-byte alignment only.
+ * `ws`: bhg_groupnorm_ws_bytes(N, C) = 8 * N * C bytes of scratch (0 for a non-positive argument), 8-byte aligned — the fp64 partials
+ * part[n][c] of dgamma, every one written before it is read in every call; may be NULL exactly when dgamma is (nothing is written to it
+ * then).  Refused with -1 and a message, before any device access: non-positive sizes, C % G != 0, D > 2^20, N * G > 2^31 - 1, NULL x /
+ * gy / mean / rstd / dx / dgy, dgamma without ws, a workspace that is too small or not 8-byte aligned, a row tensor that is not 16-byte
+ * aligned where that is required.  Deterministic (row sums and dgamma in fp64, fixed order; no atomics), asynchronous on `stream`, no
+ * host synchronisation.
+ *
+ * bhg_groupnorm_plan is host logic only (no launch, no device access): the geometry the launches take for a shape, from the very function
+ * the launch path calls (closed form), as one line of `key=value` pairs in buf: regime (0: resident, D <= 8192; 1: streamed), D, vec (4:
+ * 16-byte accesses, D % 4 == 0; 1: scalar), tpr (threads per row, a power of two in [1, 256]), rows (256 / tpr rows side by side: one row
+ * group = one workgroup), nv (vectors per thread and row), inst (resident: the vectors per thread of the kernel instance that runs, 2, 4,
+ * 8 resp. 2, 8, 32; streamed: the vectors per thread and tile), tile (streamed: elements per tile; 0 otherwise), groups = grid (workgroups
+ * of the row pass: ceil(N * G / rows), no bound, none empty), ws (bytes of the workspace a call with dgamma writes: 8 * N * C).  A shape
+ * that bhg_groupnorm_backward_vjp refuses is refused here with the same message.                                                        */
+size_t bhg_groupnorm_ws_bytes(long long N, int C);
+int bhg_groupnorm_plan(long long N, int C, long long HW, int G, char* buf, size_t buf_bytes);
+int bhg_groupnorm_backward_vjp(const float* x, const float* gy, const float* a, const float* gamma, const float* mean,
+                               const float* rstd, const float* b, const float* c, long long N, int C, long long HW, int G, float* dx,
+                               float* dgy, float* dgamma, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- the attention core inside an opaque Hessian-vector product, short sequences (csrc/bhg_attention.hip) -----------------------------
  * The fused SDPA kernels have no double backward; on the math path ATen differentiates bmm -> softmax -> bmm by decomposition.  This
  * entry point is the vector-Jacobian product of attention's first backward in ONE launch with no workspace: one workgroup of 256 threads
