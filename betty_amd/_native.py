@@ -266,6 +266,14 @@ SYMBOLS = {
         [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_longlong, c_int, ctypes.c_longlong, c_int,
          c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p],
     ),
+    "bhg_act_plan": (c_int, [ctypes.c_longlong, c_int, c_char_p, c_size_t]),
+    "bhg_act_backward_vjp": (
+        c_int, [c_int, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_longlong, c_void_p]),
+    "bhg_gated_act_plan": (c_int, [ctypes.c_longlong, ctypes.c_longlong, c_int, c_char_p, c_size_t]),
+    "bhg_gated_act_backward_vjp": (
+        c_int,
+        [c_int, ctypes.c_longlong, ctypes.c_longlong] + [c_void_p, ctypes.c_longlong] * 8 + [c_void_p],
+    ),
     "bhg_attention_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_char_p, c_size_t]),
     "bhg_attention_backward_vjp": (
         c_int,

@@ -508,6 +508,31 @@ def groupnorm_plan(N: int, C: int, HW: int, G: int) -> dict:
     return out
 
 
+def _plan_line(text: str) -> dict:
+    return {k: int(v) if re.fullmatch(r"-?\d+", v) else v for k, v in re.findall(r"(\w+)=(\S+)", text)}
+
+
+def activation_plan(n: int, aligned16: bool = True) -> dict:
+    """What bhg_act_backward_vjp takes for n contiguous elements, as a dict: ``vec`` (4: 16-byte accesses — ``aligned16``, the caller's
+    statement that every pointer is 16-byte aligned —, 1: scalar), ``block`` (256), ``units`` = ceil(n / vec), ``grid`` workgroups (none
+    empty, at most 2048), ``iters`` trips of the grid-stride loop and ``inst``, the kernel instance as a string (include/bhg.h:
+    bhg_act_plan — host logic only: works on a box without a GPU).  A size the launch refuses raises."""
+    buf = ctypes.create_string_buffer(256)
+    _native.check(_native.load().bhg_act_plan(int(n), 1 if aligned16 else 0, buf, 256), "bhg_act_plan")
+    return _plan_line(buf.value.decode())
+
+
+def gated_activation_plan(rows: int, H: int, vec_ok: bool = True) -> dict:
+    """What bhg_gated_act_backward_vjp takes for ``rows`` rows of H elements, as a dict: ``vec`` (4 when H % 4 == 0 and ``vec_ok`` — the
+    caller's statement that every leading dimension is a multiple of 4 and every pointer 16-byte aligned —, else 1), ``block`` (256),
+    ``tpr`` threads per row, ``rows`` rows side by side in a workgroup, ``cb`` workgroups along a row, ``rgroups`` row groups, ``work`` =
+    rgroups * cb pieces, ``grid`` workgroups (none empty, at most 2048), ``iters`` trips of the grid-stride loop and ``inst``, the kernel
+    instance as a string (include/bhg.h: bhg_gated_act_plan — host logic only).  A shape the launch refuses raises."""
+    buf = ctypes.create_string_buffer(256)
+    _native.check(_native.load().bhg_gated_act_plan(int(rows), int(H), 1 if vec_ok else 0, buf, 256), "bhg_gated_act_plan")
+    return _plan_line(buf.value.decode())
+
+
 def attention_plan(B: int, H: int, L: int, S: int, d: int, vec_ok: bool = True) -> dict:
     """What bhg_attention_backward_vjp takes for B x H heads of L queries, S keys and d elements, as a dict: ``vec`` (4: 16-byte accesses —
     d % 4 == 0 and ``vec_ok``, the caller's statement that every stride is a multiple of 4 —, 1: scalar), ``ps`` / ``pd`` (padded row

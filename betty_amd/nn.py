@@ -22,7 +22,9 @@ ReLU -> depthwise k x k -> 1 x 1 -> BatchNorm2d; ``declare_layers_(module, depth
 ``declare_layers_(module, layernorm=True)`` applies it; ``FusedGroupNorm`` / ``declare_layers_(module, groupnorm=True)`` do the same for
 ``nn.GroupNorm``.  ``scaled_dot_product_attention`` / ``declared_attention()`` (last) declare the
 attention core for short sequences: a function and a context manager, because attention is not a module;
-``tiled_scaled_dot_product_attention`` / ``declared_attention(tiled=True)`` extend it to 512 tokens (opt-in).
+``tiled_scaled_dot_product_attention`` / ``declared_attention(tiled=True)`` extend it to 512 tokens (opt-in).  ``gelu``, ``silu``,
+``tanh``, ``sigmoid``, ``softplus``, ``glu`` and ``gated_activation`` (at the very end) declare the smooth activations: functions,
+``declared_activations()`` as a context manager and ``declare_activations_(module)`` / ``declare_layers_(module, activations=True)``.
 """
 from __future__ import annotations
 
@@ -39,7 +41,9 @@ __all__ = ["FusedBatchNorm2d", "fuse_batchnorm_", "fused_batchnorm_calls", "Poin
            "declare_depthwise_convs_", "depthwise_conv_calls", "FusedLayerNorm", "fuse_layernorm_", "fused_layernorm_calls", "FusedGroupNorm", "fuse_groupnorm_",
            "fused_groupnorm_calls", "declare_layers_",
            "scaled_dot_product_attention", "declared_attention", "declared_attention_calls", "tiled_scaled_dot_product_attention",
-           "declared_attention_tiled_calls"]
+           "declared_attention_tiled_calls",
+           "gelu", "silu", "tanh", "sigmoid", "softplus", "glu", "gated_activation", "declare_activations_", "declared_activations",
+           "declared_activation_calls", "DeclaredGELU", "DeclaredSiLU", "DeclaredTanh", "DeclaredSigmoid", "DeclaredSoftplus", "DeclaredGLU"]
 
 _CALLS = {"forward": 0, "backward": 0, "backward_vjp": 0}   # test / measurement hook: which nodes ran
 
@@ -600,9 +604,11 @@ def fuse_groupnorm_(module: torch.nn.Module) -> int:
     return n
 
 
-def declare_layers_(module: torch.nn.Module, depthwise: bool = False, layernorm: bool = False, groupnorm: bool = False) -> dict:
+def declare_layers_(module: torch.nn.Module, depthwise: bool = False, layernorm: bool = False, groupnorm: bool = False,
+                    activations: bool = False) -> dict:
     """Every layer declaration this module offers, in place: ``{"batchnorm": n, "pointwise_conv": m}``, with ``depthwise=True`` also
-    ``"depthwise_conv": k``, with ``layernorm=True`` also ``"layernorm": l``, and with ``groupnorm=True`` also ``"groupnorm": g``."""
+    ``"depthwise_conv": k``, with ``layernorm=True`` also ``"layernorm": l``, with ``groupnorm=True`` also ``"groupnorm": g``, and with
+    ``activations=True`` also ``"activations": a`` (``declare_activations_``, further down)."""
     out = {"batchnorm": fuse_batchnorm_(module), "pointwise_conv": declare_pointwise_convs_(module)}
     if depthwise:
         out["depthwise_conv"] = declare_depthwise_convs_(module)
@@ -610,6 +616,8 @@ def declare_layers_(module: torch.nn.Module, depthwise: bool = False, layernorm:
         out["layernorm"] = fuse_layernorm_(module)
     if groupnorm:
         out["groupnorm"] = fuse_groupnorm_(module)
+    if activations:
+        out["activations"] = declare_activations_(module)
     return out
 
 
@@ -865,3 +873,320 @@ def declared_attention(tiled: bool = False):
         yield
     finally:
         F.scaled_dot_product_attention = previous
+
+
+# ---- declared activations: GELU, SiLU, tanh, sigmoid, softplus, GLU and the gated forms of a transformer's feed-forward block --------------
+# ATen differentiates an activation's backward by decomposition: 5 (tanh) to 37 (tanh-approximated GELU) element-wise launches per
+# activation and product, and F.silu's FIRST backward is already 8 operators once grad mode is on.  Declared, the forward is the torch
+# function's own kernel and the first backward ATen's single backward kernel (gelu_backward, silu_backward, tanh_backward,
+# sigmoid_backward, softplus_backward, glu_backward; a few torch operations for the gated form), tied into the graph as two
+# autograd.Function nodes as for layer norm, and the backward OF the backward node is one bhg_act_backward_vjp or
+# bhg_gated_act_backward_vjp call (csrc/bhg_activation.hip): ONE launch, no workspace.  Activations are functions as well as modules:
+# functions, a context manager (like declared_attention) and a re-classing of the nn modules (like fuse_layernorm_).
+_ACT_CALLS = {"forward": 0, "backward": 0, "backward_vjp": 0}   # test / measurement hook: which nodes ran
+_ACT_KINDS = {"gelu": 0, "gelu_tanh": 1, "silu": 2, "tanh": 3, "sigmoid": 4, "softplus": 5}   # include/bhg.h: BHG_ACT_*
+_ACT_GATED = ("gelu", "gelu_tanh", "silu", "tanh", "sigmoid")
+_ACT_MIN_NUMEL = 1   # no measured shape is slower declared (profiles/activation_double_backward.txt): the family starts at one element
+_TORCH_GELU, _TORCH_SILU = torch.nn.functional.gelu, torch.nn.functional.silu   # what anything outside the family IS
+_TORCH_SOFTPLUS, _TORCH_GLU = torch.nn.functional.softplus, torch.nn.functional.glu
+_TORCH_TANH, _TORCH_SIGMOID = torch.tanh, torch.sigmoid
+
+
+def declared_activation_calls() -> dict:
+    return dict(_ACT_CALLS)
+
+
+def _act_forward_fn(kind, x, beta, threshold):
+    if kind == "gelu":
+        return _TORCH_GELU(x)
+    if kind == "gelu_tanh":
+        return _TORCH_GELU(x, approximate="tanh")
+    if kind == "silu":
+        return _TORCH_SILU(x)
+    if kind == "tanh":
+        return _TORCH_TANH(x)
+    if kind == "sigmoid":
+        return _TORCH_SIGMOID(x)
+    return _TORCH_SOFTPLUS(x, beta=beta, threshold=threshold)
+
+
+def _act_backward_fn(kind, gy, x, y, beta, threshold):
+    """ATen's single backward kernel of the kind: what the torch function's ordinary backward runs (y: the output, for tanh / sigmoid)."""
+    aten = torch.ops.aten
+    if kind == "gelu":
+        return aten.gelu_backward(gy, x, approximate="none")
+    if kind == "gelu_tanh":
+        return aten.gelu_backward(gy, x, approximate="tanh")
+    if kind == "silu":
+        return aten.silu_backward(gy, x)
+    if kind == "tanh":
+        return aten.tanh_backward(gy, y)
+    if kind == "sigmoid":
+        return aten.sigmoid_backward(gy, y)
+    return aten.softplus_backward(gy, x, beta, threshold)
+
+
+def _act_vjp_hip(form, kind, ins, need, beta=1.0, threshold=20.0):
+    """The double backward's one call.  form "plain": ins = (x, gy, a) -> (dx, dgy) through bhg_act_backward_vjp; "glu": the same
+    tensors of F.glu(x, -1), taken as the halves of the gated form (v first, u second) and written into the halves of one dx; "gated":
+    ins = (u, v, gy, au, av) -> (du, dv, dgy) through bhg_gated_act_backward_vjp.  ``need`` says which outputs are wanted (the others are
+    None).  The product's only implementation: it raises when the HIP extension is missing or the tensors are not on the GPU."""
+    if not ins[0].is_cuda:
+        raise _native.NativeLibraryError("a declared activation's double backward needs CUDA/HIP tensors; there is no CPU fallback")
+    lib = _native.load()
+
+    def prep(t):
+        if t is None:
+            return None
+        t = t.detach()
+        return t if (t.dtype == torch.float32 and t.is_contiguous()) else t.to(torch.float32).contiguous()
+
+    ins = [prep(t) for t in ins]
+    ptr = lambda t: None if t is None else t.data_ptr()   # noqa: E731
+    k = _ACT_KINDS["sigmoid" if form == "glu" else kind]
+    with torch.cuda.device(ins[0].device):
+        if form == "plain":
+            x, gy, a = ins
+            dx, dgy = (torch.empty_like(x) if on else None for on in need)
+            _native.check(lib.bhg_act_backward_vjp(k, float(beta), float(threshold), x.data_ptr(), gy.data_ptr(), a.data_ptr(), ptr(dx), ptr(dgy),
+                                                   x.numel(), _stream()), "bhg_act_backward_vjp")
+            return dx, dgy
+        if form == "glu":
+            x, gy, a = ins
+            H = x.shape[-1] // 2
+            rows = x.numel() // (2 * H)
+            dx, dgy = (torch.empty_like(t) if on else None for on, t in zip(need, (x, gy)))
+            off = lambda t: None if t is None else t.data_ptr() + 4 * H   # noqa: E731  (the second half of a row: u, au, du)
+            _native.check(lib.bhg_gated_act_backward_vjp(k, rows, H, off(x), 2 * H, x.data_ptr(), 2 * H, gy.data_ptr(), H, off(a), 2 * H,
+                                                         a.data_ptr(), 2 * H, off(dx), 2 * H, ptr(dx), 2 * H, ptr(dgy), H, _stream()),
+                          "bhg_gated_act_backward_vjp")
+            return dx, dgy
+        u, v, gy, au, av = ins
+        H = u.shape[-1] if u.dim() else 1
+        rows = u.numel() // H
+        du, dv, dgy = (torch.empty_like(u) if on else None for on in need)
+        _native.check(lib.bhg_gated_act_backward_vjp(k, rows, H, u.data_ptr(), H, v.data_ptr(), H, gy.data_ptr(), H, ptr(au), H, ptr(av), H,
+                                                     ptr(du), H, ptr(dv), H, ptr(dgy), H, _stream()), "bhg_gated_act_backward_vjp")
+        return du, dv, dgy
+
+
+_ACT_VJP_IMPL = [_act_vjp_hip]   # TEST HOOK ONLY (tests/test_declared_activations.py swaps in the float64 restatement to check the graph plumbing on CPU)
+
+
+class _ActBackward(torch.autograd.Function):
+    """(x, gy) -> gx = gy f'(x): an activation's backward as a graph node whose own backward is ONE fused call."""
+
+    @staticmethod
+    def forward(ctx, x, gy, y, kind, beta, threshold):
+        _ACT_CALLS["backward"] += 1
+        gy = gy.contiguous()
+        if kind == "glu":
+            gx = torch.ops.aten.glu_backward(gy, x, x.dim() - 1)
+        else:
+            gx = _act_backward_fn(kind, gy, x, y, beta, threshold)   # the backward the torch function itself runs: the same kernel
+        ctx.save_for_backward(x, gy)
+        ctx.kind, ctx.beta, ctx.threshold = kind, beta, threshold
+        ctx.set_materialize_grads(False)
+        return gx
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, a):
+        need = tuple(ctx.needs_input_grad[:2])
+        if a is None or not any(need):
+            return (None,) * 6
+        x, gy = ctx.saved_tensors
+        _ACT_CALLS["backward_vjp"] += 1
+        dx, dgy = _ACT_VJP_IMPL[0]("glu" if ctx.kind == "glu" else "plain", ctx.kind, (x, gy, a), need, ctx.beta, ctx.threshold)
+        return dx, dgy, None, None, None, None
+
+
+class _ActForward(torch.autograd.Function):
+    """An activation on the torch function's own kernel; its backward is the node above (so create_graph=True records THAT node)."""
+
+    @staticmethod
+    def forward(ctx, x, kind, beta, threshold):
+        _ACT_CALLS["forward"] += 1
+        y = _TORCH_GLU(x, -1) if kind == "glu" else _act_forward_fn(kind, x, beta, threshold)
+        ctx.save_for_backward(x, y if kind in ("tanh", "sigmoid") else None)
+        ctx.kind, ctx.beta, ctx.threshold = kind, beta, threshold
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, y = ctx.saved_tensors
+        return _ActBackward.apply(x, gy, None if y is None else y.detach(), ctx.kind, ctx.beta, ctx.threshold), None, None, None
+
+
+class _GatedActBackward(torch.autograd.Function):
+    """(u, v, gy) -> (gu, gv) = (gy f'(u) v, gy f(u)): the gated form's backward as a graph node whose own backward is ONE fused call."""
+
+    @staticmethod
+    def forward(ctx, u, v, gy, fu, kind):
+        _ACT_CALLS["backward"] += 1
+        gy = gy.contiguous()
+        gu = _act_backward_fn(kind, gy * v, u, fu, 1.0, 20.0)   # what autograd runs for act(u) * v: mul's backward, then the kind's
+        gv = gy * fu
+        ctx.save_for_backward(u, v, gy)
+        ctx.kind = kind
+        ctx.set_materialize_grads(False)
+        return gu, gv
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, au, av):
+        need = tuple(ctx.needs_input_grad[:3])
+        if (au is None and av is None) or not any(need):
+            return (None,) * 5
+        u, v, gy = ctx.saved_tensors
+        _ACT_CALLS["backward_vjp"] += 1
+        du, dv, dgy = _ACT_VJP_IMPL[0]("gated", ctx.kind, (u, v, gy, au, av), need)
+        return du, dv, dgy, None, None
+
+
+class _GatedActForward(torch.autograd.Function):
+    """act(gate) * up on the torch functions' own kernels; its backward is the node above."""
+
+    @staticmethod
+    def forward(ctx, u, v, kind):
+        _ACT_CALLS["forward"] += 1
+        fu = _act_forward_fn(kind, u, 1.0, 20.0)
+        ctx.save_for_backward(u, v, fu)
+        ctx.kind = kind
+        return fu * v
+
+    @staticmethod
+    def backward(ctx, gy):
+        u, v, fu = ctx.saved_tensors
+        gu, gv = _GatedActBackward.apply(u, v, gy, fu, ctx.kind)
+        return (gu if ctx.needs_input_grad[0] else None), (gv if ctx.needs_input_grad[1] else None), None
+
+
+def _act_declared(x) -> bool:
+    return (torch.is_grad_enabled() and torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()
+            and x.numel() >= _ACT_MIN_NUMEL and not x.is_nested)
+
+
+def gelu(input, approximate="none"):
+    """``torch.nn.functional.gelu`` whose double backward is one fused launch (comment above), for CUDA fp32 contiguous inputs of at
+    least one element with grad enabled.  Anything else IS the torch function with the caller's arguments, errors included.  Third
+    derivatives are not provided."""
+    if approximate not in ("none", "tanh") or not _act_declared(input):
+        return _TORCH_GELU(input, approximate=approximate)
+    return _ActForward.apply(input, "gelu" if approximate == "none" else "gelu_tanh", 1.0, 20.0)
+
+
+def silu(input, inplace=False):
+    """``torch.nn.functional.silu``, declared as :func:`gelu` is (``inplace=True`` keeps the torch path)."""
+    if inplace or not _act_declared(input):
+        return _TORCH_SILU(input, inplace=inplace)
+    return _ActForward.apply(input, "silu", 1.0, 20.0)
+
+
+def tanh(input):
+    """``torch.tanh``, declared as :func:`gelu` is."""
+    if not _act_declared(input):
+        return _TORCH_TANH(input)
+    return _ActForward.apply(input, "tanh", 1.0, 20.0)
+
+
+def sigmoid(input):
+    """``torch.sigmoid``, declared as :func:`gelu` is."""
+    if not _act_declared(input):
+        return _TORCH_SIGMOID(input)
+    return _ActForward.apply(input, "sigmoid", 1.0, 20.0)
+
+
+def softplus(input, beta=1.0, threshold=20.0):
+    """``torch.nn.functional.softplus``, declared as :func:`gelu` is, with ATen's linear branch where ``beta * x > threshold``."""
+    if not (_act_declared(input) and isinstance(beta, (int, float)) and isinstance(threshold, (int, float)) and beta != 0):
+        return _TORCH_SOFTPLUS(input, beta=beta, threshold=threshold)
+    return _ActForward.apply(input, "softplus", float(beta), float(threshold))
+
+
+def glu(input, dim=-1):
+    """``torch.nn.functional.glu`` on the last dimension, of even size, declared as :func:`gelu` is: the gated form with the logistic
+    function, the first half of a row the linear factor.  Any other ``dim`` keeps the torch path."""
+    if not (_act_declared(input) and isinstance(dim, int) and input.dim() >= 1 and dim in (-1, input.dim() - 1) and input.shape[-1] % 2 == 0):
+        return _TORCH_GLU(input, dim)
+    return _ActForward.apply(input, "glu", 1.0, 20.0)
+
+
+def gated_activation(gate, up, activation="silu"):
+    """``act(gate) * up`` — SwiGLU with ``"silu"``, GeGLU with ``"gelu"`` / ``"gelu_tanh"``, also ``"tanh"`` and ``"sigmoid"`` — whose
+    double backward is one fused launch, for two CUDA fp32 contiguous tensors of equal shape on one device with grad enabled.  Anything
+    else is the same expression in torch operations."""
+    if activation not in _ACT_GATED:
+        raise ValueError(f"gated_activation: activation must be one of {_ACT_GATED}, got {activation!r}")
+    if not (_act_declared(gate) and _act_declared(up) and gate.shape == up.shape and gate.device == up.device):
+        return _act_forward_fn(activation, gate, 1.0, 20.0) * up
+    return _GatedActForward.apply(gate, up, activation)
+
+
+class DeclaredGELU(torch.nn.GELU):
+    def forward(self, input):
+        return gelu(input, approximate=self.approximate)
+
+
+class DeclaredSiLU(torch.nn.SiLU):
+    def forward(self, input):
+        return silu(input, inplace=self.inplace)
+
+
+class DeclaredTanh(torch.nn.Tanh):
+    def forward(self, input):
+        return tanh(input)
+
+
+class DeclaredSigmoid(torch.nn.Sigmoid):
+    def forward(self, input):
+        return sigmoid(input)
+
+
+class DeclaredSoftplus(torch.nn.Softplus):
+    def forward(self, input):
+        return softplus(input, self.beta, self.threshold)
+
+
+class DeclaredGLU(torch.nn.GLU):
+    def forward(self, input):
+        return glu(input, self.dim)
+
+
+_ACT_MODULES = {torch.nn.GELU: DeclaredGELU, torch.nn.SiLU: DeclaredSiLU, torch.nn.Tanh: DeclaredTanh, torch.nn.Sigmoid: DeclaredSigmoid,
+                torch.nn.Softplus: DeclaredSoftplus, torch.nn.GLU: DeclaredGLU}
+
+
+def declare_activations_(module: torch.nn.Module) -> int:
+    """Declare every ``nn.GELU``, ``nn.SiLU``, ``nn.Tanh``, ``nn.Sigmoid``, ``nn.Softplus`` and ``nn.GLU`` of ``module`` (exact classes;
+    subclasses are left alone) in place: only the class changes.  ``nn.SiLU(inplace=True)`` and an ``nn.GLU`` on a dimension other than
+    -1 are left as they are.  ``nn.TransformerEncoderLayer`` / ``nn.TransformerDecoderLayer`` capture their activation function at
+    construction: where that attribute IS torch's ``F.gelu`` it is replaced by :func:`gelu`.  Returns how many were declared."""
+    n = 0
+    for m in module.modules():
+        cls = _ACT_MODULES.get(type(m))
+        if cls is not None:
+            if (cls is DeclaredSiLU and m.inplace) or (cls is DeclaredGLU and m.dim != -1):
+                continue
+            m.__class__ = cls
+            n += 1
+        elif type(m) in (torch.nn.TransformerEncoderLayer, torch.nn.TransformerDecoderLayer) and m.activation is _TORCH_GELU:
+            m.activation = gelu
+            n += 1
+    return n
+
+
+@contextlib.contextmanager
+def declared_activations():
+    """Inside the context ``torch.nn.functional.gelu`` / ``silu`` / ``softplus`` / ``glu`` are the functions above: ``nn.GELU``,
+    ``nn.SiLU``, ``nn.Softplus``, ``nn.GLU`` and model code that calls the torch functions reach the declaration without being rewritten
+    (``torch.tanh`` / ``torch.sigmoid`` and the Tensor methods are not patched: ``nn.Tanh`` / ``nn.Sigmoid`` are reached by
+    ``declare_activations_``, other code by calling :func:`tanh` / :func:`sigmoid`).  Only the forward that records the graph has to run
+    inside.  Restored on exit, exceptions included; nesting is safe."""
+    F = torch.nn.functional
+    previous = (F.gelu, F.silu, F.softplus, F.glu)
+    F.gelu, F.silu, F.softplus, F.glu = gelu, silu, softplus, glu
+    try:
+        yield
+    finally:
+        F.gelu, F.silu, F.softplus, F.glu = previous

@@ -735,6 +735,43 @@ int bhg_attention_tiled_backward_vjp(const float* q, const float* k, const float
                                      int causal, float scale, int B, int H, int L, int S, int d, float* dq, float* dk, float* dv,
                                      float* dgo, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- smooth activations, plain and gated: their share of a Hessian-vector product (csrc/bhg_activation.hip) ----------------------------
+ * Plain, y = f(x): the first backward is F : (x, gy) -> gx = gy f'(x).  bhg_act_backward_vjp is its vector-Jacobian product: for a
+ * cotangent a of gx,      dgy = a f'(x)      dx = a gy f''(x).
+ * Gated, y = f(u) v: the first backward is F : (u, v, gy) -> (gu, gv) = (gy f'(u) v, gy f(u)).  bhg_gated_act_backward_vjp: for
+ * cotangents au of gu and av of gv,
+ *      dgy = au f'(u) v + av f(u)      du = au gy f''(u) v + av gy f'(u)      dv = au gy f'(u).
+ * Kinds: erf GELU, tanh-approximated GELU, SiLU, tanh, the logistic function, and softplus(beta, threshold) with ATen's linear branch
+ * where beta x > threshold (plain only; `beta` and `threshold` are read by no other kind).  The derivatives are written without a
+ * subtraction from one (sech^2 and sg(x) sg(-x), from exp of a non-positive argument): finite for every finite x.
+ *
+ * ONE launch each: 256 threads per workgroup, grid = min(work / 256, 2048) and a grid-stride loop whose trip count is a function of the
+ * arguments alone; x, gy, a are read once and dx, dgy written once (20 bytes per element; gated 32).  fp32 arithmetic, 64-bit indexing,
+ * no atomics, no LDS, no workspace: bitwise deterministic.  Asynchronous on `stream`, no host synchronisation.
+ *   plain: n contiguous fp32 elements.  16-byte accesses when every non-NULL pointer is 16-byte aligned (the n % 4 tail in the same
+ *     launch), otherwise the scalar instance: misalignment is not a refusal.  dx or dgy may be NULL (not wanted: nothing is stored).
+ *   gated: element (r, j) of every array is ptr + r * ld + j, 0 <= j < H <= ld.  Contiguous arrays have ld = H; the halves of a glu
+ *     input x = [v | u] and of the cotangent of its gradient are one buffer at ld = 2 H, and du, dv may be the two halves of one dx.
+ *     au or av may be NULL (an absent cotangent: zero), not both; any output may be NULL.  16-byte accesses when H % 4 == 0, every
+ *     ld % 4 == 0 and every non-NULL pointer is 16-byte aligned; scalar otherwise.
+ * Refused with -1 and a message, before any device access: an unknown kind (softplus in the gated form); n, rows or H <= 0; ld < H;
+ * NULL x / gy / a resp. u / v / gy; every output NULL; au and av both NULL; more than 2^62 elements resp. rows * max ld > 2^62.
+ *
+ * The plan functions are host logic only (no launch, no device access), answered by the very functions the launches call, one line of
+ * `key=value` pairs: vec (4 or 1), block (256), grid, iters (trips of the grid-stride loop), inst (the kernel instance, templated on the
+ * kind), and units (plain: ceil(n / vec), one per thread and trip) resp. tpr (threads per row, a power of two), rows (256 / tpr rows side
+ * by side in a workgroup), cb (workgroups along a row: ceil(H / vec / tpr)), rgroups (ceil(rows / (256 / tpr))) and work (rgroups cb
+ * workgroup-sized pieces, one per workgroup and trip).  `aligned16` / `vec_ok`: the caller's statement that the pointers are 16-byte
+ * aligned (and, gated, that every ld is a multiple of 4).                                                                              */
+enum { BHG_ACT_GELU = 0, BHG_ACT_GELU_TANH = 1, BHG_ACT_SILU = 2, BHG_ACT_TANH = 3, BHG_ACT_SIGMOID = 4, BHG_ACT_SOFTPLUS = 5 };
+int bhg_act_plan(long long n, int aligned16, char* buf, size_t buf_bytes);
+int bhg_act_backward_vjp(int kind, float beta, float threshold, const float* x, const float* gy, const float* a, float* dx, float* dgy,
+                         long long n, void* stream);
+int bhg_gated_act_plan(long long rows, long long H, int vec_ok, char* buf, size_t buf_bytes);
+int bhg_gated_act_backward_vjp(int kind, long long rows, long long H, const float* u, long long ld_u, const float* v, long long ld_v,
+                               const float* gy, long long ld_gy, const float* au, long long ld_au, const float* av, long long ld_av,
+                               float* du, long long ld_du, float* dv, long long ld_dv, float* dgy, long long ld_dgy, void* stream);
+
 /* ---- finite-difference hypergradient of a ReLU-MLP inner problem (darts, SAMA; csrc/bhg_fd.hip) ------------------------------------
  * betty/hypergradient/darts.py:29-67 (sama.py:25-59 alike) for L_in = (1/B) sum_i s_lam(CE_i.detach()) * CE_i(w) (+ a ridge without lam):
  *   bhg_mlp_fd_forward  evaluates the network y = (... relu(x W_1^T + b_1) ...) W_L^T + b_L at w+ = w + eps v and w- = w+ - 2 eps v and
