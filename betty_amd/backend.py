@@ -495,6 +495,17 @@ def layernorm_plan(M: int, D: int) -> dict:
     return {k: int(v) for k, v in re.findall(r"(\w+)=(-?\d+)", buf.value.decode())}
 
 
+def rmsnorm_plan(M: int, D: int) -> dict:
+    """The launch geometry bhg_rmsnorm_backward_vjp takes for M rows of D elements, as a dict: ``vec`` (4: 16-byte accesses, 1: scalar),
+    ``tpr`` threads per row, ``rows`` rows side by side (one row group), ``nv`` vectors per thread (``inst``: of the kernel instance),
+    ``groups`` row groups in ``slices`` slices of ``gps`` groups (<= ``max_slices``: what fills the chip at the instance's register
+    count), ``ws`` bytes of workspace written when dgamma is wanted (include/bhg.h: bhg_rmsnorm_plan — host logic only: works on a box
+    without a GPU).  A shape the launch refuses raises."""
+    buf = ctypes.create_string_buffer(256)
+    _native.check(_native.load().bhg_rmsnorm_plan(int(M), int(D), buf, 256), "bhg_rmsnorm_plan")
+    return {k: int(v) for k, v in re.findall(r"(\w+)=(-?\d+)", buf.value.decode())}
+
+
 def groupnorm_plan(N: int, C: int, HW: int, G: int) -> dict:
     """The launch geometry bhg_groupnorm_backward_vjp takes for an [N, C, *spatial] input with HW spatial positions and G groups, as a
     dict: ``regime`` ("resident": rows of D <= 8192 elements held in registers, or "streamed"), ``D``, ``vec`` (4: 16-byte accesses, 1:

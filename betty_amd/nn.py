@@ -20,7 +20,8 @@ other dtypes, channels-last — it IS ``nn.BatchNorm2d``.  Third derivatives are
 ReLU -> depthwise k x k -> 1 x 1 -> BatchNorm2d; ``declare_layers_(module, depthwise=True)`` applies all three.  ``FusedLayerNorm``
 (at the end) is the same declaration for ``nn.LayerNorm`` — the normalisation of a transformer block;
 ``declare_layers_(module, layernorm=True)`` applies it; ``FusedGroupNorm`` / ``declare_layers_(module, groupnorm=True)`` do the same for
-``nn.GroupNorm``.  ``scaled_dot_product_attention`` / ``declared_attention()`` (last) declare the
+``nn.GroupNorm``, and ``FusedRMSNorm`` / ``declare_layers_(module, rmsnorm=True)`` / ``rms_norm`` / ``declared_rmsnorm()`` for
+``nn.RMSNorm``.  ``scaled_dot_product_attention`` / ``declared_attention()`` (last) declare the
 attention core for short sequences: a function and a context manager, because attention is not a module;
 ``tiled_scaled_dot_product_attention`` / ``declared_attention(tiled=True)`` extend it to 512 tokens (opt-in).  ``gelu``, ``silu``,
 ``tanh``, ``sigmoid``, ``softplus``, ``glu`` and ``gated_activation`` (at the very end) declare the smooth activations: functions,
@@ -39,7 +40,7 @@ from . import _native
 
 __all__ = ["FusedBatchNorm2d", "fuse_batchnorm_", "fused_batchnorm_calls", "PointwiseConv2d", "declare_pointwise_convs_", "DepthwiseConv2d",
            "declare_depthwise_convs_", "depthwise_conv_calls", "FusedLayerNorm", "fuse_layernorm_", "fused_layernorm_calls", "FusedGroupNorm", "fuse_groupnorm_",
-           "fused_groupnorm_calls", "declare_layers_",
+           "fused_groupnorm_calls", "FusedRMSNorm", "fuse_rmsnorm_", "fused_rmsnorm_calls", "rms_norm", "declared_rmsnorm", "declare_layers_",
            "scaled_dot_product_attention", "declared_attention", "declared_attention_calls", "tiled_scaled_dot_product_attention",
            "declared_attention_tiled_calls",
            "gelu", "silu", "tanh", "sigmoid", "softplus", "glu", "gated_activation", "declare_activations_", "declared_activations",
@@ -604,11 +605,189 @@ def fuse_groupnorm_(module: torch.nn.Module) -> int:
     return n
 
 
+# ---- FusedRMSNorm: the normalisation of a LLaMA-style pre-norm decoder block ---------------------------------------------------------------
+# On the GPU nn.RMSNorm runs aten::_fused_rms_norm, whose derivative formula switches to infinitely_differentiable_native_rms_norm_backward
+# as soon as grad mode is on: under create_graph=True even the first backward is a chain of element-wise operators, and the double
+# backward a longer one.  Declared, the layer's forward and first backward are ATen's single kernels (_fused_rms_norm /
+# _fused_rms_norm_backward), tied into the graph as two autograd.Function nodes as for layer norm, and the backward OF the backward node
+# is one bhg_rmsnorm_backward_vjp call (csrc/bhg_rmsnorm.hip): at most two launches.
+_RMS_CALLS = {"forward": 0, "backward": 0, "backward_vjp": 0}   # test / measurement hook: which nodes ran
+_RMS_MAX_D = 8192                                               # the family bhg_rmsnorm_backward_vjp takes: rows of at most 8192 elements
+_TORCH_RMS_NORM = torch.nn.functional.rms_norm                  # what anything outside the family IS
+
+
+def fused_rmsnorm_calls() -> dict:
+    return dict(_RMS_CALLS)
+
+
+_RMS_WS = {}   # (device, stream) -> scratch for the per-slice sums of dgamma
+
+
+def _rms_workspace(device, M, D, lib):
+    key = (str(device), int(torch.cuda.current_stream(device).cuda_stream))
+    n = int(lib.bhg_rmsnorm_ws_bytes(int(M), int(D)))
+    ws = _RMS_WS.get(key)
+    if ws is None or ws.numel() < n:
+        ws = _RMS_WS[key] = torch.empty(max(n, 1 << 16), dtype=torch.uint8, device=device)
+    return ws
+
+
+def _rms_vjp_hip(x, gy, a, gamma, rstd, b):
+    """(dx, dgy, dgamma) through bhg_rmsnorm_backward_vjp; dgamma is None when gamma is.  The product's only implementation: it raises
+    when the HIP extension is missing or the tensors are not on the GPU."""
+    if not x.is_cuda:
+        raise _native.NativeLibraryError("FusedRMSNorm's double backward needs CUDA/HIP tensors; there is no CPU fallback")
+    lib = _native.load()
+    M = rstd.numel()
+    D = x.numel() // M
+
+    def prep(t):
+        if t is None:
+            return None
+        t = t.detach()
+        return t if (t.dtype == torch.float32 and t.is_contiguous() and t.data_ptr() % 16 == 0) else t.to(torch.float32).contiguous().clone()
+
+    x, gy, a, gamma, rstd, b = (prep(t) for t in (x, gy, a, gamma, rstd, b))
+    if gamma is None:
+        b = None
+    dx, dgy = torch.empty_like(x), torch.empty_like(x)
+    dgamma = torch.empty_like(gamma) if gamma is not None else None
+    ptr = lambda t: None if t is None else t.data_ptr()   # noqa: E731
+    with torch.cuda.device(x.device):
+        ws = _rms_workspace(x.device, M, D, lib) if gamma is not None else None
+        _native.check(
+            lib.bhg_rmsnorm_backward_vjp(x.data_ptr(), gy.data_ptr(), ptr(a), ptr(gamma), rstd.data_ptr(), ptr(b), int(M), int(D),
+                                         dx.data_ptr(), dgy.data_ptr(), ptr(dgamma), ptr(ws), 0 if ws is None else ws.numel(), _stream()),
+            "bhg_rmsnorm_backward_vjp")
+    return dx, dgy, dgamma
+
+
+_RMS_VJP_IMPL = [_rms_vjp_hip]   # TEST HOOK ONLY (tests/test_fused_rmsnorm.py swaps in the float64 restatement to check the graph plumbing on CPU)
+
+
+class _RMSBackward(torch.autograd.Function):
+    """(x, gy, gamma) -> (gx, ggamma): RMS norm's backward as a graph node whose own backward is ONE fused call."""
+
+    @staticmethod
+    def forward(ctx, x, gy, gamma, rstd, normalized_shape, need_dx):
+        _RMS_CALLS["backward"] += 1
+        gy = gy.contiguous()
+        if x.is_cuda:
+            # the backward nn.RMSNorm itself runs without create_graph: one kernel, not the decomposition
+            gx, gg = torch.ops.aten._fused_rms_norm_backward(gy, x, normalized_shape, rstd, gamma, [bool(need_dx), gamma is not None])
+        else:
+            # _fused_rms_norm_backward has no CPU kernel: the closed form (csrc/bhg_rmsnorm.hip), for the CPU plumbing tests only — the
+            # module never declares a CPU input
+            xh = x * rstd
+            g = gy if gamma is None else gy * gamma
+            dims = tuple(range(x.dim() - len(normalized_shape), x.dim()))
+            gx = rstd * (g - xh * (g * xh).mean(dim=dims, keepdim=True)) if need_dx else None
+            gg = (gy * xh).reshape(-1, *normalized_shape).sum(0) if gamma is not None else None
+        ctx.save_for_backward(x, gy, gamma, rstd)
+        ctx.set_materialize_grads(False)
+        return (gx if need_dx else None), (gg if gamma is not None else None)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, a, b):
+        need = ctx.needs_input_grad
+        if (a is None and b is None) or not any(need[:3]):
+            return (None,) * 6
+        x, gy, gamma, rstd = ctx.saved_tensors
+        _RMS_CALLS["backward_vjp"] += 1
+        dx, dgy, dgamma = _RMS_VJP_IMPL[0](x, gy, a, gamma, rstd, b)
+        return (dx if need[0] else None), (dgy if need[1] else None), (dgamma if need[2] else None), None, None, None
+
+
+class _RMSForward(torch.autograd.Function):
+    """RMS norm on ATen's own kernel; its backward is the node above (so create_graph=True records THAT node)."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, normalized_shape, eps):
+        _RMS_CALLS["forward"] += 1
+        y, rstd = torch.ops.aten._fused_rms_norm(x, normalized_shape, gamma, eps)
+        ctx.save_for_backward(x, gamma, rstd)
+        ctx.normalized_shape = normalized_shape
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, gamma, rstd = ctx.saved_tensors
+        gx, gg = _RMSBackward.apply(x, gy, gamma, rstd, ctx.normalized_shape, ctx.needs_input_grad[0])
+        return gx, gg, None, None
+
+
+def _rms_declared(x, normalized_shape, weight) -> bool:
+    """Whether an RMS norm of ``x`` over ``normalized_shape`` with ``weight`` lies in the declared family (FusedRMSNorm's docstring)."""
+    if not (torch.is_grad_enabled() and torch.is_tensor(x) and isinstance(normalized_shape, (list, tuple))):
+        return False
+    ns = tuple(normalized_shape)
+    if not all(isinstance(v, int) for v in ns) or len(ns) == 0:
+        return False
+    D = 1
+    for v in ns:
+        D *= v
+    if not (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.data_ptr() % 16 == 0 and x.numel() > 0 and not x.is_nested):
+        return False
+    if not (1 <= D <= _RMS_MAX_D and x.dim() >= len(ns) and tuple(x.shape[x.dim() - len(ns):]) == ns):
+        return False                  # a shape mismatch: the torch function's own error
+    if weight is None:
+        return True
+    return (torch.is_tensor(weight) and weight.dtype == torch.float32 and weight.is_contiguous() and weight.device == x.device
+            and tuple(weight.shape) == ns)
+
+
+def rms_norm(input, normalized_shape, weight=None, eps=None):
+    """``torch.nn.functional.rms_norm`` whose double backward is fused (comment above): the hook for hand-written norm modules.  Declared
+    inside :class:`FusedRMSNorm`'s family; anything else IS the torch function with the caller's arguments, errors included."""
+    if not ((eps is None or isinstance(eps, (int, float))) and _rms_declared(input, normalized_shape, weight)):
+        return _TORCH_RMS_NORM(input, normalized_shape, weight, eps)
+    return _RMSForward.apply(input, weight, list(normalized_shape), None if eps is None else float(eps))
+
+
+class FusedRMSNorm(torch.nn.RMSNorm):
+    """``nn.RMSNorm`` whose double backward is fused (comment above).  Same parameters and ``state_dict`` (``elementwise_affine=False``
+    and ``eps=None`` included; a multi-dimensional ``normalized_shape`` is one row of its product); an input outside the declared family —
+    not CUDA fp32 contiguous and 16-byte aligned, more than 8192 normalised elements, zero elements, grad disabled, a weight on another
+    device or of another dtype — IS ``nn.RMSNorm``, errors included.  Third derivatives are not provided."""
+
+    def forward(self, x):
+        if not _rms_declared(x, tuple(self.normalized_shape), self.weight):
+            return super().forward(x)
+        return _RMSForward.apply(x, self.weight, list(self.normalized_shape), self.eps)
+
+
+def fuse_rmsnorm_(module: torch.nn.Module) -> int:
+    """Declare every ``nn.RMSNorm`` of ``module`` (exact class; subclasses are left alone) as :class:`FusedRMSNorm`, in place: same
+    parameters and hooks, only the class changes.  Returns how many layers were declared."""
+    n = 0
+    for m in module.modules():
+        if type(m) is torch.nn.RMSNorm:
+            m.__class__ = FusedRMSNorm
+            n += 1
+    return n
+
+
+@contextlib.contextmanager
+def declared_rmsnorm():
+    """Inside the context ``torch.nn.functional.rms_norm`` is :func:`rms_norm`: ``nn.RMSNorm`` and model code that calls the torch
+    function reach the declaration without being rewritten.  Only the forward that records the graph has to run inside.  Restored on
+    exit, exceptions included; nesting is safe."""
+    F = torch.nn.functional
+    previous = F.rms_norm
+    F.rms_norm = rms_norm
+    try:
+        yield
+    finally:
+        F.rms_norm = previous
+
+
 def declare_layers_(module: torch.nn.Module, depthwise: bool = False, layernorm: bool = False, groupnorm: bool = False,
-                    activations: bool = False) -> dict:
+                    activations: bool = False, rmsnorm: bool = False) -> dict:
     """Every layer declaration this module offers, in place: ``{"batchnorm": n, "pointwise_conv": m}``, with ``depthwise=True`` also
-    ``"depthwise_conv": k``, with ``layernorm=True`` also ``"layernorm": l``, with ``groupnorm=True`` also ``"groupnorm": g``, and with
-    ``activations=True`` also ``"activations": a`` (``declare_activations_``, further down)."""
+    ``"depthwise_conv": k``, with ``layernorm=True`` also ``"layernorm": l``, with ``groupnorm=True`` also ``"groupnorm": g``, with
+    ``activations=True`` also ``"activations": a`` (``declare_activations_``, further down), and with ``rmsnorm=True`` also
+    ``"rmsnorm": r``."""
     out = {"batchnorm": fuse_batchnorm_(module), "pointwise_conv": declare_pointwise_convs_(module)}
     if depthwise:
         out["depthwise_conv"] = declare_depthwise_convs_(module)
@@ -618,6 +797,8 @@ def declare_layers_(module: torch.nn.Module, depthwise: bool = False, layernorm:
         out["groupnorm"] = fuse_groupnorm_(module)
     if activations:
         out["activations"] = declare_activations_(module)
+    if rmsnorm:
+        out["rmsnorm"] = fuse_rmsnorm_(module)
     return out
 
 

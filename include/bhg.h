@@ -633,6 +633,40 @@ int bhg_layernorm_backward_vjp(const float* x, const float* gy, const float* a, 
                                const float* rstd, const float* b, const float* c, long long M, int D, float* dx, float* dgy,
                                float* dgamma, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- RMS normalisation inside an opaque Hessian-vector product (csrc/bhg_rmsnorm.hip) ----------------------------------------------------
+ * aten::_fused_rms_norm's derivative formula switches to infinitely_differentiable_native_rms_norm_backward as soon as grad mode is on:
+ * under create_graph=True the first backward is a chain of element-wise operators and the double backward a longer one.  This entry
+ * point is that derivative in at most two launches.  The layer: M rows of D contiguous fp32 elements, rstd = rsqrt(mean_j x^2 + eps),
+ * xh = x * rstd, y = gamma * xh; its first backward is
+ *     F : (x, gy, gamma) -> (gx, ggamma)      g = gamma * gy, gx = rstd * (g - xh * mean_j (g * xh)), ggamma_j = sum_i gy_ij xh_ij
+ * and for cotangents a (of gx, shaped like x; may be NULL = zero) and b (of ggamma, [D]; may be NULL):
+ *     dx, dgy (shaped like x, overwritten), dgamma ([D], overwritten; may be NULL)  =  d( <a, gx> + <b, ggamma> ) / d(x, gy, gamma)
+ * with rstd ([M], what the forward saved) treated as the function of x it is.  gamma may be NULL (elementwise_affine = False:
+ * gamma = 1); b and dgamma are then NULL too.  Every non-NULL output is overwritten in full (dgamma with zeros when a is absent).
+ * 1 <= D <= 8192 (a row is held in registers between its four fp64 row sums and its outputs: x, gy, a are read once), M >= 1.  x, gy, a,
+ * dx, dgy must be 16-byte aligned when D % 4 == 0 (16-byte accesses; scalar accesses otherwise); rstd, gamma, b, dgamma need their
+ * natural 4-byte alignment only.
+ * `ws`: bhg_rmsnorm_ws_bytes(M, D) bytes of scratch (0 for a shape outside the family), 8-byte aligned — the per-slice fp64 sums of
+ * dgamma, exactly slices * D * 8 bytes; read and written only when dgamma is wanted (NULL otherwise).  Refused with -1 and a message,
+ * before any device access: non-positive sizes, D > 8192, NULL x / gy / rstd / dx / dgy, b or dgamma without gamma, with dgamma a
+ * workspace that is NULL, too small or not 8-byte aligned, a row tensor that is not 16-byte aligned where that is required.
+ * Deterministic (row sums and dgamma in fp64, fixed order; no atomics), asynchronous on `stream`, no host synchronisation; 20
+ * algorithmic bytes per element.
+ *
+ * bhg_rmsnorm_plan is host logic only (no launch, no device access): the geometry the launches take for a shape, from the very
+ * function the launch path calls (closed form: nothing is searched), as one line of `key=value` pairs in buf: vec (4: 16-byte accesses,
+ * D % 4 == 0; 1: scalar), tpr (threads per row, a power of two in [1, 256]), rows (256 / tpr rows side by side: one row group), nv
+ * (vectors per thread and row) and inst (the vectors per thread of the kernel instance that runs: 2, 4, 8 resp. 2, 8, 32), groups (row
+ * groups), gps (row groups per slice), slices (workgroups of the row pass, <= max_slices, none empty: slice s is the rows
+ * [s gps rows, min(M, (s + 1) gps rows))), max_slices (256 CUs times the workgroups a CU holds at the instance's register count: 256
+ * to 2048, not layer norm's 64), ws (bytes of the workspace the call writes: slices * D * 8).  A slice holds at least 8 rows whenever
+ * there is more than one (gps * rows >= 8, so slices <= ceil(M / 8)): a slice costs 16 D bytes of partials, a row 20 D bytes.  A shape
+ * that bhg_rmsnorm_backward_vjp refuses is refused here with the same message.                                                           */
+size_t bhg_rmsnorm_ws_bytes(long long M, int D);
+int bhg_rmsnorm_plan(long long M, int D, char* buf, size_t buf_bytes);
+int bhg_rmsnorm_backward_vjp(const float* x, const float* gy, const float* a, const float* gamma, const float* rstd, const float* b,
+                             long long M, int D, float* dx, float* dgy, float* dgamma, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- group normalisation inside an opaque Hessian-vector product (csrc/bhg_groupnorm.hip) ----------------------------------------------
  * ATen's derivative formula for native_group_norm switches to infinitely_differentiable_native_group_norm_backward as soon as grad mode is
  * on: under create_graph=True the first backward is a chain of element-wise operators and the double backward a longer one.  This entry
