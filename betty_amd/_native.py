@@ -266,6 +266,13 @@ SYMBOLS = {
         [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_longlong, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
          c_size_t, c_void_p],
     ),
+    "bhg_cross_entropy_ws_bytes": (c_size_t, [ctypes.c_longlong, c_int, c_int]),
+    "bhg_cross_entropy_plan": (c_int, [ctypes.c_longlong, c_int, c_int, c_char_p, c_size_t]),
+    "bhg_cross_entropy_backward_vjp": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, ctypes.c_longlong, c_int, ctypes.c_longlong, c_void_p, c_void_p, c_void_p,
+         c_size_t, c_void_p],
+    ),
     "bhg_groupnorm_ws_bytes": (c_size_t, [ctypes.c_longlong, c_int]),
     "bhg_groupnorm_plan": (c_int, [ctypes.c_longlong, c_int, ctypes.c_longlong, c_int, c_char_p, c_size_t]),
     "bhg_groupnorm_backward_vjp": (

@@ -506,6 +506,19 @@ def rmsnorm_plan(M: int, D: int) -> dict:
     return {k: int(v) for k, v in re.findall(r"(\w+)=(-?\d+)", buf.value.decode())}
 
 
+def cross_entropy_plan(N: int, C: int, scalar_g: bool = False) -> dict:
+    """The launch geometry bhg_cross_entropy_backward_vjp takes for N rows of C classes, as a dict: ``regime`` ("short": several rows
+    side by side in a workgroup, "row": one row per workgroup, held in registers, or "split": a row over ``slices`` workgroups of
+    ``chunk`` elements, two launches), ``vec`` (4: 16-byte accesses, 1: scalar), ``tpr`` threads per row, ``rows`` rows side by side,
+    ``nv`` vectors per thread (``inst``: of the kernel instance; 0 when split), ``groups`` row groups, ``gps`` of them per workgroup,
+    ``wgs`` workgroups of the first launch, ``launches`` (2 with a scalar g: ``scalar_g``, the reductions "sum" and "mean"), ``ws`` bytes
+    of workspace (include/bhg.h: bhg_cross_entropy_plan — host logic only: works on a box without a GPU).  A shape the launch refuses
+    raises."""
+    buf = ctypes.create_string_buffer(256)
+    _native.check(_native.load().bhg_cross_entropy_plan(int(N), int(C), int(bool(scalar_g)), buf, 256), "bhg_cross_entropy_plan")
+    return {k: (int(v) if v.lstrip("-").isdigit() else v) for k, v in re.findall(r"(\w+)=(-?\w+)", buf.value.decode())}
+
+
 def groupnorm_plan(N: int, C: int, HW: int, G: int) -> dict:
     """The launch geometry bhg_groupnorm_backward_vjp takes for an [N, C, *spatial] input with HW spatial positions and G groups, as a
     dict: ``regime`` ("resident": rows of D <= 8192 elements held in registers, or "streamed"), ``D``, ``vec`` (4: 16-byte accesses, 1:

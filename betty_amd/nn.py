@@ -26,6 +26,8 @@ attention core for short sequences: a function and a context manager, because at
 ``tiled_scaled_dot_product_attention`` / ``declared_attention(tiled=True)`` extend it to 512 tokens (opt-in).  ``gelu``, ``silu``,
 ``tanh``, ``sigmoid``, ``softplus``, ``glu`` and ``gated_activation`` (at the very end) declare the smooth activations: functions,
 ``declared_activations()`` as a context manager and ``declare_activations_(module)`` / ``declare_layers_(module, activations=True)``.
+``cross_entropy`` / ``declared_cross_entropy()`` / ``DeclaredCrossEntropyLoss`` / ``declare_layers_(module, cross_entropy=True)`` (after
+them) declare the loss itself.
 """
 from __future__ import annotations
 
@@ -44,7 +46,8 @@ __all__ = ["FusedBatchNorm2d", "fuse_batchnorm_", "fused_batchnorm_calls", "Poin
            "scaled_dot_product_attention", "declared_attention", "declared_attention_calls", "tiled_scaled_dot_product_attention",
            "declared_attention_tiled_calls",
            "gelu", "silu", "tanh", "sigmoid", "softplus", "glu", "gated_activation", "declare_activations_", "declared_activations",
-           "declared_activation_calls", "DeclaredGELU", "DeclaredSiLU", "DeclaredTanh", "DeclaredSigmoid", "DeclaredSoftplus", "DeclaredGLU"]
+           "declared_activation_calls", "DeclaredGELU", "DeclaredSiLU", "DeclaredTanh", "DeclaredSigmoid", "DeclaredSoftplus", "DeclaredGLU",
+           "cross_entropy", "declared_cross_entropy", "declared_cross_entropy_calls", "DeclaredCrossEntropyLoss", "declare_cross_entropy_"]
 
 _CALLS = {"forward": 0, "backward": 0, "backward_vjp": 0}   # test / measurement hook: which nodes ran
 
@@ -783,11 +786,11 @@ def declared_rmsnorm():
 
 
 def declare_layers_(module: torch.nn.Module, depthwise: bool = False, layernorm: bool = False, groupnorm: bool = False,
-                    activations: bool = False, rmsnorm: bool = False) -> dict:
+                    activations: bool = False, rmsnorm: bool = False, cross_entropy: bool = False) -> dict:
     """Every layer declaration this module offers, in place: ``{"batchnorm": n, "pointwise_conv": m}``, with ``depthwise=True`` also
     ``"depthwise_conv": k``, with ``layernorm=True`` also ``"layernorm": l``, with ``groupnorm=True`` also ``"groupnorm": g``, with
     ``activations=True`` also ``"activations": a`` (``declare_activations_``, further down), and with ``rmsnorm=True`` also
-    ``"rmsnorm": r``."""
+    ``"rmsnorm": r``, and with ``cross_entropy=True`` also ``"cross_entropy": c`` (``declare_cross_entropy_``, at the very end)."""
     out = {"batchnorm": fuse_batchnorm_(module), "pointwise_conv": declare_pointwise_convs_(module)}
     if depthwise:
         out["depthwise_conv"] = declare_depthwise_convs_(module)
@@ -799,6 +802,8 @@ def declare_layers_(module: torch.nn.Module, depthwise: bool = False, layernorm:
         out["activations"] = declare_activations_(module)
     if rmsnorm:
         out["rmsnorm"] = fuse_rmsnorm_(module)
+    if cross_entropy:
+        out["cross_entropy"] = declare_cross_entropy_(module)
     return out
 
 
@@ -1371,3 +1376,187 @@ def declared_activations():
         yield
     finally:
         F.gelu, F.silu, F.softplus, F.glu = previous
+
+
+# ---- declared cross-entropy: the loss every opaque inner problem ends in -------------------------------------------------------------------
+# Under create_graph=True the first backward of F.cross_entropy is nll_loss_backward followed by _log_softmax_backward_data, and ATen
+# differentiates those two by a chain of element-wise and reduction operators over the whole [N, C] logit matrix.  Declared, the forward
+# (log_softmax, nll_loss_forward) and the first backward are ATen's own kernels, tied into the graph as two autograd.Function nodes as for
+# the norms, and the backward OF the backward node is one bhg_cross_entropy_backward_vjp call (csrc/bhg_cross_entropy.hip): at most two
+# launches.  What is saved is what torch saves — ATen's log_softmax output, the target and total_weight — and not the logits: the forward
+# node hands its log_softmax out as a second output that nothing but the backward node sees, and that output stands in for the logits
+# in the graph (its cotangent IS the logits': _CEForward.backward passes it through unchanged).
+_CE_CALLS = {"forward": 0, "backward": 0, "backward_vjp": 0}   # test / measurement hook: which nodes ran
+_CE_MAX_C = 262144                                              # the family bhg_cross_entropy_backward_vjp takes
+_TORCH_CROSS_ENTROPY = torch.nn.functional.cross_entropy        # what anything outside the family IS
+_CE_REDUCTIONS = {"none": 0, "mean": 1, "sum": 2}               # at::Reduction
+
+
+def declared_cross_entropy_calls() -> dict:
+    return dict(_CE_CALLS)
+
+
+_CE_WS = {}   # (device, stream) -> scratch for the per-slice sums of split rows and the per-workgroup sums of a scalar dg
+
+
+def _ce_workspace(device, n):
+    key = (str(device), int(torch.cuda.current_stream(device).cuda_stream))
+    ws = _CE_WS.get(key)
+    if ws is None or ws.numel() < n:
+        ws = _CE_WS[key] = torch.empty(max(n, 1 << 16), dtype=torch.uint8, device=device)
+    return ws
+
+
+def _ce_vjp_hip(lsm, y, g, a, denom, ignore_index, want):
+    """(dz, dg) through bhg_cross_entropy_backward_vjp, each None where ``want`` says so; g is [N] or 0-dim (then dg is 0-dim and denom,
+    one device float or None, divides g going in and dg going out).  The product's only implementation: it raises when the HIP extension
+    is missing or the tensors are not on the GPU."""
+    if not lsm.is_cuda:
+        raise _native.NativeLibraryError("the declared cross-entropy's double backward needs CUDA/HIP tensors; there is no CPU fallback")
+    lib = _native.load()
+    N, C = lsm.shape
+    scalar = g.dim() == 0
+
+    def prep(t):
+        t = t.detach()
+        return t if (t.dtype == torch.float32 and t.is_contiguous() and t.data_ptr() % 16 == 0) else t.to(torch.float32).contiguous().clone()
+
+    lsm, g, a = (prep(t) for t in (lsm, g, a))
+    y = y.detach().contiguous()
+    denom = None if denom is None else prep(denom)
+    dz = torch.empty_like(lsm) if want[0] else None
+    dg = torch.empty_like(g) if want[1] else None
+    ptr = lambda t: None if t is None else t.data_ptr()   # noqa: E731
+    with torch.cuda.device(lsm.device):
+        n = int(lib.bhg_cross_entropy_ws_bytes(int(N), int(C), int(scalar)))
+        ws = _ce_workspace(lsm.device, n) if n else None
+        _native.check(
+            lib.bhg_cross_entropy_backward_vjp(lsm.data_ptr(), y.data_ptr(), g.data_ptr(), int(scalar), ptr(denom), a.data_ptr(), int(N), int(C),
+                                               int(ignore_index), ptr(dz), ptr(dg), ptr(ws), 0 if ws is None else ws.numel(), _stream()),
+            "bhg_cross_entropy_backward_vjp")
+    return dz, dg
+
+
+_CE_VJP_IMPL = [_ce_vjp_hip]   # TEST HOOK ONLY (tests/test_declared_cross_entropy.py swaps in the float64 restatement to check the graph plumbing on CPU)
+
+
+class _CEBackward(torch.autograd.Function):
+    """(z, g) -> gz: cross-entropy's backward as a graph node whose own backward is ONE fused call.  ``z`` only links the graph (it is
+    whatever stands for the logits there; it is neither read nor saved)."""
+
+    @staticmethod
+    def forward(ctx, z, g, lsm, y, total_weight, reduction, ignore_index):
+        _CE_CALLS["backward"] += 1
+        g = g.contiguous()
+        lsm = lsm.detach()
+        gl = torch.ops.aten.nll_loss_backward(g, lsm, y, None, _CE_REDUCTIONS[reduction], ignore_index, total_weight)
+        gz = torch.ops.aten._log_softmax_backward_data(gl, lsm, 1, lsm.dtype)
+        ctx.save_for_backward(lsm, y, g, total_weight)
+        ctx.reduction, ctx.ignore_index = reduction, ignore_index
+        ctx.set_materialize_grads(False)
+        return gz
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, a):
+        need = ctx.needs_input_grad
+        if a is None or not (need[0] or need[1]):
+            return (None,) * 7
+        lsm, y, g, total_weight = ctx.saved_tensors
+        _CE_CALLS["backward_vjp"] += 1
+        denom = total_weight if ctx.reduction == "mean" else None
+        dz, dg = _CE_VJP_IMPL[0](lsm, y, g, a, denom, ctx.ignore_index, (bool(need[0]), bool(need[1])))
+        return (dz if need[0] else None), (dg if need[1] else None), None, None, None, None, None
+
+
+class _CEForward(torch.autograd.Function):
+    """Cross-entropy on ATen's own kernels; its backward is the node above (so create_graph=True records THAT node).  Returns
+    (loss, link): link is the saved log_softmax, handed out only so that the backward can reach the logits' place in the graph without
+    the logits being kept alive.  INTERNAL ONLY: link is a differentiable output whose derivative with respect to the logits is
+    treated as the identity, not log_softmax's Jacobian — it must reach nothing but _CEBackward, and :func:`cross_entropy` discards it."""
+
+    @staticmethod
+    def forward(ctx, z, y, reduction, ignore_index):
+        _CE_CALLS["forward"] += 1
+        lsm = torch.log_softmax(z, 1)
+        loss, total_weight = torch.ops.aten.nll_loss_forward(lsm, y, None, _CE_REDUCTIONS[reduction], ignore_index)
+        ctx.save_for_backward(lsm, y, total_weight)
+        ctx.reduction, ctx.ignore_index = reduction, ignore_index
+        ctx.set_materialize_grads(False)
+        return loss, lsm
+
+    @staticmethod
+    def backward(ctx, g, glink):
+        lsm, y, total_weight = ctx.saved_tensors
+        gz = None
+        if g is not None:
+            gz = _CEBackward.apply(lsm, g, lsm, y, total_weight, ctx.reduction, ctx.ignore_index)
+        if glink is not None:   # the cotangent of the logits' stand-in: the double backward's dz
+            gz = glink if gz is None else gz + glink
+        return gz, None, None, None
+
+
+def _ce_declared(input, target, weight, size_average, ignore_index, reduce, reduction, label_smoothing) -> bool:
+    """Whether a cross-entropy call lies in the declared family (:func:`cross_entropy`'s docstring)."""
+    if not (torch.is_grad_enabled() and torch.is_tensor(input) and torch.is_tensor(target)):
+        return False
+    if not (weight is None and size_average is None and reduce is None and reduction in _CE_REDUCTIONS):
+        return False
+    if not (isinstance(label_smoothing, (int, float)) and label_smoothing == 0.0 and isinstance(ignore_index, int) and not isinstance(ignore_index, bool)):
+        return False
+    if not (input.is_cuda and input.dtype == torch.float32 and input.dim() == 2 and input.is_contiguous() and input.data_ptr() % 16 == 0
+            and not input.is_nested):
+        return False
+    N, C = input.shape
+    if not (N >= 1 and 1 <= C <= _CE_MAX_C):
+        return False
+    return target.dtype == torch.int64 and target.dim() == 1 and target.shape[0] == N and target.device == input.device
+
+
+def cross_entropy(input, target, weight=None, size_average=None, ignore_index=-100, reduce=None, reduction="mean", label_smoothing=0.0):
+    """``torch.nn.functional.cross_entropy`` whose double backward is fused (comment above).  Loss and first gradient are ATen's own
+    kernels' (bit-equal to the torch function's).  Declared only when grad mode is on, ``input`` is CUDA fp32, 2-D ``[N, C]``, contiguous
+    and 16-byte aligned with ``N >= 1`` and ``1 <= C <= 262144``, ``target`` is int64 ``[N]`` on the same device (class indices),
+    ``weight is None``, ``label_smoothing == 0.0``, ``size_average`` and ``reduce`` are ``None`` and ``reduction`` is ``"none"``,
+    ``"mean"`` or ``"sum"``.  Anything else IS the torch function with the caller's arguments, errors included: probability targets,
+    class weights, label smoothing, ``[N, C, d1, ...]`` and unbatched ``[C]`` inputs, half and bfloat16 inputs, CPU tensors, the
+    deprecated ``size_average`` / ``reduce``, an unknown ``reduction``, grad mode off.  Third derivatives are not provided."""
+    if not _ce_declared(input, target, weight, size_average, ignore_index, reduce, reduction, label_smoothing):
+        return _TORCH_CROSS_ENTROPY(input, target, weight=weight, size_average=size_average, ignore_index=ignore_index, reduce=reduce,
+                                    reduction=reduction, label_smoothing=label_smoothing)
+    loss, _ = _CEForward.apply(input, target, reduction, ignore_index)
+    return loss
+
+
+class DeclaredCrossEntropyLoss(torch.nn.CrossEntropyLoss):
+    """``nn.CrossEntropyLoss`` whose double backward is fused: same arguments and buffers; a call outside :func:`cross_entropy`'s family
+    (class weights, label smoothing, ...) IS ``nn.CrossEntropyLoss``."""
+
+    def forward(self, input, target):
+        return cross_entropy(input, target, weight=self.weight, ignore_index=self.ignore_index, reduction=self.reduction,
+                             label_smoothing=self.label_smoothing)
+
+
+def declare_cross_entropy_(module: torch.nn.Module) -> int:
+    """Declare every ``nn.CrossEntropyLoss`` of ``module`` (exact class; subclasses are left alone) as :class:`DeclaredCrossEntropyLoss`,
+    in place: only the class changes.  Returns how many were declared."""
+    n = 0
+    for m in module.modules():
+        if type(m) is torch.nn.CrossEntropyLoss:
+            m.__class__ = DeclaredCrossEntropyLoss
+            n += 1
+    return n
+
+
+@contextlib.contextmanager
+def declared_cross_entropy():
+    """Inside the context ``torch.nn.functional.cross_entropy`` is :func:`cross_entropy`: ``nn.CrossEntropyLoss`` and model code that
+    calls the torch function reach the declaration without being rewritten.  Only the forward that records the graph has to run inside.
+    Restored on exit, exceptions included; nesting is safe."""
+    F = torch.nn.functional
+    previous = F.cross_entropy
+    F.cross_entropy = cross_entropy
+    try:
+        yield
+    finally:
+        F.cross_entropy = previous

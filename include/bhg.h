@@ -667,6 +667,40 @@ int bhg_rmsnorm_plan(long long M, int D, char* buf, size_t buf_bytes);
 int bhg_rmsnorm_backward_vjp(const float* x, const float* gy, const float* a, const float* gamma, const float* rstd, const float* b,
                              long long M, int D, float* dx, float* dgy, float* dgamma, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- cross-entropy inside an opaque Hessian-vector product (csrc/bhg_cross_entropy.hip) ---------------------------------------------------
+ * Under create_graph=True the first backward of F.cross_entropy is nll_loss_backward followed by _log_softmax_backward_data; ATen
+ * differentiates those two by a chain of element-wise and reduction operators over the whole [N, C] logit matrix.  This entry point is
+ * that double backward in at most two launches.  Per row i: lsm_i = log_softmax(z_i) (what the forward saved), P = exp(lsm), target
+ * y_i, m_i = [y_i != ignore_index and 0 <= y_i < C]; the first backward is
+ *     F : (z, g) -> gz      gz_ic = g_i m_i (P_ic - [c = y_i])
+ * and for the cotangent a of gz ([N, C]), with s_i = sum_c P_ic a_ic:
+ *     dz_ic = g_i m_i P_ic (a_ic - s_i)        dg_i = m_i (s_i - a_{i, y_i})
+ * g is [N] (reduction "none"), or ONE element when g_is_scalar ("sum", "mean"); dg is then one element too, sum_i dg_i.  `denom` (may be
+ * NULL) is one device float — nll_loss_forward's total_weight — that divides g going in and the scalar dg going out: "mean" without a
+ * host synchronisation (only with g_is_scalar).  dz ([N, C]) and dg may each be NULL: a NULL output is neither computed nor written;
+ * every non-NULL output is overwritten in full.  An ignored row writes zeros and reads neither lsm nor a; a target outside [0, C) is
+ * never used as an index.  1 <= C <= 262144, N >= 1.  lsm, a and dz must be 16-byte aligned when C % 4 == 0 (16-byte accesses; scalar
+ * accesses otherwise); y needs 8-byte, g / denom / dg 4-byte alignment.
+ * `ws`: bhg_cross_entropy_ws_bytes(N, C, g_is_scalar) bytes of scratch (0 where none is needed or for a shape outside the family),
+ * 8-byte aligned: the per-slice fp64 partials of s_i (split rows) followed by the per-workgroup fp64 partials of the scalar dg (only
+ * touched when dg is wanted).  Refused with -1 and a message, before any device access: non-positive sizes, C > 262144, NULL lsm / y /
+ * g / a, both outputs NULL, denom without g_is_scalar, a needed workspace that is NULL, too small or not 8-byte aligned, lsm / a / dz
+ * not 16-byte aligned where that is required.  Deterministic (row sums in fp64, fixed order; no atomics), asynchronous on `stream`, no
+ * host synchronisation; 12 algorithmic bytes per element (read lsm, read a, write dz).
+ *
+ * bhg_cross_entropy_plan is host logic only (no launch, no device access): the geometry the launches take, from the very function the
+ * launch path calls (closed form), as one line of `key=value` pairs in buf: regime (short: several rows side by side in a workgroup;
+ * row: one row per workgroup, held in registers; split: a row over `slices` workgroups, two launches), vec (4 / 1), tpr (threads per
+ * row, short regime; 256 otherwise), rows (rows per workgroup), nv (vectors per thread and row) and inst (the kernel instance's vectors
+ * per thread; 0 in the split regime), slices and chunk (split regime: workgroups per row and elements per slice, chunk a multiple of
+ * 1024; 1 and C otherwise), wgs (workgroups of the first launch, <= max_wgs), launches, ws (bytes of workspace).  A shape that
+ * bhg_cross_entropy_backward_vjp refuses is refused here with the same message.                                                          */
+size_t bhg_cross_entropy_ws_bytes(long long N, int C, int g_is_scalar);
+int bhg_cross_entropy_plan(long long N, int C, int g_is_scalar, char* buf, size_t buf_bytes);
+int bhg_cross_entropy_backward_vjp(const float* lsm, const long long* y, const float* g, int g_is_scalar, const float* denom,
+                                   const float* a, long long N, int C, long long ignore_index, float* dz, float* dg, void* ws,
+                                   size_t ws_bytes, void* stream);
+
 /* ---- group normalisation inside an opaque Hessian-vector product (csrc/bhg_groupnorm.hip) ----------------------------------------------
  * ATen's derivative formula for native_group_norm switches to infinitely_differentiable_native_group_norm_backward as soon as grad mode is
  * on: under create_graph=True the first backward is a chain of element-wise operators and the double backward a longer one.  This entry
