@@ -206,6 +206,8 @@ SYMBOLS = {
     "bhg_mlp_timeout_flag_dev": (c_void_p, [POINTER(Mlp), c_void_p]),
     "bhg_mlp_head_j_dev": (c_void_p, [POINTER(Mlp), c_void_p, POINTER(c_int), POINTER(c_int)]),
     "bhg_mlp_head_j_t2h_dev": (c_void_p, [POINTER(Mlp), c_void_p, POINTER(c_int)]),
+    "bhg_mlp_rb0_copy_dev": (c_void_p, [POINTER(Mlp), c_void_p, POINTER(c_int)]),
+    "bhg_mlp_t2_dots":(c_int, [c_int, _PP, _PP, POINTER(c_int), POINTER(c_int), c_int, c_void_p, POINTER(c_int), c_void_p]),
     "bhg_mlp_stage_batch": (c_int, [POINTER(Mlp), c_void_p, c_void_p, c_void_p, c_void_p]),
     "bhg_mlp_supports_packed_prepare": (c_int, [POINTER(Mlp)]),
     "bhg_mlp_forward_packed": (c_int, [POINTER(Mlp), _PP, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),

@@ -26,6 +26,7 @@
 
 #include "bhg_common.hpp"
 #include "bhg_mlp_headj.hpp"   // the head launch in its head_j form: device code in bhg_mlp_headj.hip
+#include "bhg_mlp_tail.hpp"    // the closing launch of a solve's last iteration: device code in bhg_mlp_tail.hip
 
 #ifdef BHG_STAMPS
 namespace bhg { __device__ unsigned long long* d_stamps = nullptr; }
@@ -596,9 +597,10 @@ struct FusedWs {
   // head_j (bhg_mlp_headj.hpp): J = W_3 diag(mask_2) W_2 per sample, [round32(Bp C)][d_2], built once per solve from the packed
   // operand hj_Ap [d_3 / 16][round32(B C)][16]; nT2j: T2h partials of the head launch's tiles, appended to partT2 (0: the form cannot apply)
   float* hj_J; float* hj_Ap; int nT2j;
-  // ... with 16 x 16 tiles T2h arrives by pairs of tiles instead: two buffers of Bp doubles, one per iteration parity (adjacent: one
-  // memset clears both, once per solve); the tiles of iteration k add into hj_t2h[k & 1], its head rows clear the other one
+  // ... with 16 x 16 tiles T2h arrives by pairs of tiles instead: two buffers of Bp doubles, one per iteration parity (adjacent: the
+  // solve's set-up launch clears both, once per solve); the tiles of iteration k add into hj_t2h[k & 1], its head rows clear the other one
   double* hj_t2h[2];
+  bool rb0c_set;                    // this solve's set-up launch (build_head_j) left r|b0 in the hoist region's copy: iteration 0 skips its own
   size_t bytes;
 };
 // The shapes the head_j form takes — where lin_head applies (plan_solve adds the solver's own conditions): L = 4, <= 12 classes, last
@@ -708,10 +710,20 @@ int pack_operands(const bhg_mlp* m, const FusedWs& w, hipStream_t st, bool weigh
 
 // head_j: J = A W_2 once per solve — A[b C + c][k] = W_3[c][k] mask_2[b][k] packed by k_headj_pack, then the backward product through
 // W_2 (the chain's own k_wskpc on Wb[L-2]) with round32(B C) rows instead of the padded batch; row-major output, rows >= B C zero.
-int build_head_j(const bhg_mlp* m, const FusedWs& w, hipStream_t st) {
+// The pack launch also does the solve's two small set-up chores (key head_j_setup = 0: a memset and a copy of the runtime instead): both
+// parities of the pair slots of T2h start a solve at zero (bhg_mlp_headj.hpp: t2pair), and k_graw's tiles of iteration 0 read r|b0 from
+// the copy rb0c.  The slice is final here — the caller's init kernel wrote it (a right-hand side taken in place leaves the bias slices
+// explicit, bhg_mlp_cg_state_mask) — and nothing before iteration 0's closing launch writes either side: k_hoist and its reduce read
+// the residual, the first product runs without update blocks, and rb0c is a region of its own inside the hoist scratch.
+int build_head_j(const bhg_mlp* m, FusedWs* ws, const float* rb0, float* rb0c, hipStream_t st) {
+  const FusedWs& w = *ws;
   const int L = m->L, C = m->dims[L], K = m->dims[L - 1], N = m->dims[L - 2], RA = headj_rows(m->B, C);
   BHG_REQUIRE(w.nT2j > 0 && w.hj_J && w.hj_Ap && w.Wb[L - 2], "the head_j form was planned for a net it cannot take");
-  if (int rc = launch_headj_pack(m->W[L - 1], m->mask[L - 2], w.hj_Ap, m->B, C, K, RA, st)) return rc;
+  const bool setup = dbg(DBG_head_j_setup, 1) != 0;
+  const bool pairs = head_j_tile(m) == 2;
+  if (int rc = launch_headj_pack(m->W[L - 1], m->mask[L - 2], w.hj_Ap, m->B, C, K, RA, (setup && pairs) ? w.hj_t2h[0] : nullptr, 2 * m->Bp,
+                                 setup ? rb0 : nullptr, rb0c, m->dims[1], st)) return rc;
+  ws->rb0c_set = setup;
   WskpBuilder wb;
   WskpProb q{};
   q.Ap = w.hj_Ap; q.Bq = w.Wb[L - 2]; q.RA = RA; q.RB = N; q.K = K; q.B = m->B * C; q.nsplit = 1;
@@ -719,8 +731,7 @@ int build_head_j(const bhg_mlp* m, const FusedWs& w, hipStream_t st) {
   wb.add(q);
   wb.launch(st);
   BHG_HIP_CHECK(hipGetLastError());
-  // both parities of the pair slots of T2h start a solve at zero (bhg_mlp_headj.hpp: t2pair)
-  if (head_j_tile(m) == 2) BHG_HIP_CHECK(hipMemsetAsync(w.hj_t2h[0], 0, sizeof(double) * 2 * m->Bp, st));
+  if (pairs && !setup) BHG_HIP_CHECK(hipMemsetAsync(w.hj_t2h[0], 0, sizeof(double) * 2 * m->Bp, st));
   return BHG_OK;
 }
 
@@ -943,7 +954,7 @@ int lin_first_product(const bhg_mlp* m, const void* const* dir, const ChainMode&
 #endif
   hipLaunchKernelGGL((k_wskpl<2, 4, false>), dim3(grid), dim3(64 * kWskpWaves), 0, st, la);
   ++g_lin_launches;
-  if (cm.first)   // r|b0 as k_graw's tiles will read it (its bias blocks update the slice in the same launch)
+  if (cm.first && !cm.ws->rb0c_set)   // r|b0 as k_graw's tiles will read it (its bias blocks update the slice in the same launch)
     BHG_HIP_CHECK(hipMemcpyAsync(hbase + hp->rb0c_off, cm.fa + cm.starts[1], sizeof(float) * (size_t)m->dims[1],
                                  hipMemcpyDeviceToDevice, st));
   return BHG_OK;
@@ -1094,10 +1105,23 @@ int hoist_head(const bhg_mlp* m, const void* const* dir, const ChainMode& cm, co
   return BHG_OK;
 }
 
-void hoist_backward(const bhg_mlp* m, const ChainMode& cm, const ChainPlan& pl, hipStream_t st, int staged_mink) {
+int hoist_backward(const bhg_mlp* m, const ChainMode& cm, const ChainPlan& pl, hipStream_t st, int staged_mink) {
   const int L = m->L, Bp = m->Bp, B = m->B;
   const HoistPlan* hp = pl.hp;
   float* hbase = pl.hoist;
+  // The last iteration of a solve without a solution vector ends with its step length (chain_close): Rd_{l-1} is dead, and all the
+  // products below would leave behind is T2_l — which never needed them (bhg_mlp_tail.hpp).  One launch for every layer's dot product,
+  // on the operands the products' epilogues would have read, into the same slots.  (key cg_last_backward = 1: the products, as before)
+  if (pl.cg && cm.skip_outputs && cm.gphase == 0 && dbg(DBG_cg_last_backward, 0) == 0) {
+    T2DotsLaunch t{};
+    for (int l = L - 2; l >= 1; --l) {
+      t.gb[t.n] = hbase + hp->g_off[hp->gb[l]]; t.rh[t.n] = m->Rh[l - 1];
+      t.RA[t.n] = Bp; t.RB[t.n] = m->dims[l]; t.t2_off[t.n] = cm.ws->t2_off[l];
+      ++t.n;
+    }
+    t.B = B; t.partT2 = cm.ws->partT2;
+    return launch_t2_dots(t, st);
+  }
   // backward chain: Rd_{l-1} = mask_{l-1} * (Rd_l W_l + Gb_l); T2_l = 2 <Gb_l, Rh_{l-1}> from the tile epilogue
   for (int l = L - 2; l >= 1; --l) {
     const int K = m->dims[l + 1], N = m->dims[l];
@@ -1129,6 +1153,7 @@ void hoist_backward(const bhg_mlp* m, const ChainMode& cm, const ChainPlan& pl, 
     if (pl.cg) { w.rh = m->Rh[l - 1]; w.partT2 = cm.ws->partT2 + cm.ws->t2_off[l]; }
     launch_gemm_wsk<LAYOUT_RC>(w, st, K >= staged_mink);
   }
+  return BHG_OK;
 }
 
 // The whole R-chain in its hoisted form.  (projected Neumann's closing pass stops after the head: Rz(v_K) is in the accumulator then)
@@ -1137,7 +1162,8 @@ int chain_hoisted(const bhg_mlp* m, const void* const* dir, const ChainMode& cm,
   const int staged_mink = dbg(DBG_hoist_staged_mink, 256);
   if (int rc = hoist_forward(m, dir, cm, pl, st, staged_mink, cs)) return rc;
   if (int rc = hoist_head(m, dir, cm, pl, st, cs)) return rc;
-  if (!cm.stop_after_head) hoist_backward(m, cm, pl, st, staged_mink);
+  if (!cm.stop_after_head)
+    if (int rc = hoist_backward(m, cm, pl, st, staged_mink)) return rc;
   return BHG_OK;
 }
 
@@ -1797,6 +1823,17 @@ double* bhg_mlp_head_j_t2h_dev(const bhg_mlp* m, void* fws, int* doubles) {
   return w.hj_t2h[0];
 }
 
+float* bhg_mlp_rb0_copy_dev(const bhg_mlp* m, void* fws, int* floats) {
+  if (!mlp_desc_ok(m) || !fws) return nullptr;
+  FusedWs w;
+  carve_fused_ws(m, fws, &w);
+  HoistPlan hp;
+  hoist_plan(m, &hp);
+  if (!hp.ok || !hp.lin_ok) return nullptr;
+  if (floats) *floats = m->dims[1];
+  return w.hoist + hp.rb0c_off;
+}
+
 size_t bhg_mlp_fused_ws_bytes(const bhg_mlp* m) {
   if (!mlp_desc_ok(m)) return 0;
   FusedWs w;
@@ -1947,7 +1984,7 @@ int bhg_mlp_cg_solve_rhs(const bhg_mlp* m, float* x, float* r, float* p, const i
   if (c.plan.hoist && c.plan.packed && !m->prepacked)   // (prepacked: bhg_mlp_forward_packed / _backward_packed left the packed operands)
     if (int rc = pack_operands(m, c.w, st)) return rc;
   if (c.plan.head_j && K >= 2)   // (the projected iterations 1 .. K-1 read J)
-    if (int rc = build_head_j(m, c.w, st)) return rc;
+    if (int rc = build_head_j(m, &c.w, r + starts[1], c.w.hoist + c.plan.hp.rb0c_off, st)) return rc;
   for (int k = 0; k < K; ++k)
     if (int rc = cg_iteration(&c, k, 0, nullptr, 1.0, st)) return rc;
   BHG_HIP_CHECK(hipGetLastError());

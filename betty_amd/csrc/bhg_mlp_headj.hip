@@ -214,8 +214,17 @@ __global__ __launch_bounds__(256) void k_headj(HeadjArgs g) {
 }
 
 // A[b C + c][k] = W_3[c][k] mask_2[b][k] in the packed layout [K / 16][RA][16]: one float4 of the output per thread (k_pack's indexing)
+// Ahead of its share, workgroup 0 clears `zero` and workgroup 1 (0 in a launch of one) copies csrc to cdst: what a memset and a copy of
+// the runtime did in two launches of their own on the solve's dependent chain.  Nothing in this launch reads either.
 __global__ __launch_bounds__(256) void k_headj_pack(const float* __restrict__ W3, const float* __restrict__ mask2, float* __restrict__ Ap,
-                                                    const int B, const int C, const int K, const int RA) {
+                                                    const int B, const int C, const int K, const int RA, double* __restrict__ zero,
+                                                    const int nzero, const float* __restrict__ csrc, float* __restrict__ cdst,
+                                                    const int ncopy4) {
+  if (zero && blockIdx.x == 0)
+    for (int i = threadIdx.x; i < nzero; i += 256) zero[i] = 0.0;
+  if (csrc && blockIdx.x == (gridDim.x > 1 ? 1u : 0u))
+    for (int i = threadIdx.x; i < ncopy4; i += 256)
+      reinterpret_cast<f32x4*>(cdst)[i] = reinterpret_cast<const f32x4*>(csrc)[i];
   const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
   const int64_t total = (int64_t)RA * K / 4;
   if (idx >= total) return;
@@ -272,10 +281,15 @@ int launch_headj(const HeadjLaunch& a, hipStream_t st) {
   return BHG_OK;
 }
 
-int launch_headj_pack(const float* W3, const float* mask2, float* Ap, int B, int C, int K, int RA, hipStream_t st) {
-  BHG_REQUIRE(W3 && mask2 && Ap && B >= 1 && C >= 1 && K % 16 == 0 && RA % 32 == 0 && RA >= B * C, "bad arguments");
+int launch_headj_pack(const float* W3, const float* mask2, float* Ap, int B, int C, int K, int RA, double* zero, int nzero,
+                      const float* csrc, float* cdst, int ncopy, hipStream_t st) {
+  BHG_REQUIRE(W3 && mask2 && Ap && B >= 1 && C >= 1 && K >= 16 && K % 16 == 0 && RA >= 32 && RA % 32 == 0 && RA >= B * C, "bad arguments");
+  BHG_REQUIRE(!zero || nzero >= 0, "bad size of the buffer to clear");
+  BHG_REQUIRE(!csrc || (cdst && ncopy >= 0 && ncopy % 4 == 0 && (((uintptr_t)csrc | (uintptr_t)cdst) & 15) == 0),
+              "the slice to copy must be 16-byte aligned, its length a multiple of 4");
   const int64_t total = (int64_t)RA * K / 4;
-  hipLaunchKernelGGL(k_headj_pack, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, W3, mask2, Ap, B, C, K, RA);
+  hipLaunchKernelGGL(k_headj_pack, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, W3, mask2, Ap, B, C, K, RA, zero, nzero, csrc,
+                     cdst, ncopy / 4);
   return BHG_OK;
 }
 

@@ -53,6 +53,9 @@ inline int headj_tile_shape(int rows, int K, int B) {
 int launch_headj(const HeadjLaunch& a, hipStream_t st);
 
 // A[b C + c][k] = W_3[c][k] mask_2[b][k], packed [K / 16][RA][16] (RA = round32(B C); rows >= B C zero) for J = A W_2
-int launch_headj_pack(const float* W3, const float* mask2, float* Ap, int B, int C, int K, int RA, hipStream_t st);
+// Two set-up chores of a solve ride in its first workgroups: zero[0 .. nzero) = 0.0 (the pair slots of T2h; NULL: not asked for) and
+// cdst[0 .. ncopy) = csrc (r|b0 for iteration 0's closing launch; csrc NULL: not asked for; ncopy % 4 == 0, both 16-byte aligned)
+int launch_headj_pack(const float* W3, const float* mask2, float* Ap, int B, int C, int K, int RA, double* zero, int nzero,
+                      const float* csrc, float* cdst, int ncopy, hipStream_t st);
 
 }  // namespace bhg

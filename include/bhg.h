@@ -514,6 +514,18 @@ const float* bhg_mlp_head_j_dev(const bhg_mlp* m, void* fws, int* rows, int* col
  * pairs of tiles in two buffers of Bp doubles inside `fws`, one per iteration parity, which every solve clears before its first use.
  * Device address of the first (the second follows it), *doubles = 2 Bp.  NULL where the head_j form does not apply.  For tests.      */
 double* bhg_mlp_head_j_t2h_dev(const bhg_mlp* m, void* fws, int* doubles);
+/* The six-launch forms keep a copy of the residual's first-bias slice inside `fws` for the closing launch of an iteration (its tiles read
+ * the copy while its bias blocks update the slice); every solve writes it before its first use — in the head_j form the solve's set-up
+ * launch does, together with the clearing of the pair buffers above.  Device address, *floats = dims[1]; NULL where no six-launch form
+ * applies.  For tests; reads nothing on the device.                                                                                   */
+float* bhg_mlp_rb0_copy_dev(const bhg_mlp* m, void* fws, int* floats);
+/* The closing launch of the last iteration of bhg_mlp_cg_solve without a solution vector, on its own (csrc/bhg_mlp_tail.hpp): nothing
+ * reads that iteration's R-backward products, so only the second-order shares T2_l = 2 <Gb_l(p), Rh_{l-1}(p)> of p.Hp are formed — for
+ * n <= BHG_MLP_MAX_LAYERS layers in one launch.  gb[i], rh[i]: fp32 [RA[i]][RB[i]] row-major, 16-byte aligned (RA, RB multiples of 32);
+ * only rows < B are read.  Layer i owns the (RA[i] / 32) (RB[i] / 32) doubles of partT2 from t2_off[i]: every one of them is written
+ * (fp64 partials in a fixed order, or 0.0), their sum is T2_i, and nothing else is touched.  For tests; asynchronous on `stream`.      */
+int bhg_mlp_t2_dots(int n, const float* const* gb, const float* const* rh, const int* RA, const int* RB, int B, double* partT2,
+                    const int* t2_off, void* stream);
 
 /* ---- closed-form meta-weight-net (round 5; csrc/bhg_mwn.hip) --------------------------------------------------------------------
  * The UPPER problem of data reweighting (examples/learning_to_reweight/model.py:98-111 `MLP(hidden_size, num_layers = 1)`, called at
