@@ -304,6 +304,14 @@ SYMBOLS = {
          POINTER(ctypes.c_longlong), c_int, c_float, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
          c_size_t, c_void_p],
     ),
+    "bhg_attention_wide_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "bhg_attention_wide_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_char_p, c_size_t]),
+    "bhg_attention_wide_backward_vjp": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(ctypes.c_longlong), c_void_p,
+         POINTER(ctypes.c_longlong), c_int, c_float, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+         c_size_t, c_void_p],
+    ),
 }
 
 _libs = {}          # path -> bound CDLL

@@ -23,7 +23,8 @@ ReLU -> depthwise k x k -> 1 x 1 -> BatchNorm2d; ``declare_layers_(module, depth
 ``nn.GroupNorm``, and ``FusedRMSNorm`` / ``declare_layers_(module, rmsnorm=True)`` / ``rms_norm`` / ``declared_rmsnorm()`` for
 ``nn.RMSNorm``.  ``scaled_dot_product_attention`` / ``declared_attention()`` (last) declare the
 attention core for short sequences: a function and a context manager, because attention is not a module;
-``tiled_scaled_dot_product_attention`` / ``declared_attention(tiled=True)`` extend it to 512 tokens (opt-in).  ``gelu``, ``silu``,
+``tiled_scaled_dot_product_attention`` / ``declared_attention(tiled=True)`` extend it to 512 tokens (opt-in), and
+``wide_scaled_dot_product_attention`` / ``declared_attention(wide=True)`` to heads of 65 to 128 elements (opt-in).  ``gelu``, ``silu``,
 ``tanh``, ``sigmoid``, ``softplus``, ``glu`` and ``gated_activation`` (at the very end) declare the smooth activations: functions,
 ``declared_activations()`` as a context manager and ``declare_activations_(module)`` / ``declare_layers_(module, activations=True)``.
 ``cross_entropy`` / ``declared_cross_entropy()`` / ``DeclaredCrossEntropyLoss`` / ``declare_layers_(module, cross_entropy=True)`` (after
@@ -44,7 +45,7 @@ __all__ = ["FusedBatchNorm2d", "fuse_batchnorm_", "fused_batchnorm_calls", "Poin
            "declare_depthwise_convs_", "depthwise_conv_calls", "FusedLayerNorm", "fuse_layernorm_", "fused_layernorm_calls", "FusedGroupNorm", "fuse_groupnorm_",
            "fused_groupnorm_calls", "FusedRMSNorm", "fuse_rmsnorm_", "fused_rmsnorm_calls", "rms_norm", "declared_rmsnorm", "declare_layers_",
            "scaled_dot_product_attention", "declared_attention", "declared_attention_calls", "tiled_scaled_dot_product_attention",
-           "declared_attention_tiled_calls",
+           "declared_attention_tiled_calls", "wide_scaled_dot_product_attention", "declared_attention_wide_calls",
            "gelu", "silu", "tanh", "sigmoid", "softplus", "glu", "gated_activation", "declare_activations_", "declared_activations",
            "declared_activation_calls", "DeclaredGELU", "DeclaredSiLU", "DeclaredTanh", "DeclaredSigmoid", "DeclaredSoftplus", "DeclaredGLU",
            "cross_entropy", "declared_cross_entropy", "declared_cross_entropy_calls", "DeclaredCrossEntropyLoss", "declare_cross_entropy_"]
@@ -836,15 +837,22 @@ def _attn_vjp_hip(q, k, v, go, aq, ak, av, mask, causal, scale, need):
     """(dq, dk, dv, dgo) through bhg_attention_backward_vjp; ``need`` says which of the four are wanted (the others are None).  Strided
     views are handed in as they are.  The product's only implementation: it raises when the HIP extension is missing or the tensors are
     not on the GPU."""
-    return _attn_vjp_launch(q, k, v, go, aq, ak, av, mask, causal, scale, need, False)
+    return _attn_vjp_launch(q, k, v, go, aq, ak, av, mask, causal, scale, need, None)
 
 
 def _attn_tiled_vjp_hip(q, k, v, go, aq, ak, av, mask, causal, scale, need):
     """The same through bhg_attention_tiled_backward_vjp (L, S <= 512): two launches and a workspace cached per (device, stream)."""
-    return _attn_vjp_launch(q, k, v, go, aq, ak, av, mask, causal, scale, need, True)
+    return _attn_vjp_launch(q, k, v, go, aq, ak, av, mask, causal, scale, need, "bhg_attention_tiled")
 
 
-def _attn_vjp_launch(q, k, v, go, aq, ak, av, mask, causal, scale, need, tiled):
+def _attn_wide_vjp_hip(q, k, v, go, aq, ak, av, mask, causal, scale, need):
+    """The same through bhg_attention_wide_backward_vjp (L, S <= 512, 65 <= d <= 128): two launches and the same cached workspace."""
+    return _attn_vjp_launch(q, k, v, go, aq, ak, av, mask, causal, scale, need, "bhg_attention_wide")
+
+
+def _attn_vjp_launch(q, k, v, go, aq, ak, av, mask, causal, scale, need, family):
+    """``family`` picks the entry point: None for bhg_attention_backward_vjp, otherwise the prefix of a sibling with a workspace
+    (``<family>_ws_bytes`` and ``<family>_backward_vjp``)."""
     if not q.is_cuda:
         raise _native.NativeLibraryError("declared attention's double backward needs CUDA/HIP tensors; there is no CPU fallback")
     lib = _native.load()
@@ -876,12 +884,12 @@ def _attn_vjp_launch(q, k, v, go, aq, ak, av, mask, causal, scale, need, tiled):
     outs = [torch.empty(sh, dtype=torch.float32, device=q.device) if on else None for on, sh in zip(need, (lshape, sshape, sshape, lshape))]
     ptr = lambda t: None if t is None else t.data_ptr()   # noqa: E731
     with torch.cuda.device(q.device):
-        if tiled:
-            ws = _attn_tiled_workspace(q.device, int(lib.bhg_attention_tiled_ws_bytes(B, H, L)))
+        if family:
+            ws = _attn_tiled_workspace(q.device, int(getattr(lib, family + "_ws_bytes")(B, H, L)))
             _native.check(
-                lib.bhg_attention_tiled_backward_vjp(*(ptr(t) for t in ins), strides, ptr(mask), mstrides, 1 if causal else 0, float(scale),
-                                                     B, H, L, S, d, *(ptr(t) for t in outs), ws.data_ptr(), ws.numel(), _stream()),
-                "bhg_attention_tiled_backward_vjp")
+                getattr(lib, family + "_backward_vjp")(*(ptr(t) for t in ins), strides, ptr(mask), mstrides, 1 if causal else 0, float(scale),
+                                                       B, H, L, S, d, *(ptr(t) for t in outs), ws.data_ptr(), ws.numel(), _stream()),
+                family + "_backward_vjp")
         else:
             _native.check(
                 lib.bhg_attention_backward_vjp(*(ptr(t) for t in ins), strides, ptr(mask), mstrides, 1 if causal else 0, float(scale), B, H, L,
@@ -989,9 +997,44 @@ class _AttnTiledForward(_AttnForward):
         return gq, gk, gv, None, None, None
 
 
-def _declared_mask(q, k, v, attn_mask, dropout_p, is_causal, kw, max_len=_ATTN_MAX):
-    """False when the call is outside the declared family (at most ``max_len`` queries and keys); otherwise the additive fp32 mask as a
-    (B, H, L, S) view, or None."""
+# Head widths 65 .. 128 (opt-in): the same two nodes again, whose double backward is ONE bhg_attention_wide_backward_vjp call
+# (csrc/bhg_attention_wide.hip: 64 x 16 score tiles in the query launch, 32 x 32 in the key launch, the same workspace).
+_ATTN_WIDE_CALLS = {"forward": 0, "backward": 0, "backward_vjp": 0}
+_ATTN_WIDE_MAX_D = 128
+_ATTN_WIDE_MAX = 256   # the largest measured length up to which no measured shape is slower declared (profiles/attention_wide_double_backward.txt)
+_ATTN_WIDE_VJP_IMPL = [_attn_wide_vjp_hip]   # TEST HOOK ONLY (tests/test_declared_attention_wide.py swaps in the float64 restatement)
+
+
+def declared_attention_wide_calls() -> dict:
+    return dict(_ATTN_WIDE_CALLS)
+
+
+class _AttnWideBackward(_AttnBackward):
+    @staticmethod
+    def forward(ctx, q, k, v, go, P, mask, causal, scale):
+        return _attn_first_backward(ctx, _ATTN_WIDE_CALLS, q, k, v, go, P, mask, causal, scale)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, aq, ak, av):
+        return _attn_double_backward(ctx, _ATTN_WIDE_CALLS, _ATTN_WIDE_VJP_IMPL, aq, ak, av)
+
+
+class _AttnWideForward(_AttnForward):
+    @staticmethod
+    def forward(ctx, q, k, v, mask, causal, scale):
+        return _attn_forward(ctx, _ATTN_WIDE_CALLS, q, k, v, mask, causal, scale)
+
+    @staticmethod
+    def backward(ctx, go):
+        q, k, v, P, mask = ctx.saved_tensors
+        gq, gk, gv = _AttnWideBackward.apply(q, k, v, go, P, mask, ctx.causal, ctx.scale)
+        return gq, gk, gv, None, None, None
+
+
+def _declared_mask(q, k, v, attn_mask, dropout_p, is_causal, kw, max_len=_ATTN_MAX, max_d=_ATTN_MAX):
+    """False when the call is outside the declared family (at most ``max_len`` queries and keys, at most ``max_d`` elements per head);
+    otherwise the additive fp32 mask as a (B, H, L, S) view, or None."""
     if kw.pop("enable_gqa", False) or kw:
         return False
     if not (torch.is_grad_enabled() and dropout_p == 0.0 and all(torch.is_tensor(t) for t in (q, k, v))):
@@ -1002,7 +1045,7 @@ def _declared_mask(q, k, v, attn_mask, dropout_p, is_causal, kw, max_len=_ATTN_M
     S = k.shape[2]
     if not (tuple(k.shape) == (B, H, S, d) and tuple(v.shape) == (B, H, S, d) and B >= 1 and H >= 1 and B * H < 2 ** 31):
         return False
-    if not (1 <= L <= max_len and 1 <= S <= max_len and 1 <= d <= _ATTN_MAX):
+    if not (1 <= L <= max_len and 1 <= S <= max_len and 1 <= d <= max_d):
         return False
     if d > 1 and not all(t.stride(3) == 1 for t in (q, k, v)):
         return False
@@ -1045,16 +1088,33 @@ def tiled_scaled_dot_product_attention(query, key, value, attn_mask=None, dropou
     return node.apply(query, key, value, mask, bool(is_causal), s)
 
 
+def wide_scaled_dot_product_attention(query, key, value, attn_mask=None, dropout_p=0.0, is_causal=False, scale=None, **kw):
+    """``tiled_scaled_dot_product_attention`` above, whose declared family also takes 65 to ``_ATTN_WIDE_MAX_D`` (128) elements per head
+    at up to ``_ATTN_WIDE_MAX`` queries and keys (every other condition as above).  With at most 64 elements per head it IS the function
+    above: the same nodes, the same counters.  Wider, the double backward is one bhg_attention_wide_backward_vjp call, counted by
+    ``declared_attention_wide_calls()``.  Anything else IS the torch function with the caller's arguments, errors included."""
+    if not (torch.is_tensor(query) and query.dim() == 4 and query.shape[-1] > _ATTN_MAX):
+        return tiled_scaled_dot_product_attention(query, key, value, attn_mask=attn_mask, dropout_p=dropout_p, is_causal=is_causal, scale=scale,
+                                                  **kw)
+    mask = _declared_mask(query, key, value, attn_mask, dropout_p, is_causal, dict(kw), _ATTN_WIDE_MAX, _ATTN_WIDE_MAX_D)
+    if mask is False:
+        return _TORCH_SDPA(query, key, value, attn_mask=attn_mask, dropout_p=dropout_p, is_causal=is_causal, scale=scale, **kw)
+    s = 1.0 / math.sqrt(query.shape[-1]) if scale is None else float(scale)
+    return _AttnWideForward.apply(query, key, value, mask, bool(is_causal), s)
+
+
 @contextlib.contextmanager
-def declared_attention(tiled: bool = False):
+def declared_attention(tiled: bool = False, wide: bool = False):
     """Inside the context ``torch.nn.functional.scaled_dot_product_attention`` is the function above: ``nn.MultiheadAttention``,
     ``nn.TransformerEncoder`` and model code that calls the torch function reach the declaration without being rewritten, and
     ``sdpa_kernel(MATH)`` is not needed for shapes in the family.  ``tiled=True`` installs ``tiled_scaled_dot_product_attention``
-    instead (sequences of up to ``_ATTN_TILED_MAX`` tokens).  Only the forward that records the graph has to run inside; the
+    instead (sequences of up to ``_ATTN_TILED_MAX`` tokens), ``wide=True`` ``wide_scaled_dot_product_attention`` (that, and heads of up
+    to ``_ATTN_WIDE_MAX_D`` elements).  Only the forward that records the graph has to run inside; the
     solve's double backward runs wherever it runs.  Restored on exit, exceptions included; nesting is safe."""
     F = torch.nn.functional
     previous = F.scaled_dot_product_attention
-    F.scaled_dot_product_attention = tiled_scaled_dot_product_attention if tiled else scaled_dot_product_attention
+    F.scaled_dot_product_attention = (wide_scaled_dot_product_attention if wide else
+                                      tiled_scaled_dot_product_attention if tiled else scaled_dot_product_attention)
     try:
         yield
     finally:

@@ -9,7 +9,8 @@ training_step stays OPAQUE — the Hessian-vector products are autograd's double
   * the RMS norms with `betty_amd.nn.declare_layers_(net, rmsnorm=True)`: one bhg_rmsnorm_backward_vjp call per layer and product
     (csrc/bhg_rmsnorm.hip, at most two launches) instead of ATen's decomposition;
   * the attention core by running the forward inside `betty_amd.nn.declared_attention()`, which F.scaled_dot_product_attention(...,
-    is_causal=True) then reaches (`tiled=True` for sequences of more than 64 tokens);
+    is_causal=True) then reaches (`tiled=True` for sequences of more than 64 tokens; `wide=True` for heads of more than 64 elements,
+    `--width 256 --heads 2` for LLaMA's 128);
   * SwiGLU by calling `betty_amd.nn.gated_activation(gate, up, "silu")` where the block would have written F.silu(gate) * up.
 
     python examples/llama_block_declared.py --k 5 --iters 10 [--undeclared]
@@ -60,7 +61,8 @@ class Decoder(nn.Module):
         if not DECLARED[0]:   # the fused SDPA kernels have no double backward: the math path
             with torch.nn.attention.sdpa_kernel(torch.nn.attention.SDPBackend.MATH):
                 return self.head(self.norm(self.blocks(self.embed(tokens)))[:, -1])
-        with bnn.declared_attention(tiled=tokens.shape[1] > 64):   # only the forward that records the graph has to run inside
+        wide = self.embed.embedding_dim // self.blocks[0].heads > 64
+        with bnn.declared_attention(tiled=tokens.shape[1] > 64, wide=wide):   # only the forward that records the graph has to run inside
             return self.head(self.norm(self.blocks(self.embed(tokens)))[:, -1])
 
 
@@ -98,6 +100,8 @@ def main():
     ap.add_argument("--batch", type=int, default=16)
     ap.add_argument("--tokens", type=int, default=24)
     ap.add_argument("--blocks", type=int, default=2)
+    ap.add_argument("--width", type=int, default=64)
+    ap.add_argument("--heads", type=int, default=4)
     ap.add_argument("--undeclared", action="store_true", help="leave every layer undeclared (the A/B arm)")
     args = ap.parse_args()
     DECLARED[0] = not args.undeclared
@@ -112,7 +116,7 @@ def main():
         return x, torch.where(flip, torch.randint(0, classes, (args.batch,), generator=g), y)
 
     train, clean = [make(0.5) for _ in range(8)], [make(0.0) for _ in range(4)]
-    net, mwn = Decoder(vocab=vocab, blocks=args.blocks, classes=classes), MWN()
+    net, mwn = Decoder(vocab=vocab, width=args.width, heads=args.heads, blocks=args.blocks, classes=classes), MWN()
     declared = bnn.declare_layers_(net, rmsnorm=True) if DECLARED[0] else {}
     cfg = Config(type=args.algo, unroll_steps=1, cg_iterations=args.k, cg_alpha=1.0, neumann_iterations=args.k, neumann_alpha=0.05)
     upper = Reweight(name="reweight", module=mwn, optimizer=torch.optim.Adam(mwn.parameters(), lr=1e-3), train_data_loader=clean, config=Config())
@@ -120,6 +124,7 @@ def main():
     engine = Engine(config=EngineConfig(train_iters=args.iters), problems=[upper, inner],
                     dependencies={"u2l": {upper: [inner]}, "l2u": {inner: [upper]}})
     c0 = (bnn.fused_rmsnorm_calls(), bnn.declared_attention_calls(), bnn.declared_activation_calls())
+    wide0 = bnn.declared_attention_wide_calls()["backward_vjp"]
     t0 = time.perf_counter()
     engine.run()
     if torch.cuda.is_available():
@@ -131,6 +136,8 @@ def main():
     print(f"LLaMA-style decoder, {args.blocks} blocks, declared {declared.get('rmsnorm', 0)} RMS norms{'' if DECLARED[0] else ' (nothing)'}, "
           f"{args.algo} K={args.k}: {upper.count} upper steps in {dt:.2f} s; fused double-backward calls: RMS norm {rms}, attention {attn}, "
           f"SwiGLU {act}; meta-weight-net finite {finite}")
+    if args.width // args.heads > 64:
+        print(f"heads of {args.width // args.heads} elements: wide attention double-backward calls {bnn.declared_attention_wide_calls()['backward_vjp'] - wide0}")
 
 
 if __name__ == "__main__":

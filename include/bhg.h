@@ -815,6 +815,31 @@ int bhg_attention_tiled_backward_vjp(const float* q, const float* k, const float
                                      int causal, float scale, int B, int H, int L, int S, int d, float* dq, float* dk, float* dv,
                                      float* dgo, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- the attention core for head widths 65 .. 128: the wide sibling (csrc/bhg_attention_wide.hip) ---------------------------------------
+ * The same vector-Jacobian product, the same quantities, arguments, workspace and two-launch scheme as
+ * bhg_attention_tiled_backward_vjp, for 1 <= L, S <= 512 and 65 <= d <= 128 (LLaMA-style heads of 128 elements).  At dp = 128 the
+ * sibling's tiles do not fit one CU, so each launch has a tiling of its own:
+ *   1  grid B H ceil(L / 64): 64 resident query rows x 16 streamed keys per score tile (bm x bn, pitch ps = 20): a wave owns 16 rows, so a
+ *      row's five online statistics stay inside one wave; (a) the online pass, (b) dq and dgo (skipped when both are NULL);
+ *   2  grid B H ceil(S / 32): 32 resident keys x 32 streamed queries (kbn x kbm, pitch kps = 36), the statistics read from the workspace;
+ *      dk and dv (not launched when both are NULL).
+ * Causal tile skipping, dead key tiles, fully masked rows (NaN), exact-fp32 MFMA products, fp64 statistics, determinism and the
+ * workspace layout (bhg_attention_wide_ws_bytes(B, H, L) = 40 B H L bytes, 8-byte aligned) are those of the tiled sibling.
+ * Refused with -1 and a message, before any device access: everything the tiled sibling refuses, with its words, except that d < 65 is
+ * "fewer than 65 elements per head" (it names the two siblings that take d <= 64) and the upper limit is "more than 128 elements per
+ * head".
+ *
+ * bhg_attention_wide_plan is host logic only, answered by the very function the launch calls, one line of `key=value` pairs: vec, bm = 64,
+ * bn = 16, ps = 20, kbm = 32, kbn = 32, kps = 36, dp (d rounded up to 16), pd = dp + 4, grid_q and grid_k, lds_q =
+ * 4 ((3 bm + 4 bn) pd + 4 bm ps) and lds_k = 4 ((3 kbm + 4 kbn) pd + 3 kbm kps) (bytes of dynamic LDS of the two launches: 155648 and
+ * 132096 at dp = 128, <= max_lds = 163840), ws (bytes).                                                                                   */
+size_t bhg_attention_wide_ws_bytes(int B, int H, int L);
+int bhg_attention_wide_plan(int B, int H, int L, int S, int d, int vec_ok, char* buf, size_t buf_bytes);
+int bhg_attention_wide_backward_vjp(const float* q, const float* k, const float* v, const float* go, const float* aq, const float* ak,
+                                    const float* av, const long long* strides, const float* mask, const long long* mask_strides,
+                                    int causal, float scale, int B, int H, int L, int S, int d, float* dq, float* dk, float* dv,
+                                    float* dgo, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- smooth activations, plain and gated: their share of a Hessian-vector product (csrc/bhg_activation.hip) ----------------------------
  * Plain, y = f(x): the first backward is F : (x, gy) -> gx = gy f'(x).  bhg_act_backward_vjp is its vector-Jacobian product: for a
  * cotangent a of gx,      dgy = a f'(x)      dx = a gy f''(x).
