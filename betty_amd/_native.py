@@ -312,6 +312,18 @@ SYMBOLS = {
          POINTER(ctypes.c_longlong), c_int, c_float, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
          c_size_t, c_void_p],
     ),
+    "bhg_attention_fused_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "bhg_attention_fused_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_char_p, c_size_t]),
+    "bhg_attention_fused_forward": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, POINTER(ctypes.c_longlong), c_void_p, POINTER(ctypes.c_longlong), c_int, c_float, c_int, c_int, c_int,
+         c_int, c_int, c_void_p, c_void_p, c_void_p],
+    ),
+    "bhg_attention_fused_backward": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(ctypes.c_longlong), c_void_p, POINTER(ctypes.c_longlong), c_int,
+         c_float, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p],
+    ),
 }
 
 _libs = {}          # path -> bound CDLL

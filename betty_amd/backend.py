@@ -580,6 +580,18 @@ def attention_tiled_plan(B: int, H: int, L: int, S: int, d: int, vec_ok: bool = 
     return {k: int(v) for k, v in re.findall(r"(\w+)=(-?\d+)", buf.value.decode())}
 
 
+def attention_fused_plan(B: int, H: int, L: int, S: int, d: int, vec_ok: bool = True) -> dict:
+    """What bhg_attention_fused_forward / bhg_attention_fused_backward take for B x H heads of L <= 512 queries, S <= 512 keys and
+    d <= 64 elements, as a dict: ``vec``, ``bm`` x ``bn``, ``ps``, ``dp``, ``pd`` (as for the tiled sibling), ``grid_f`` / ``grid_q`` /
+    ``grid_k`` and ``lds_f`` / ``lds_q`` / ``lds_k`` (workgroups and bytes of dynamic LDS of the forward and of the backward's query and
+    key launches), ``stats`` (bytes of saved row statistics per query row) and ``ws`` (bytes of the backward's workspace)
+    (include/bhg.h: bhg_attention_fused_plan — host logic only).  A shape the launches refuse raises."""
+    buf = ctypes.create_string_buffer(256)
+    _native.check(_native.load().bhg_attention_fused_plan(int(B), int(H), int(L), int(S), int(d), 1 if vec_ok else 0, buf, 256),
+                  "bhg_attention_fused_plan")
+    return {k: int(v) for k, v in re.findall(r"(\w+)=(-?\d+)", buf.value.decode())}
+
+
 def attention_wide_plan(B: int, H: int, L: int, S: int, d: int, vec_ok: bool = True) -> dict:
     """What bhg_attention_wide_backward_vjp takes for B x H heads of L <= 512 queries, S <= 512 keys and 65 <= d <= 128 elements, as a
     dict: ``vec``, ``bm`` x ``bn`` / ``ps`` (queries x keys and row pitch of a score tile of the query launch), ``kbm`` x ``kbn`` / ``kps``

@@ -24,7 +24,9 @@ ReLU -> depthwise k x k -> 1 x 1 -> BatchNorm2d; ``declare_layers_(module, depth
 ``nn.RMSNorm``.  ``scaled_dot_product_attention`` / ``declared_attention()`` (last) declare the
 attention core for short sequences: a function and a context manager, because attention is not a module;
 ``tiled_scaled_dot_product_attention`` / ``declared_attention(tiled=True)`` extend it to 512 tokens (opt-in), and
-``wide_scaled_dot_product_attention`` / ``declared_attention(wide=True)`` to heads of 65 to 128 elements (opt-in).  ``gelu``, ``silu``,
+``wide_scaled_dot_product_attention`` / ``declared_attention(wide=True)`` to heads of 65 to 128 elements (opt-in);
+``fused_scaled_dot_product_attention`` / ``declared_attention(fused=True)`` give the tiled family a native forward and first backward
+that save no probability matrix (opt-in).  ``gelu``, ``silu``,
 ``tanh``, ``sigmoid``, ``softplus``, ``glu`` and ``gated_activation`` (at the very end) declare the smooth activations: functions,
 ``declared_activations()`` as a context manager and ``declare_activations_(module)`` / ``declare_layers_(module, activations=True)``.
 ``cross_entropy`` / ``declared_cross_entropy()`` / ``DeclaredCrossEntropyLoss`` / ``declare_layers_(module, cross_entropy=True)`` (after
@@ -46,6 +48,7 @@ __all__ = ["FusedBatchNorm2d", "fuse_batchnorm_", "fused_batchnorm_calls", "Poin
            "fused_groupnorm_calls", "FusedRMSNorm", "fuse_rmsnorm_", "fused_rmsnorm_calls", "rms_norm", "declared_rmsnorm", "declare_layers_",
            "scaled_dot_product_attention", "declared_attention", "declared_attention_calls", "tiled_scaled_dot_product_attention",
            "declared_attention_tiled_calls", "wide_scaled_dot_product_attention", "declared_attention_wide_calls",
+           "fused_scaled_dot_product_attention", "declared_attention_fused_calls",
            "gelu", "silu", "tanh", "sigmoid", "softplus", "glu", "gated_activation", "declare_activations_", "declared_activations",
            "declared_activation_calls", "DeclaredGELU", "DeclaredSiLU", "DeclaredTanh", "DeclaredSigmoid", "DeclaredSoftplus", "DeclaredGLU",
            "cross_entropy", "declared_cross_entropy", "declared_cross_entropy_calls", "DeclaredCrossEntropyLoss", "declare_cross_entropy_"]
@@ -1032,6 +1035,104 @@ class _AttnWideForward(_AttnForward):
         return gq, gk, gv, None, None, None
 
 
+# Fused forward and first backward (opt-in): two nodes that call bhg_attention_fused_forward / bhg_attention_fused_backward
+# (csrc/bhg_attention_fused.hip: 64 x 32 score tiles on the MFMA, the online softmax, O in registers).  The forward saves O and two floats
+# per query row (row maximum, denominator) and never P; the backward node's own backward is still _attn_double_backward — the short
+# kernel up to 64 tokens, the tiled one beyond — because those kernels take (q, k, v, gO) and recompute their statistics.  O and the
+# statistics enter the backward node detached: D = rowsum(gO * O) = rowsum(P * gP), and that dependence on q, k, v is inside the fused
+# vector-Jacobian product, as P's is for the nodes above.  No CPU fallback.
+_ATTN_FUSED_CALLS = {"forward": 0, "backward": 0, "backward_vjp": 0}
+_ATTN_FUSED_MAX = 512   # the largest measured length up to which no measured shape is slower fused (profiles/attention_fused_first_backward.txt)
+
+
+def declared_attention_fused_calls() -> dict:
+    return dict(_ATTN_FUSED_CALLS)
+
+
+def _attn_fused_operand(t, shape):
+    """``t`` as the fused kernels read it in place: fp32, ``shape``, unit last stride, 16-byte aligned (a copy only where it is not)."""
+    t = t.detach()
+    if t.dtype != torch.float32:
+        t = t.to(torch.float32)
+    if tuple(t.shape) != shape:
+        t = t.expand(shape)
+    if (shape[3] > 1 and t.stride(3) != 1) or t.data_ptr() % 16 != 0:
+        t = t.contiguous() if not t.is_contiguous() else t.clone()
+    return t
+
+
+def _attn_fused_launch(entry, ins, stats, mask, causal, scale, outs, tail=()):
+    """One call of ``entry`` (bhg_attention_fused_forward / _backward): the inputs with their strides (the saved statistics behind them,
+    for the backward), the mask in place, then the outputs."""
+    if not ins[0].is_cuda:
+        raise _native.NativeLibraryError("declared attention's fused forward and backward need CUDA/HIP tensors; there is no CPU fallback")
+    lib = _native.load()
+    B, H, L, d = ins[0].shape
+    S = ins[1].shape[2]
+    strides = (ctypes.c_longlong * (4 * len(ins)))()
+    for i, t in enumerate(ins):
+        strides[4 * i:4 * i + 4] = list(t.stride())
+    mstrides = None
+    if mask is not None:
+        mask = mask.detach()
+        mstrides = (ctypes.c_longlong * 4)(*mask.stride())
+    ptr = lambda t: None if t is None else t.data_ptr()   # noqa: E731
+    with torch.cuda.device(ins[0].device):
+        _native.check(
+            getattr(lib, entry)(*(ptr(t) for t in ins), *(ptr(t) for t in stats), strides, ptr(mask), mstrides, 1 if causal else 0,
+                                float(scale), B, H, L, S, d, *(ptr(t) for t in outs), *tail, _stream()), entry)
+
+
+class _AttnFusedBackward(torch.autograd.Function):
+    """(q, k, v, go, O, stats) -> (gq, gk, gv) in one bhg_attention_fused_backward call (``need``: which of the three are wanted, the
+    others are None); its own backward is ONE fused call of the existing double backward."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, go, O, stats, mask, causal, scale, need):
+        _ATTN_FUSED_CALLS["backward"] += 1
+        B, H, L, d = q.shape
+        S = k.shape[2]
+        lshape, sshape = (B, H, L, d), (B, H, S, d)
+        ins = [_attn_fused_operand(t, sh) for t, sh in zip((q, k, v, O, go), (lshape, sshape, sshape, lshape, lshape))]
+        outs = [torch.empty(sh, dtype=torch.float32, device=q.device) if on else None for on, sh in zip(need, (lshape, sshape, sshape))]
+        ws = _attn_tiled_workspace(q.device, 8 * B * H * L)
+        _attn_fused_launch("bhg_attention_fused_backward", ins, [stats], mask, causal, scale, outs, (ws.data_ptr(), ws.numel()))
+        ctx.save_for_backward(q, k, v, go, mask)
+        ctx.causal, ctx.scale = causal, scale
+        ctx.short = max(L, S) <= _ATTN_MAX
+        ctx.set_materialize_grads(False)
+        return tuple(outs)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, aq, ak, av):
+        impl = _ATTN_VJP_IMPL if ctx.short else _ATTN_TILED_VJP_IMPL
+        return _attn_double_backward(ctx, _ATTN_FUSED_CALLS, impl, aq, ak, av) + (None, None)
+
+
+class _AttnFusedForward(torch.autograd.Function):
+    """Attention in one bhg_attention_fused_forward call; saves O and the row statistics, no (B, H, L, S) tensor of its own."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, mask, causal, scale):
+        _ATTN_FUSED_CALLS["forward"] += 1
+        B, H, L, d = q.shape
+        S = k.shape[2]
+        ins = [_attn_fused_operand(t, sh) for t, sh in zip((q, k, v), ((B, H, L, d), (B, H, S, d), (B, H, S, d)))]
+        O = torch.empty((B, H, L, d), dtype=torch.float32, device=q.device)
+        stats = torch.empty((B, H, L, 2), dtype=torch.float32, device=q.device)
+        _attn_fused_launch("bhg_attention_fused_forward", ins, [], mask, causal, scale, [O, stats])
+        ctx.save_for_backward(q, k, v, O, stats, mask)
+        ctx.causal, ctx.scale = causal, scale
+        return O
+
+    @staticmethod
+    def backward(ctx, go):
+        q, k, v, O, stats, mask = ctx.saved_tensors
+        gq, gk, gv = _AttnFusedBackward.apply(q, k, v, go, O.detach(), stats, mask, ctx.causal, ctx.scale, tuple(ctx.needs_input_grad[:3]))
+        return gq, gk, gv, None, None, None
+
+
 def _declared_mask(q, k, v, attn_mask, dropout_p, is_causal, kw, max_len=_ATTN_MAX, max_d=_ATTN_MAX):
     """False when the call is outside the declared family (at most ``max_len`` queries and keys, at most ``max_d`` elements per head);
     otherwise the additive fp32 mask as a (B, H, L, S) view, or None."""
@@ -1103,17 +1204,40 @@ def wide_scaled_dot_product_attention(query, key, value, attn_mask=None, dropout
     return _AttnWideForward.apply(query, key, value, mask, bool(is_causal), s)
 
 
+def fused_scaled_dot_product_attention(query, key, value, attn_mask=None, dropout_p=0.0, is_causal=False, scale=None, **kw):
+    """``tiled_scaled_dot_product_attention`` above with a native forward and first backward: for its family up to ``_ATTN_FUSED_MAX``
+    queries and keys (d <= 64 and every other condition as above) the forward is one bhg_attention_fused_forward call that saves O and
+    8 bytes per query row instead of P, the first backward one bhg_attention_fused_backward call, and the double backward the existing
+    fused call (the short kernel up to 64 tokens, the tiled one beyond), all counted by ``declared_attention_fused_calls()``.  Anything
+    else IS the torch function with the caller's arguments, errors included."""
+    mask = _declared_mask(query, key, value, attn_mask, dropout_p, is_causal, dict(kw), min(_ATTN_FUSED_MAX, _ATTN_TILED_MAX))
+    if mask is False:
+        return _TORCH_SDPA(query, key, value, attn_mask=attn_mask, dropout_p=dropout_p, is_causal=is_causal, scale=scale, **kw)
+    s = 1.0 / math.sqrt(query.shape[-1]) if scale is None else float(scale)
+    return _AttnFusedForward.apply(query, key, value, mask, bool(is_causal), s)
+
+
+def _wide_or_fused_scaled_dot_product_attention(query, key, value, attn_mask=None, dropout_p=0.0, is_causal=False, scale=None, **kw):
+    """``declared_attention(wide=True, fused=True)``: heads of more than 64 elements take the wide function, everything else the fused one."""
+    wide = torch.is_tensor(query) and query.dim() == 4 and query.shape[-1] > _ATTN_MAX
+    return (wide_scaled_dot_product_attention if wide else fused_scaled_dot_product_attention)(
+        query, key, value, attn_mask=attn_mask, dropout_p=dropout_p, is_causal=is_causal, scale=scale, **kw)
+
+
 @contextlib.contextmanager
-def declared_attention(tiled: bool = False, wide: bool = False):
+def declared_attention(tiled: bool = False, wide: bool = False, fused: bool = False):
     """Inside the context ``torch.nn.functional.scaled_dot_product_attention`` is the function above: ``nn.MultiheadAttention``,
     ``nn.TransformerEncoder`` and model code that calls the torch function reach the declaration without being rewritten, and
     ``sdpa_kernel(MATH)`` is not needed for shapes in the family.  ``tiled=True`` installs ``tiled_scaled_dot_product_attention``
     instead (sequences of up to ``_ATTN_TILED_MAX`` tokens), ``wide=True`` ``wide_scaled_dot_product_attention`` (that, and heads of up
-    to ``_ATTN_WIDE_MAX_D`` elements).  Only the forward that records the graph has to run inside; the
+    to ``_ATTN_WIDE_MAX_D`` elements), ``fused=True`` ``fused_scaled_dot_product_attention`` (the tiled family with a native forward and
+    first backward that save no probability matrix; with ``wide=True`` as well, heads of more than 64 elements still take the wide
+    function).  Only the forward that records the graph has to run inside; the
     solve's double backward runs wherever it runs.  Restored on exit, exceptions included; nesting is safe."""
     F = torch.nn.functional
     previous = F.scaled_dot_product_attention
-    F.scaled_dot_product_attention = (wide_scaled_dot_product_attention if wide else
+    F.scaled_dot_product_attention = (_wide_or_fused_scaled_dot_product_attention if wide and fused else
+                                      fused_scaled_dot_product_attention if fused else wide_scaled_dot_product_attention if wide else
                                       tiled_scaled_dot_product_attention if tiled else scaled_dot_product_attention)
     try:
         yield

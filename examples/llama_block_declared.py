@@ -31,6 +31,7 @@ from betty_amd.engine import Engine, EngineConfig  # noqa: E402
 from betty_amd.problems import ImplicitProblem  # noqa: E402
 
 DECLARED = [True]
+FUSED = [False]   # --fused
 
 
 class Block(nn.Module):
@@ -62,7 +63,7 @@ class Decoder(nn.Module):
             with torch.nn.attention.sdpa_kernel(torch.nn.attention.SDPBackend.MATH):
                 return self.head(self.norm(self.blocks(self.embed(tokens)))[:, -1])
         wide = self.embed.embedding_dim // self.blocks[0].heads > 64
-        with bnn.declared_attention(tiled=tokens.shape[1] > 64, wide=wide):   # only the forward that records the graph has to run inside
+        with bnn.declared_attention(tiled=tokens.shape[1] > 64, wide=wide, fused=FUSED[0]):   # only the forward that records the graph has to run inside
             return self.head(self.norm(self.blocks(self.embed(tokens)))[:, -1])
 
 
@@ -103,8 +104,9 @@ def main():
     ap.add_argument("--width", type=int, default=64)
     ap.add_argument("--heads", type=int, default=4)
     ap.add_argument("--undeclared", action="store_true", help="leave every layer undeclared (the A/B arm)")
+    ap.add_argument("--fused", action="store_true", help="attention's forward and first backward native as well (declared_attention(fused=True))")
     args = ap.parse_args()
-    DECLARED[0] = not args.undeclared
+    DECLARED[0], FUSED[0] = not args.undeclared, args.fused
     torch.manual_seed(0)
     g = torch.Generator().manual_seed(1)
     vocab, classes = 32, 8
@@ -124,7 +126,7 @@ def main():
     engine = Engine(config=EngineConfig(train_iters=args.iters), problems=[upper, inner],
                     dependencies={"u2l": {upper: [inner]}, "l2u": {inner: [upper]}})
     c0 = (bnn.fused_rmsnorm_calls(), bnn.declared_attention_calls(), bnn.declared_activation_calls())
-    wide0 = bnn.declared_attention_wide_calls()["backward_vjp"]
+    wide0, fused0 = bnn.declared_attention_wide_calls()["backward_vjp"], bnn.declared_attention_fused_calls()
     t0 = time.perf_counter()
     engine.run()
     if torch.cuda.is_available():
@@ -136,6 +138,8 @@ def main():
     print(f"LLaMA-style decoder, {args.blocks} blocks, declared {declared.get('rmsnorm', 0)} RMS norms{'' if DECLARED[0] else ' (nothing)'}, "
           f"{args.algo} K={args.k}: {upper.count} upper steps in {dt:.2f} s; fused double-backward calls: RMS norm {rms}, attention {attn}, "
           f"SwiGLU {act}; meta-weight-net finite {finite}")
+    if args.fused:
+        print(f"fused attention nodes: {({key: n - fused0[key] for key, n in bnn.declared_attention_fused_calls().items()})}")
     if args.width // args.heads > 64:
         print(f"heads of {args.width // args.heads} elements: wide attention double-backward calls {bnn.declared_attention_wide_calls()['backward_vjp'] - wide0}")
 

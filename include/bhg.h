@@ -840,6 +840,37 @@ int bhg_attention_wide_backward_vjp(const float* q, const float* k, const float*
                                     int causal, float scale, int B, int H, int L, int S, int d, float* dq, float* dk, float* dv,
                                     float* dgo, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- the attention core's forward and first backward without a score matrix in memory (csrc/bhg_attention_fused.hip) --------------------
+ * The tiled sibling's family, layout, tiles and arithmetic (1 <= L, S <= 512, 1 <= d <= 64, fp32, 64 x 32 score tiles, every product on
+ * the fp32-input MFMA), for the two nodes in front of its vector-Jacobian product:
+ *   forward   O = softmax_rows(s q k^T + mask) v.  ONE launch, grid B H ceil(L / 64): Q resident, the key tiles streamed, the online row
+ *      maximum and denominator, O accumulated in registers and rescaled when the maximum moves.  Writes o (B, H, L, d) contiguous and
+ *      `stats`: (B, H, L) pairs of floats (row maximum, softmax denominator), 8 bytes per query row, 8-byte aligned.  No L x S array.
+ *   backward  (q, k, v, o, go, stats) -> (gq, gk, gv), each may be NULL (not all three).  TWO launches:
+ *      1  grid B H ceil(L / 64): D = rowsum(go * o) per row in fp64 -> ws; then, unless gq is NULL, gq = s gS k with
+ *         P = exp(score - max) / l recomputed per tile and gS = P * (go v^T - D);
+ *      2  grid B H ceil(S / 32): gv = P^T go and gk = s gS^T q, the statistics and D read from memory (not launched when both are NULL).
+ *      `strides` holds four element strides for each of q, k, v, o, go (20 entries; the forward's: q, k, v, 12 entries).
+ * Workspace `ws`: bhg_attention_fused_ws_bytes(B, H, L) = 8 B H L bytes, 8-byte aligned (0 for sizes <= 0).
+ * Causal tile skipping, dead key tiles and fully masked rows (NaN) as in the tiled sibling.  No atomics, no grid barrier: deterministic.
+ * Asynchronous on `stream`, no host synchronisation.  Refused with -1 and a message, before any device access: the shapes the tiled
+ * sibling refuses, with its words; a NULL input, output (forward), statistic or workspace; a non-unit last stride; a negative stride; on
+ * the vector path a pointer that is not 16-byte aligned; a short or misaligned workspace.
+ *
+ * bhg_attention_fused_plan is host logic only, answered by the very function the launches call, one line of `key=value` pairs: vec,
+ * bm = 64, bn = 32, ps = 36, dp, pd = dp + 4, grid_f = grid_q and grid_k, lds_f = 4 ((bm + 2 bn) pd + bm ps), lds_q =
+ * 4 ((2 bm + 2 bn) pd + bm ps) + 8 bm and lds_k = 4 ((2 bm + 2 bn) pd + 2 bm ps) (bytes of dynamic LDS: 44032, 61952 and 70656 at
+ * dp = 64), stats = 8 (bytes per query row), ws (bytes).                                                                                 */
+size_t bhg_attention_fused_ws_bytes(int B, int H, int L);
+int bhg_attention_fused_plan(int B, int H, int L, int S, int d, int vec_ok, char* buf, size_t buf_bytes);
+int bhg_attention_fused_forward(const float* q, const float* k, const float* v, const long long* strides, const float* mask,
+                                const long long* mask_strides, int causal, float scale, int B, int H, int L, int S, int d, float* o,
+                                void* stats, void* stream);
+int bhg_attention_fused_backward(const float* q, const float* k, const float* v, const float* o, const float* go, const void* stats,
+                                 const long long* strides, const float* mask, const long long* mask_strides, int causal, float scale,
+                                 int B, int H, int L, int S, int d, float* gq, float* gk, float* gv, void* ws, size_t ws_bytes,
+                                 void* stream);
+
 /* ---- smooth activations, plain and gated: their share of a Hessian-vector product (csrc/bhg_activation.hip) ----------------------------
  * Plain, y = f(x): the first backward is F : (x, gy) -> gx = gy f'(x).  bhg_act_backward_vjp is its vector-Jacobian product: for a
  * cotangent a of gx,      dgy = a f'(x)      dx = a gy f''(x).

@@ -12,7 +12,9 @@ _ATTN_TILED_MAX to 512 for its own process), whatever value ships.
   (iii) at 16 x 128 tokens, the distance of each product from the same problem's float64 product.
 
     python scripts/attention_tiled_profile.py [--out profiles/attention_tiled_double_backward.txt] [--calls 40] [--ref-calls 10] [--reps 5] [--dry]
+        [--fused]
 
+--fused adds declared_attention(fused=True) (csrc/bhg_attention_fused.hip) as a third arm of (ii) and (iii).
 --dry prints the shape table with its plans and stops (no GPU needed); every measurement needs a GPU and fails without one."""
 import argparse
 import os
@@ -113,19 +115,21 @@ class _Routed(nn.Module):
 
     def __init__(self, net, declared):
         super().__init__()
-        self.net, self.declared = net, declared
+        self.net, self.declared = net, declared   # False, True (tiled) or "fused"
 
     def forward(self, x):
-        with (bnn.declared_attention(tiled=True) if self.declared else sdpa_kernel(SDPBackend.MATH)):
+        with (bnn.declared_attention(tiled=True, fused=self.declared == "fused") if self.declared else sdpa_kernel(SDPBackend.MATH)):
             return self.net(x)
 
 
-def encoder(say, reps, tokens, with_fp64):
+def encoder(say, reps, tokens, with_fp64, fused=False):
     say("")
     say(f"(ii) one double-backward Hessian-vector product of a two-layer nn.TransformerEncoder (d_model 768, 12 heads, ffn 3072, no dropout, "
         f"16 x {tokens} tokens), layer norm declared: median wall ms of {reps} (three alternating rounds), kernel launches")
     row, product = {}, {}
     forms = {"layer norm": (False, torch.float32), "layer norm + tiled attention": (True, torch.float32)}
+    if fused:
+        forms["layer norm + fused attention"] = ("fused", torch.float32)
     if with_fp64:
         forms["float64"] = (False, torch.float64)
     for form, (attn, dtype) in forms.items():
@@ -141,9 +145,10 @@ def encoder(say, reps, tokens, with_fp64):
         vec = [torch.randn(t.shape, generator=g).to(DEV, dtype) for t in params]
         grads = torch.autograd.grad((net(x) ** 2).mean(), params, create_graph=True)
         hvp = lambda grads=grads, params=params, vec=vec: torch.autograd.grad(grads, params, grad_outputs=vec, retain_graph=True)   # noqa: E731
-        c0 = bnn.declared_attention_tiled_calls()["backward_vjp"]
+        vjps = lambda: bnn.declared_attention_tiled_calls()["backward_vjp"] + bnn.declared_attention_fused_calls()["backward_vjp"]   # noqa: E731
+        c0 = vjps()
         product[form] = torch.cat([t.reshape(-1) for t in hvp()]).double().cpu()
-        row[form] = (hvp, bnn.declared_attention_tiled_calls()["backward_vjp"] - c0)
+        row[form] = (hvp, vjps() - c0)
         if dtype == torch.float64:
             del row[form], grads, hvp
             torch.cuda.empty_cache()
@@ -173,6 +178,7 @@ def main():
     ap.add_argument("--ref-calls", type=int, default=10)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--dry", action="store_true")
+    ap.add_argument("--fused", action="store_true", help="(ii), (iii): a third arm, declared_attention(fused=True)")
     args = ap.parse_args()
     lines = []
 
@@ -197,7 +203,7 @@ def main():
     bnn._ATTN_TILED_MAX = 512
     per_call(say, args.calls, args.ref_calls)
     for tokens in TOKENS:
-        encoder(say, args.reps, tokens, with_fp64=tokens == TOKENS[0])
+        encoder(say, args.reps, tokens, with_fp64=tokens == TOKENS[0], fused=args.fused)
 
 
 if __name__ == "__main__":
