@@ -299,9 +299,10 @@ __global__ __launch_bounds__(kThreads) void k_attn_vjp(const AtArgs q) {
       if (mrow) sc += mrow[i * q.mst[2]];
       if (!in || (q.causal && j > i)) sc = -INFINITY;
       const float mx = at_wave_max(sc);
-      const double e = in ? (double)expf(sc - mx) : 0.0;   // a fully masked row: -inf - -inf, NaN as on the math path
+      const bool dead = mx == -INFINITY;                   // a fully masked row: P = 0, as on the math path (-inf - -inf would be NaN)
+      const double e = in && !dead ? (double)expf(sc - mx) : 0.0;
       const double sum = wave_sum(e);
-      const float pf = (float)(e / sum);
+      const float pf = dead ? 0.f : (float)(e / sum);
       const double p = (double)pf;
       const double gp = (double)X1[at];
       const double t = has_t ? (double)(q.scale * X2[at]) : 0.0;

@@ -19,8 +19,9 @@
 //   k_attn_fused_bk   grid B H ceil(S / 32): K and V resident, the 64-row tiles of Q and gO streamed, (mx, l) and D read from memory,
 //       P and gS through two LDS tiles (read transposed), gv and gk accumulated in registers.  Not launched when both are NULL.
 // A tile whose keys are all masked leaves the running maximum at -inf: e is then taken against 0 (exp(-inf) = 0, not NaN) and the
-// rescale of the still-empty sums is skipped, so live keys in a later tile are not poisoned.  A fully masked ROW ends with l = 0 and
-// is NaN, as on the math path.  Under the causal flag the tiles wholly above the diagonal are skipped in all three kernels.
+// rescale of the still-empty sums is skipped, so live keys in a later tile are not poisoned.  A fully masked ROW ends with (mx, l) = (-inf, 0)
+// and takes 1 / l = 0 in all three kernels: O and its row of gq are exact zeros and it adds nothing to gk and gv, as on torch's math
+// path (2.10).  Under the causal flag the tiles wholly above the diagonal are skipped in all three kernels.
 //
 // Every product runs on the fp32-input MFMA v_mfma_f32_16x16x4_f32: exact fp32, bit for bit a k-ordered fmaf chain.  Lane
 // (n = lane & 15, g = lane >> 4) supplies A[n][k] and B[k][n]; step c of a group of four uses k = 4 g + c, so a lane's four A values
@@ -300,7 +301,7 @@ __global__ __launch_bounds__(kThreads) void k_attn_fused_f(const FuArgs q) {
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const double l = fu_sum16(a_l[r]);
-    il[r] = (float)(1.0 / l);
+    il[r] = l > 0.0 ? (float)(1.0 / l) : 0.f;   // a fully masked row: O = 0, saved as (mx, l) = (-inf, 0)
     const int i = i0 + 16 * w + 4 * g + r;
     if (n == 0 && i < L) q.stats_out[(long long)bh * L + i] = make_float2(mx[r], (float)l);
   }
@@ -395,7 +396,7 @@ __global__ __launch_bounds__(kThreads) void k_attn_fused_bq(const FuArgs q) {
     D[r] = Ds[row];
     if (i < L) {
       const float2 st = q.stats[(long long)bh * L + i];
-      mx[r] = st.x; il[r] = 1.0 / (double)st.y;
+      mx[r] = st.x; il[r] = st.y > 0.f ? 1.0 / (double)st.y : 0.0;   // l = 0: a dead row, P = 0
     }
   }
   fu_f32x4 acc[NCB];
@@ -472,7 +473,7 @@ __global__ __launch_bounds__(kThreads) void k_attn_fused_bk(const FuArgs q) {
       mx[r] = 0.f; il[r] = 1.0; D[r] = 0.0;
       if (i < L) {
         const float2 st = q.stats[(long long)bh * L + i];
-        mx[r] = st.x; il[r] = 1.0 / (double)st.y;
+        mx[r] = st.x; il[r] = st.y > 0.f ? 1.0 / (double)st.y : 0.0;   // l = 0: a dead row, P = 0
         D[r] = q.ws[(long long)bh * L + i];
       }
     }

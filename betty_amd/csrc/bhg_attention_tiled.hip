@@ -13,8 +13,9 @@
 // rescales them by exp(m_old - m_new) when the running maximum moves, and divides by l at the end.  R needs no second pass:
 //     R = rowsum(P * T * gP) - 2 D E + rowsum(P * (gO aV^T))            (bP summed against P, with rowsum(P) = 1).
 // A tile whose keys are all masked leaves the running maximum at -inf: e is then taken against 0 (exp(-inf) = 0, not NaN) and the
-// rescale of the still-empty sums is skipped, so live keys in a later tile are not poisoned.  A fully masked ROW ends with l = 0 and
-// is NaN, as on the math path and in the sibling.
+// rescale of the still-empty sums is skipped, so live keys in a later tile are not poisoned.  A fully masked ROW ends with m = -inf and
+// l = 0 and all five sums 0; they are divided by 1 instead, so D = E = R = 0 and P = exp(-inf) = 0: its probabilities are zero, as on torch's math path (2.10) and in the sibling, so it adds
+// nothing to any output and its rows of dQ and dgO are exact zeros.
 //
 // TWO launches, no atomics, no grid barrier (float64 restatement of exactly this scheme: tests/attention_tiled_ref.py):
 //   k_attn_tiled_q   grid B H ceil(L / 64): a block owns 64 query rows (Q, gO, aQ resident in LDS) and sweeps the key tiles twice.
@@ -390,9 +391,12 @@ __global__ __launch_bounds__(kThreads) void k_attn_tiled_q(const TlArgs q) {
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const double l = tl_sum16(a_l[r]);
-    const double D = tl_sum16(a_gp[r]) / l, E = tl_sum16(a_t[r]) / l;
-    const double R = tl_sum16(a_tgp[r]) / l - 2.0 * D * E + tl_sum16(a_w[r]) / l;
-    st.il[r] = 1.0 / l; st.D[r] = D; st.E[r] = E; st.R[r] = R;
+    // A fully masked row (or one past L) has e = 0 throughout: l = 0 and the four other sums are 0 as well.  Divided by 1 instead of by
+    // 0 they give D = E = R = 0, and P = exp(-inf) * 1 = 0 with them gS = bgP = bS = 0: zeros, where 0 / 0 was NaN.
+    const double ld = l > 0.0 ? l : 1.0;
+    const double D = tl_sum16(a_gp[r]) / ld, E = tl_sum16(a_t[r]) / ld;
+    const double R = tl_sum16(a_tgp[r]) / ld - 2.0 * D * E + tl_sum16(a_w[r]) / ld;
+    st.il[r] = 1.0 / ld; st.D[r] = D; st.E[r] = E; st.R[r] = R;
     const int i = i0 + 16 * w + 4 * g + r;
     if (n == 0 && i < L) {
       double* o = q.ws + ((long long)bh * L + i) * kTlStats;
@@ -486,7 +490,7 @@ __global__ __launch_bounds__(kThreads) void k_attn_tiled_k(const TlArgs q) {
       st.m[r] = 0.f; st.il[r] = 1.0; st.D[r] = st.E[r] = st.R[r] = 0.0;
       if (i < L) {
         const double* o = q.ws + ((long long)bh * L + i) * kTlStats;
-        st.m[r] = (float)o[0]; st.il[r] = 1.0 / o[1]; st.D[r] = o[2]; st.E[r] = o[3]; st.R[r] = o[4];
+        st.m[r] = (float)o[0]; st.il[r] = o[1] > 0.0 ? 1.0 / o[1] : 0.0; st.D[r] = o[2]; st.E[r] = o[3]; st.R[r] = o[4];   // l = 0: a dead row, P = 0
       }
     }
     __syncthreads();

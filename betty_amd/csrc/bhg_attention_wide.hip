@@ -11,7 +11,8 @@
 //     sum e      sum e gP      sum e T      sum e T gP      sum e (gO aV^T)
 // per row, rescaled by exp(m_old - m_new) when the running maximum moves, and R = rowsum(P * T * gP) - 2 D E + rowsum(P * (gO aV^T)).
 // A tile whose keys are all masked leaves the maximum at -inf: e is then taken against 0 and the rescale of the still-empty sums is
-// skipped, so live keys in a later tile are not poisoned.  A fully masked ROW ends with l = 0 and is NaN, as on the math path.
+// skipped, so live keys in a later tile are not poisoned.  A fully masked ROW ends with m = -inf, l = 0 and all five sums 0; divided by 1
+// instead they give D = E = R = 0 and P = exp(-inf) = 0: its probabilities are zero, as on torch's math path (2.10), and its rows of dQ and dgO are exact zeros.
 //
 // THE TILING, and why.  At dp = 128 an operand row is 132 floats (pitch dp + 4, an odd number of 16-byte units), 528 bytes, so the
 // sibling's three 64-row and four 32-row tiles alone are 168 960 bytes: more than a CU has.  The two launches have different needs, so
@@ -372,9 +373,12 @@ __global__ __launch_bounds__(kThreads) void k_attn_wide_q(const WdArgs q) {
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const double l = wd_sum16(a_l[r]);
-    const double D = wd_sum16(a_gp[r]) / l, E = wd_sum16(a_t[r]) / l;
-    const double R = wd_sum16(a_tgp[r]) / l - 2.0 * D * E + wd_sum16(a_w[r]) / l;
-    st.il[r] = 1.0 / l; st.D[r] = D; st.E[r] = E; st.R[r] = R;
+    // A fully masked row (or one past L) has e = 0 throughout: l = 0 and the four other sums are 0 as well.  Divided by 1 instead of by
+    // 0 they give D = E = R = 0, and P = exp(-inf) * 1 = 0 with them gS = bgP = bS = 0: zeros, where 0 / 0 was NaN.
+    const double ld = l > 0.0 ? l : 1.0;
+    const double D = wd_sum16(a_gp[r]) / ld, E = wd_sum16(a_t[r]) / ld;
+    const double R = wd_sum16(a_tgp[r]) / ld - 2.0 * D * E + wd_sum16(a_w[r]) / ld;
+    st.il[r] = 1.0 / ld; st.D[r] = D; st.E[r] = E; st.R[r] = R;
     const int i = i0 + 16 * w + 4 * g + r;
     if (n == 0 && i < L) {
       double* o = q.ws + ((long long)bh * L + i) * kWdStats;
@@ -484,7 +488,7 @@ __global__ __launch_bounds__(kThreads) void k_attn_wide_k(const WdArgs q) {
       st.m[r] = 0.f; st.il[r] = 1.0; st.D[r] = st.E[r] = st.R[r] = 0.0;
       if (i < L) {
         const double* o = q.ws + ((long long)bh * L + i) * kWdStats;
-        st.m[r] = (float)o[0]; st.il[r] = 1.0 / o[1]; st.D[r] = o[2]; st.E[r] = o[3]; st.R[r] = o[4];
+        st.m[r] = (float)o[0]; st.il[r] = o[1] > 0.0 ? 1.0 / o[1] : 0.0; st.D[r] = o[2]; st.E[r] = o[3]; st.R[r] = o[4];   // l = 0: a dead row, P = 0
       }
     }
     __syncthreads();

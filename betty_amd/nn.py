@@ -931,7 +931,9 @@ def _attn_forward(ctx, calls, q, k, v, mask, causal, scale):
         sc = sc + mask
     if causal:
         sc = sc.masked_fill(torch.ones(sc.shape[-2:], dtype=torch.bool, device=sc.device).triu(1), float("-inf"))
-    P = torch.softmax(sc, dim=-1)
+    # A mask can remove every key of a row (left padding under a causal mask, an empty sequence); the causal flag alone cannot.  Such a
+    # row has P = 0, as on torch's math path (2.10), which takes the same function; no device-to-host synchronisation.
+    P = torch.softmax(sc, dim=-1) if mask is None else torch._safe_softmax(sc, dim=-1)
     ctx.save_for_backward(q, k, v, P, mask)
     ctx.causal, ctx.scale = causal, scale
     return P @ v

@@ -763,7 +763,8 @@ int bhg_groupnorm_backward_vjp(const float* x, const float* gy, const float* a, 
  * (batch, head, row, last), read before the launch; the last stride must be 1, the others may be anything >= 0 (transposed and
  * broadcast views are read in place; the entries of a NULL input are ignored, and a stride whose extent is 1 is ignored).  `mask`: NULL,
  * or fp32 additive with the four HOST element strides `mask_strides` (batch, head, row, column), any of which may be 0: a (B, 1, 1, S)
- * key-padding mask is read in place.  -inf entries are allowed; a fully masked row gives NaN, as on the math path.  `causal` != 0 masks
+ * key-padding mask is read in place.  -inf entries are allowed; a fully masked row has probability zero throughout, as on torch's math path
+ * (checked against 2.10): its rows of dq and dgo are exact zeros and it adds nothing to dk and dv.  `causal` != 0 masks
  * j > i as well.  Outputs dq, dgo (B, H, L, d) and dk, dv (B, H, S, d): contiguous, each may be NULL (its products are skipped, not all
  * four); every non-NULL output is overwritten in full.
  * Family: 1 <= L, S, d <= 64; B, H >= 1.  vec = 4 (16-byte accesses) when d % 4 == 0 and every batch / head / row stride of a given input
@@ -794,7 +795,8 @@ int bhg_attention_backward_vjp(const float* q, const float* k, const float* v, c
  *   2  grid B H ceil(S / 32), 32 keys per workgroup: sweeps the query tiles with the statistics of launch 1 and accumulates dk and dv
  *      (not launched when both are NULL).
  * Under `causal` the tiles wholly above the diagonal are skipped.  A key tile that is masked out entirely does not disturb rows with
- * live keys elsewhere; a fully masked row gives NaN, as on the math path.  Every product on the fp32-input MFMA (exact fp32); the five
+ * live keys elsewhere; a fully masked row has probability zero, as on torch's math path (2.10): its workspace row is [-inf, 0, 0, 0, 0],
+ * its rows of dq and dgo are exact zeros and it adds nothing to dk and dv.  Every product on the fp32-input MFMA (exact fp32); the five
  * row statistics accumulate in fp64.  No atomics, no grid barrier: deterministic.  Asynchronous on `stream`, no host synchronisation.
  * Workspace `ws`: bhg_attention_tiled_ws_bytes(B, H, L) bytes, 8-byte aligned, written by launch 1 and read by launch 2 — the row
  * statistics only: (B, H, L) rows of five doubles [m, l, D, E, R], 40 bytes per query row (0 for sizes <= 0).  Nothing is kept between calls.
@@ -823,7 +825,7 @@ int bhg_attention_tiled_backward_vjp(const float* q, const float* k, const float
  *      row's five online statistics stay inside one wave; (a) the online pass, (b) dq and dgo (skipped when both are NULL);
  *   2  grid B H ceil(S / 32): 32 resident keys x 32 streamed queries (kbn x kbm, pitch kps = 36), the statistics read from the workspace;
  *      dk and dv (not launched when both are NULL).
- * Causal tile skipping, dead key tiles, fully masked rows (NaN), exact-fp32 MFMA products, fp64 statistics, determinism and the
+ * Causal tile skipping, dead key tiles, fully masked rows (zero probabilities), exact-fp32 MFMA products, fp64 statistics, determinism and the
  * workspace layout (bhg_attention_wide_ws_bytes(B, H, L) = 40 B H L bytes, 8-byte aligned) are those of the tiled sibling.
  * Refused with -1 and a message, before any device access: everything the tiled sibling refuses, with its words, except that d < 65 is
  * "fewer than 65 elements per head" (it names the two siblings that take d <= 64) and the upper limit is "more than 128 elements per
@@ -852,7 +854,9 @@ int bhg_attention_wide_backward_vjp(const float* q, const float* k, const float*
  *      2  grid B H ceil(S / 32): gv = P^T go and gk = s gS^T q, the statistics and D read from memory (not launched when both are NULL).
  *      `strides` holds four element strides for each of q, k, v, o, go (20 entries; the forward's: q, k, v, 12 entries).
  * Workspace `ws`: bhg_attention_fused_ws_bytes(B, H, L) = 8 B H L bytes, 8-byte aligned (0 for sizes <= 0).
- * Causal tile skipping, dead key tiles and fully masked rows (NaN) as in the tiled sibling.  No atomics, no grid barrier: deterministic.
+ * Causal tile skipping and dead key tiles as in the tiled sibling.  A fully masked row has probability zero, as on torch's math path
+ * (2.10): its statistics are (mx, l) = (-inf, 0), its rows of o and gq are exact zeros and it adds nothing to gk and gv.
+ * No atomics, no grid barrier: deterministic.
  * Asynchronous on `stream`, no host synchronisation.  Refused with -1 and a message, before any device access: the shapes the tiled
  * sibling refuses, with its words; a NULL input, output (forward), statistic or workspace; a non-unit last stride; a negative stride; on
  * the vector path a pointer that is not 16-byte aligned; a short or misaligned workspace.

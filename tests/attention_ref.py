@@ -38,8 +38,12 @@ def scores(q, k, mask, causal, scale):
 
 
 def probabilities(q, k, mask=None, causal=False, scale=None):
+    """Rows of softmax; a row whose scores are all -inf (every key masked) has probability zero, as on torch's math path (2.10)."""
     scale = default_scale(q.shape[-1]) if scale is None else scale
-    return torch.softmax(scores(q, k, mask, causal, scale), dim=-1)
+    sc = scores(q, k, mask, causal, scale)
+    dead = (sc == float("-inf")).all(-1, keepdim=True)
+    # (the dead rows' scores are replaced before the softmax as well, so that autograd sees no NaN behind the fill: 0 * NaN is NaN)
+    return torch.softmax(sc.masked_fill(dead, 0.0), dim=-1).masked_fill(dead, 0.0)
 
 
 def attention(q, k, v, mask=None, causal=False, scale=None):

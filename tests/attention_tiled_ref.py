@@ -9,7 +9,9 @@ Score tiles are BM = 64 queries x BN = 32 keys.  Per block of 64 query rows:
       sums are empty and are left alone, and e is taken against 0 instead of m, so exp(-inf - 0) = 0 and nothing turns NaN.  At the end
           l = sum e     D = (sum e gP) / l     E = (sum e T) / l
           R = rowsum(P * bP) = (sum e T gP) / l - 2 D E + (sum e (go av^T)) / l
-      (bP = T * (gP - D) - gP * E + go av^T summed against P, with rowsum(P) = 1).  A fully masked row ends with l = 0: NaN.
+      (bP = T * (gP - D) - gP * E + go av^T summed against P, with rowsum(P) = 1).  A fully masked row ends with m = -inf and l = 0
+      and has D = E = R = 0 and P = 0 (the kernel divides its sums, all 0, by 1 instead of by l): zero probabilities, as on torch's math
+      path, and zeros in every output of that row.
   (b) a second sweep recomputes the tile's raw products, forms P = exp(score - m) / l, gS, bgP, bS from the finished statistics and
       accumulates dq = s (bS k + gS ak) and dgo = bgP v + P av over the key tiles.
 Per block of 32 keys, the second launch sweeps the query tiles with the same statistics and accumulates dv = bgP^T go and
@@ -47,6 +49,11 @@ def _key_tiles(i1, S, causal):
     return [(j0, min(j0 + BN, S)) for j0 in range(0, last, BN)]
 
 
+def _inverse(l):
+    """1 / l, and 0 where l = 0: a fully masked row has probability zero, as on torch's math path."""
+    return torch.where(l > 0, 1.0 / torch.where(l > 0, l, torch.ones_like(l)), torch.zeros_like(l))
+
+
 def row_statistics(q, k, v, go, aq, ak, av, mask=None, causal=False, scale=None):
     """(m, l, D, E, R), each (B, H, L, 1), by the online pass."""
     scale = attention_ref.default_scale(q.shape[-1]) if scale is None else scale
@@ -67,8 +74,10 @@ def row_statistics(q, k, v, go, aq, ak, av, mask=None, causal=False, scale=None)
             sums = [s * f + t.sum(-1, keepdim=True) for s, t in zip(sums, terms)]
             m = m_new
         l = sums[0]
-        D, E = sums[1] / l, sums[2] / l
-        R = sums[3] / l - 2.0 * D * E + sums[4] / l
+        dead, one = l == 0, torch.ones_like(l)                                 # a dead row: D = E = R = 0
+        ld = torch.where(dead, one, l)
+        D, E = (sums[1] / ld).masked_fill(dead, 0.0), (sums[2] / ld).masked_fill(dead, 0.0)
+        R = (sums[3] / ld - 2.0 * D * E + sums[4] / ld).masked_fill(dead, 0.0)
         for o, t in zip(out, (m, l, D, E, R)):
             o.append(t)
     return tuple(torch.cat(o, dim=2) for o in out)
@@ -78,7 +87,7 @@ def _tile_matrices(tile, stats, i0, i1):
     """(P, gS, bgP, bS) of a tile from its raw products and the finished statistics of its rows."""
     sc, gP, T, W = tile
     m, l, D, E, R = (t[..., i0:i1, :] for t in stats)
-    P = torch.exp(sc - torch.where(torch.isinf(m) & (m < 0), torch.zeros_like(m), m)) / l
+    P = torch.exp(sc - torch.where(torch.isinf(m) & (m < 0), torch.zeros_like(m), m)) * _inverse(l)
     bP = T * (gP - D) - gP * E + W
     return P, P * (gP - D), P * (T - E), P * (bP - R)
 

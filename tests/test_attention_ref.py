@@ -94,3 +94,70 @@ def test_absent_cotangents_are_zeros_and_the_terms_add_up():
     for i in range(4):
         torch.testing.assert_close(sum(p[i] for p in parts), full[i], rtol=1e-12, atol=1e-12)
     assert not parts[2][2].any()   # gv = P^T go does not depend on v
+
+
+# ---- fully masked rows: zeros, as on torch's math path --------------------------------------------------------------------------------------
+DEAD_SHAPE = (2, 2, 9, 11, 4)
+FIRST_GATE = 1e-12    # O and the first derivatives (the gate of test_the_first_backward_is_autograds)
+
+
+def _dead_row_mask(kind):
+    """(mask, dead) at DEAD_SHAPE: the additive mask and a (B, H, L) bool tensor of the rows it removes every key of.
+    full: a random (B, H, L, S) mask with one dead row in one head, two dead rows in every head of batch element 1 and one row with a
+    single live key.  padding: a (B, 1, 1, S) mask that removes every key of batch element 1."""
+    B, H, L, S, _ = DEAD_SHAPE
+    dead = torch.zeros(B, H, L, dtype=torch.bool)
+    if kind == "full":
+        mask = torch.randn(B, H, L, S, generator=torch.Generator().manual_seed(17), dtype=torch.float64)
+        mask[0, 1, 3] = float("-inf")
+        mask[1, :, 2] = float("-inf")
+        mask[1, :, 7] = float("-inf")
+        mask[0, 0, 5, :S - 2] = float("-inf")       # mostly masked: two live keys, not a dead row
+        dead[0, 1, 3] = dead[1, :, 2] = dead[1, :, 7] = True
+    else:
+        mask = torch.zeros(B, 1, 1, S, dtype=torch.float64)
+        mask[1] = float("-inf")
+        dead[1] = True
+    return mask, dead
+
+
+def _torch_math_path(q, k, v, go, aq, ak, av, mask):
+    """(O, (gq, gk, gv), (dq, dk, dv, dgo)) by autograd from F.scaled_dot_product_attention under sdpa_kernel(MATH), float64, CPU."""
+    from torch.nn.attention import SDPBackend, sdpa_kernel
+
+    leaves = [t.clone().requires_grad_(True) for t in (q, k, v, go)]
+    with sdpa_kernel(SDPBackend.MATH):
+        out = torch.nn.functional.scaled_dot_product_attention(*leaves[:3], attn_mask=mask)
+        first = torch.autograd.grad(out, leaves[:3], leaves[3], create_graph=True)
+        phi = sum((a * g).sum() for a, g in zip((aq, ak, av), first))
+        second = torch.autograd.grad(phi, leaves)
+    return out.detach(), [t.detach() for t in first], second
+
+
+@pytest.mark.parametrize("kind", ["full", "padding"])
+def test_fully_masked_rows_are_zeros_as_on_torchs_math_path(kind):
+    B, H, L, S, d = DEAD_SHAPE
+    g = torch.Generator().manual_seed(23)
+    rnd = lambda *s: torch.randn(*s, generator=g, dtype=torch.float64)   # noqa: E731
+    q, go, aq = rnd(B, H, L, d), rnd(B, H, L, d), rnd(B, H, L, d)
+    k, v, ak, av = rnd(B, H, S, d), rnd(B, H, S, d), rnd(B, H, S, d), rnd(B, H, S, d)
+    mask, dead = _dead_row_mask(kind)
+    want_o, want_first, want_second = _torch_math_path(q, k, v, go, aq, ak, av, mask)
+    got_o = attention_ref.attention(q, k, v, mask)
+    got_first = attention_ref.attention_backward(q, k, v, go, mask)
+    got_second = attention_ref.attention_backward_vjp(q, k, v, go, aq, ak, av, mask=mask)
+    worst = {}
+    for gate, names, got, want in ((FIRST_GATE, ("o", "gq", "gk", "gv"), (got_o,) + tuple(got_first), [want_o] + want_first),
+                                   (GATE, ("dq", "dk", "dv", "dgo"), got_second, want_second)):
+        for name, u, w in zip(names, got, want):
+            assert bool(torch.isfinite(w).all()), ("torch's math path", kind, name)
+            assert bool(torch.isfinite(u).all()), (kind, name)
+            top, err = float(w.abs().max()), float((u - w).abs().max())
+            worst[name] = err / top
+            assert err <= gate * top, (kind, name, err, top)
+            if name in ("o", "gq", "dq", "dgo"):                      # query-side: the dead rows are exact zeros, in both
+                assert not u[dead].any() and not w[dead].any(), (kind, name)
+    if kind == "padding":                                            # a dead head: nothing reaches its keys either
+        for u in (got_first[1], got_first[2], got_second[1], got_second[2]):
+            assert not u[1].any()
+    print(f"attention_ref vs torch's math path, dead rows ({kind}): " + "  ".join(f"{n} {e:.1e}" for n, e in worst.items()))

@@ -69,12 +69,15 @@ def test_row_statistics_are_the_direct_ones():
         assert float((u - w).abs().max()) <= GATE * float(w.abs().max())
 
 
-def test_a_fully_masked_row_is_nan_and_a_wrong_identity_would_show():
+def test_a_fully_masked_row_is_zero_and_a_wrong_identity_would_show():
     ins, _, _ = _inputs(65, 65, 4, "plain")
     mask = torch.zeros(2, 2, 65, 65, dtype=torch.float64)
     mask[0, 0, 3, :] = float("-inf")
     got = attention_tiled_ref.attention_backward_vjp(*ins, mask=mask)
-    assert bool(torch.isnan(got[0][0, 0, 3]).all()) and bool(torch.isfinite(got[0][1]).all())      # as on the math path
+    _check(got, attention_ref.attention_backward_vjp(*ins, mask=mask), "row [0, 0, 3] masked")     # finite everywhere, within GATE
+    assert not got[0][0, 0, 3].any() and not got[3][0, 0, 3].any()                                  # dq, dgo: as on the math path
+    m, l, D, E, R = attention_tiled_ref.row_statistics(*ins, mask=mask)
+    assert float(m[0, 0, 3]) == float("-inf") and not any(bool(t[0, 0, 3].any()) for t in (l, D, E, R))
     # R without the - 2 D E term is far outside the gate: the check above can fail
     m, l, D, E, R = attention_tiled_ref.row_statistics(*ins)
     assert float((2.0 * D * E).abs().max()) > 1e-3 * float(R.abs().max())

@@ -13,6 +13,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 from torch.nn.attention import SDPBackend, sdpa_kernel
 
+import attention_dead_rows
 import attention_ref
 import zoo
 from conftest import rel_err
@@ -71,10 +72,12 @@ def _mask(kind, B, L, S):
         m = torch.zeros(B, 1, 1, S, dtype=torch.float64)
         m[::2, :, :, S - 1] = float("-inf")
         return m, False
+    if kind == "dead_rows":                            # left padding under the triangle: rows 0 and 1 of the last batch element are dead
+        return attention_dead_rows.dead_rows_mask(B, L, S, 2)[0], False
     return None, kind == "causal"
 
 
-@pytest.mark.parametrize("kind", ["none", "additive", "padding", "causal"])
+@pytest.mark.parametrize("kind", ["none", "additive", "padding", "causal", "dead_rows"])
 @pytest.mark.parametrize("shape", [(2, 3, 5, 5, 4), (1, 2, 7, 3, 5)], ids=lambda s: "x".join(map(str, s)))
 def test_two_node_graph_matches_the_written_out_attention_fp64(restatement, shape, kind):
     B, H, L, S, d = shape
@@ -281,3 +284,12 @@ def test_inputs_outside_the_family_return_the_torch_functions_bits_on_the_gpu():
     c0 = bnn.declared_attention_calls()
     bnn.scaled_dot_product_attention(q, k, v, attn_mask=torch.ones(5, 6, dtype=torch.bool, device=DEV))   # and the declared route is live
     assert bnn.declared_attention_calls()["forward"] == c0["forward"] + 1
+
+
+@pytest.mark.gpu
+def test_fully_masked_rows_through_multihead_attention_match_the_math_path():
+    """A left-padded sequence under a causal mask (tests/attention_dead_rows.py): 2 x 40 tokens, 4 heads of 16."""
+    c0 = bnn.declared_attention_calls()
+    attention_dead_rows.assert_route_matches_the_math_path({}, 64, 4, 40, DEV, GATE, "short route")
+    calls = {key: n - c0[key] for key, n in bnn.declared_attention_calls().items()}
+    assert calls["forward"] == 1 and calls["backward"] >= 1 and calls["backward_vjp"] >= 1, calls

@@ -9,6 +9,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import attention_dead_rows
 import attention_ref
 from conftest import rel_err
 
@@ -87,6 +88,16 @@ def test_multihead_attention_reaches_the_route():
     assert bnn.declared_attention_fused_calls()["forward"] == c0["forward"] + 1
     want = mha.double()(x.double(), x.double(), x.double(), need_weights=False)[0]
     assert max(rel_err([got.detach().cpu().numpy()], [want.detach().cpu().numpy()])) <= GATE
+
+
+@pytest.mark.gpu
+def test_fully_masked_rows_through_multihead_attention_match_the_math_path():
+    """A left-padded sequence under a causal mask (tests/attention_dead_rows.py): 2 x 70 tokens, 4 heads of 16."""
+    c0 = bnn.declared_attention_fused_calls(), bnn.declared_attention_tiled_calls(), bnn.declared_attention_calls()
+    attention_dead_rows.assert_route_matches_the_math_path({"fused": True}, 64, 4, 70, DEV, GATE, "fused route")
+    fused = {key: n - c0[0][key] for key, n in bnn.declared_attention_fused_calls().items()}
+    assert fused["forward"] == 1 and fused["backward"] >= 1 and fused["backward_vjp"] >= 1, fused
+    assert (bnn.declared_attention_tiled_calls(), bnn.declared_attention_calls()) == c0[1:]
 
 
 def test_outside_the_family_it_is_the_torch_function():

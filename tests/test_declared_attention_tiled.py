@@ -18,6 +18,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 from torch.nn.attention import SDPBackend, sdpa_kernel
 
+import attention_dead_rows
 import attention_ref
 import attention_tiled_ref
 import zoo
@@ -79,6 +80,8 @@ def _mask(kind, B, L, S):
         m = torch.zeros(B, 1, 1, S, dtype=torch.float64)
         m[::2, :, :, :40] = float("-inf")          # a whole key tile and more
         return m, False
+    if kind == "dead_rows":                            # left padding under the triangle: rows 0 .. 39 of the last batch element are dead
+        return attention_dead_rows.dead_rows_mask(B, L, S, 40)[0], False
     return None, kind == "causal"
 
 
@@ -91,7 +94,7 @@ def _counters():
     return bnn.declared_attention_calls(), bnn.declared_attention_tiled_calls()
 
 
-@pytest.mark.parametrize("kind", ["none", "additive", "padding", "causal"])
+@pytest.mark.parametrize("kind", ["none", "additive", "padding", "causal", "dead_rows"])
 def test_two_node_graph_matches_the_written_out_attention_fp64(restatement, kind):
     B, H, L, S, d = SHAPE
     qkv = _inputs(*SHAPE)
@@ -327,3 +330,12 @@ def test_hypergradient_through_tiled_attention_matches_the_undeclared_problem(al
     rel, _ = rel_err(out["declared"], out["math"])
     print(f"{algo} hypergradient (K = 5), tiled attention declared vs undeclared: {rel:.2e}")
     assert rel <= GATE, rel
+
+
+@pytest.mark.gpu
+def test_fully_masked_rows_through_multihead_attention_match_the_math_path():
+    """A left-padded sequence under a causal mask (tests/attention_dead_rows.py): 2 x 70 tokens, 4 heads of 16."""
+    c0 = _counters()
+    attention_dead_rows.assert_route_matches_the_math_path({"tiled": True}, 64, 4, 70, DEV, GATE, "tiled route")
+    short, tiled = _delta(c0)
+    assert tiled["forward"] == 1 and tiled["backward"] >= 1 and tiled["backward_vjp"] >= 1 and not any(short.values()), (short, tiled)

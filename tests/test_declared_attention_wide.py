@@ -13,6 +13,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 from torch.nn.attention import SDPBackend, sdpa_kernel
 
+import attention_dead_rows
 import attention_ref
 import attention_tiled_ref
 from betty_amd import nn as bnn
@@ -61,11 +62,14 @@ def _worst(got, want):
 
 
 @pytest.mark.parametrize("kind,needs", [("none", (True, True, True)), ("causal", (True, True, True)), ("additive", (True, True, True)),
-                                        ("none", (True, True, False)), ("none", (False, True, True))])
+                                        ("none", (True, True, False)), ("none", (False, True, True)),
+                                        ("dead_rows", (True, True, True))])   # (new cases go last: the ids count the positions)
 def test_two_node_graph_matches_the_written_out_attention_fp64(restatement, kind, needs):
     B, H, L, S, d = SHAPE
     qkv = _inputs(*SHAPE)
     mask = torch.randn(B, 1, L, S, generator=torch.Generator().manual_seed(5), dtype=torch.float64) if kind == "additive" else None
+    if kind == "dead_rows":                            # left padding under the triangle: rows 0 .. 4 of the last batch element are dead
+        mask = attention_dead_rows.dead_rows_mask(B, L, S, 5)[0]
     expanded, causal = None if mask is None else mask.expand(B, H, L, S), kind == "causal"
     c0 = bnn.declared_attention_wide_calls(), bnn.declared_attention_calls(), bnn.declared_attention_tiled_calls()
     want = _grad_and_hvp(lambda q, k, v: attention_ref.attention(q, k, v, mask, causal), qkv, needs)
@@ -184,3 +188,14 @@ def test_gradient_and_hvp_against_the_math_path_and_float64(which):
           f"(worst tensor of max|diff| / max|want|): declared {e_decl:.2e}, undeclared fp32 {e_plain:.2e}")
     assert e_first <= 1e-5, e_first
     assert e_decl <= 4.0 * e_plain or e_decl <= 2e-5, (e_decl, e_plain)
+
+
+@pytest.mark.gpu
+def test_fully_masked_rows_through_multihead_attention_match_the_math_path():
+    """A left-padded sequence under a causal mask (tests/attention_dead_rows.py): 2 x 70 tokens, 2 heads of 80.  Gate: the package's
+    parity gate, 1e-4, as in the siblings' files."""
+    c0 = bnn.declared_attention_wide_calls(), bnn.declared_attention_calls(), bnn.declared_attention_tiled_calls()
+    attention_dead_rows.assert_route_matches_the_math_path({"wide": True}, 160, 2, 70, DEV, 1e-4, "wide route")
+    wide = {key: n - c0[0][key] for key, n in bnn.declared_attention_wide_calls().items()}
+    assert wide["forward"] == 1 and wide["backward"] >= 1 and wide["backward_vjp"] >= 1, wide
+    assert (bnn.declared_attention_calls(), bnn.declared_attention_tiled_calls()) == c0[1:]
