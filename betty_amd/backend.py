@@ -604,6 +604,18 @@ def attention_wide_plan(B: int, H: int, L: int, S: int, d: int, vec_ok: bool = T
     return {k: int(v) for k, v in re.findall(r"(\w+)=(-?\d+)", buf.value.decode())}
 
 
+def attention_gqa_plan(B: int, Hq: int, Hkv: int, L: int, S: int, d: int, vec_ok: bool = True) -> dict:
+    """What bhg_attention_gqa_backward_vjp takes for B batches of Hq = g Hkv query heads on Hkv key/value heads (g >= 2), L <= 512
+    queries, S <= 512 keys, d <= 64 elements and g L <= 4096, as a dict: ``g``, ``rows`` (g L packed query rows per key/value head),
+    ``vec``, ``bm`` x ``bn``, ``dp``, ``pd``, ``ps`` (as for the tiled sibling), ``grid_q`` / ``grid_k`` and ``lds_q`` / ``lds_k``
+    (workgroups and bytes of dynamic LDS of the two launches, <= ``max_lds``) and ``ws`` (bytes of workspace) (include/bhg.h:
+    bhg_attention_gqa_plan — host logic only).  A shape the launch refuses raises."""
+    buf = ctypes.create_string_buffer(256)
+    _native.check(_native.load().bhg_attention_gqa_plan(int(B), int(Hq), int(Hkv), int(L), int(S), int(d), 1 if vec_ok else 0, buf, 256),
+                  "bhg_attention_gqa_plan")
+    return {k: int(v) for k, v in re.findall(r"(\w+)=(-?\d+)", buf.value.decode())}
+
+
 _backend = None
 _override = None
 

@@ -26,7 +26,8 @@ attention core for short sequences: a function and a context manager, because at
 ``tiled_scaled_dot_product_attention`` / ``declared_attention(tiled=True)`` extend it to 512 tokens (opt-in), and
 ``wide_scaled_dot_product_attention`` / ``declared_attention(wide=True)`` to heads of 65 to 128 elements (opt-in);
 ``fused_scaled_dot_product_attention`` / ``declared_attention(fused=True)`` give the tiled family a native forward and first backward
-that save no probability matrix (opt-in).  ``gelu``, ``silu``,
+that save no probability matrix (opt-in); ``gqa_scaled_dot_product_attention`` / ``declared_attention(gqa=True)`` declare grouped-query
+heads (``enable_gqa=True``, fewer key/value heads than query heads; opt-in).  ``gelu``, ``silu``,
 ``tanh``, ``sigmoid``, ``softplus``, ``glu`` and ``gated_activation`` (at the very end) declare the smooth activations: functions,
 ``declared_activations()`` as a context manager and ``declare_activations_(module)`` / ``declare_layers_(module, activations=True)``.
 ``cross_entropy`` / ``declared_cross_entropy()`` / ``DeclaredCrossEntropyLoss`` / ``declare_layers_(module, cross_entropy=True)`` (after
@@ -36,6 +37,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes
+import functools
 import math
 
 import torch
@@ -49,6 +51,7 @@ __all__ = ["FusedBatchNorm2d", "fuse_batchnorm_", "fused_batchnorm_calls", "Poin
            "scaled_dot_product_attention", "declared_attention", "declared_attention_calls", "tiled_scaled_dot_product_attention",
            "declared_attention_tiled_calls", "wide_scaled_dot_product_attention", "declared_attention_wide_calls",
            "fused_scaled_dot_product_attention", "declared_attention_fused_calls",
+           "gqa_scaled_dot_product_attention", "declared_attention_gqa_calls",
            "gelu", "silu", "tanh", "sigmoid", "softplus", "glu", "gated_activation", "declare_activations_", "declared_activations",
            "declared_activation_calls", "DeclaredGELU", "DeclaredSiLU", "DeclaredTanh", "DeclaredSigmoid", "DeclaredSoftplus", "DeclaredGLU",
            "cross_entropy", "declared_cross_entropy", "declared_cross_entropy_calls", "DeclaredCrossEntropyLoss", "declare_cross_entropy_"]
@@ -853,14 +856,16 @@ def _attn_wide_vjp_hip(q, k, v, go, aq, ak, av, mask, causal, scale, need):
     return _attn_vjp_launch(q, k, v, go, aq, ak, av, mask, causal, scale, need, "bhg_attention_wide")
 
 
-def _attn_vjp_launch(q, k, v, go, aq, ak, av, mask, causal, scale, need, family):
+def _attn_vjp_launch(q, k, v, go, aq, ak, av, mask, causal, scale, need, family, grouped=False):
     """``family`` picks the entry point: None for bhg_attention_backward_vjp, otherwise the prefix of a sibling with a workspace
-    (``<family>_ws_bytes`` and ``<family>_backward_vjp``)."""
+    (``<family>_ws_bytes`` and ``<family>_backward_vjp``).  ``grouped``: k, v, ak, av have their own number of heads, which the entry
+    point takes behind the query's."""
     if not q.is_cuda:
         raise _native.NativeLibraryError("declared attention's double backward needs CUDA/HIP tensors; there is no CPU fallback")
     lib = _native.load()
     B, H, L, d = q.shape
-    S = k.shape[2]
+    Hkv, S = k.shape[1:3]
+    heads = (H, Hkv) if grouped else (H,)
 
     def prep(t, shape):
         if t is None:
@@ -874,7 +879,7 @@ def _attn_vjp_launch(q, k, v, go, aq, ak, av, mask, causal, scale, need, family)
             t = t.contiguous() if not t.is_contiguous() else t.clone()
         return t
 
-    lshape, sshape = (B, H, L, d), (B, H, S, d)
+    lshape, sshape = (B, H, L, d), (B, Hkv, S, d)
     ins = [prep(t, sh) for t, sh in zip((q, k, v, go, aq, ak, av), (lshape, sshape, sshape, lshape, lshape, sshape, sshape))]
     strides = (ctypes.c_longlong * 28)()
     for i, t in enumerate(ins):
@@ -891,7 +896,7 @@ def _attn_vjp_launch(q, k, v, go, aq, ak, av, mask, causal, scale, need, family)
             ws = _attn_tiled_workspace(q.device, int(getattr(lib, family + "_ws_bytes")(B, H, L)))
             _native.check(
                 getattr(lib, family + "_backward_vjp")(*(ptr(t) for t in ins), strides, ptr(mask), mstrides, 1 if causal else 0, float(scale),
-                                                       B, H, L, S, d, *(ptr(t) for t in outs), ws.data_ptr(), ws.numel(), _stream()),
+                                                       B, *heads, L, S, d, *(ptr(t) for t in outs), ws.data_ptr(), ws.numel(), _stream()),
                 family + "_backward_vjp")
         else:
             _native.check(
@@ -1135,18 +1140,100 @@ class _AttnFusedForward(torch.autograd.Function):
         return gq, gk, gv, None, None, None
 
 
-def _declared_mask(q, k, v, attn_mask, dropout_p, is_causal, kw, max_len=_ATTN_MAX, max_d=_ATTN_MAX):
+# Grouped-query heads (opt-in): Hq = g Hkv query heads, query head h reading key/value head h // g (torch's enable_gqa).  The g heads of a
+# group share K and V, so per (batch, kv head) they are ONE attention with g L query rows: forward and first backward run in torch
+# operations on that packed (B, Hkv, g L, .) form — K and V are never repeated and gk, gv come out already summed over the group — and
+# the backward node's own backward is ONE bhg_attention_gqa_backward_vjp call (csrc/bhg_attention_gqa.hip: the tiled sibling's two
+# launches over packed rows, dk and dv accumulated over the whole group in registers).  No CPU fallback for the kernel.
+_ATTN_GQA_CALLS = {"forward": 0, "backward": 0, "backward_vjp": 0}
+_ATTN_GQA_ROWS = 4096   # g L of the family bhg_attention_gqa_backward_vjp takes
+# The largest measured length up to which no measured shape is slower declared than the torch function with enable_gqa=True on the math
+# path, beyond that comparator's spread (profiles/attention_gqa_double_backward.txt: 16 x (32 on 4) x n x n x 64 declared / torch, us:
+# 178 / 600 at n = 64, 391 / 706 at 128, 1378 / 2002 at 256, 5240 / 6592 at 512; 9 on 3 and 8 on 1 at 256, causal and padding as well).
+_ATTN_GQA_MAX = 512
+
+
+def declared_attention_gqa_calls() -> dict:
+    return dict(_ATTN_GQA_CALLS)
+
+
+def _attn_gqa_vjp_hip(q, k, v, go, aq, ak, av, mask, causal, scale, need):
+    """(dq, dk, dv, dgo) through bhg_attention_gqa_backward_vjp: q, go, aq with Hq heads, k, v, ak, av with Hkv, all read in place."""
+    return _attn_vjp_launch(q, k, v, go, aq, ak, av, mask, causal, scale, need, "bhg_attention_gqa", grouped=True)
+
+
+_ATTN_GQA_VJP_IMPL = [_attn_gqa_vjp_hip]   # TEST HOOK ONLY (tests/test_declared_attention_gqa.py swaps in the float64 restatement)
+
+
+def _attn_gqa_pack(t, Hkv):
+    """(B, Hq, L, n) -> (B, Hkv, g L, n): the query heads of a group packed into the rows (a view where (Hq, L) is contiguous)."""
+    B, Hq, L, n = t.shape
+    return t.reshape(B, Hkv, Hq // Hkv * L, n)
+
+
+class _AttnGqaBackward(torch.autograd.Function):
+    """(q, k, v, go) -> (gq, gk, gv) on the packed form; its own backward is ONE bhg_attention_gqa_backward_vjp call."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, go, P, mask, causal, scale):
+        _ATTN_GQA_CALLS["backward"] += 1
+        Hkv = k.shape[1]
+        gop, Pp = _attn_gqa_pack(go, Hkv), _attn_gqa_pack(P, Hkv)
+        gP = (gop @ v.transpose(-1, -2)).view(P.shape)
+        gS = _attn_gqa_pack(P * (gP - (P * gP).sum(-1, keepdim=True)), Hkv)
+        gq, gk, gv = ((gS @ k) * scale).view(q.shape), (gS.transpose(-1, -2) @ _attn_gqa_pack(q, Hkv)) * scale, Pp.transpose(-1, -2) @ gop
+        ctx.save_for_backward(q, k, v, go, mask)
+        ctx.causal, ctx.scale = causal, scale
+        ctx.set_materialize_grads(False)
+        return gq, gk, gv
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, aq, ak, av):
+        return _attn_double_backward(ctx, _ATTN_GQA_CALLS, _ATTN_GQA_VJP_IMPL, aq, ak, av)
+
+
+class _AttnGqaForward(torch.autograd.Function):
+    """Grouped-query attention on ATen's kernels, packed; saves P as (B, Hq, L, S).  Its backward is the node above."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, mask, causal, scale):
+        _ATTN_GQA_CALLS["forward"] += 1
+        B, Hq, L, d = q.shape
+        Hkv, S = k.shape[1:3]
+        sc = ((_attn_gqa_pack(q, Hkv) @ k.transpose(-1, -2)) * scale).view(B, Hq, L, S)
+        if mask is not None:
+            sc = sc + mask
+        if causal:
+            sc = sc.masked_fill(torch.ones(L, S, dtype=torch.bool, device=sc.device).triu(1), float("-inf"))
+        P = torch.softmax(sc, dim=-1) if mask is None else torch._safe_softmax(sc, dim=-1)   # fully masked rows: P = 0 (see _attn_forward)
+        ctx.save_for_backward(q, k, v, P, mask)
+        ctx.causal, ctx.scale = causal, scale
+        return (_attn_gqa_pack(P, Hkv) @ v).view(B, Hq, L, d)
+
+    @staticmethod
+    def backward(ctx, go):
+        q, k, v, P, mask = ctx.saved_tensors
+        gq, gk, gv = _AttnGqaBackward.apply(q, k, v, go, P, mask, ctx.causal, ctx.scale)
+        return gq, gk, gv, None, None, None
+
+
+def _declared_mask(q, k, v, attn_mask, dropout_p, is_causal, kw, max_len=_ATTN_MAX, max_d=_ATTN_MAX, gqa=False):
     """False when the call is outside the declared family (at most ``max_len`` queries and keys, at most ``max_d`` elements per head);
-    otherwise the additive fp32 mask as a (B, H, L, S) view, or None."""
-    if kw.pop("enable_gqa", False) or kw:
+    otherwise the additive fp32 mask as a (B, H, L, S) view, or None.  ``gqa``: the grouped-query family instead — ``enable_gqa=True``
+    and k, v with 1 / g of the query's heads, g >= 2 and g L <= ``_ATTN_GQA_ROWS``."""
+    enable_gqa = kw.pop("enable_gqa", False)
+    if (enable_gqa is not True if gqa else enable_gqa) or kw:
         return False
     if not (torch.is_grad_enabled() and dropout_p == 0.0 and all(torch.is_tensor(t) for t in (q, k, v))):
         return False
     if not all(t.is_cuda and t.dtype == torch.float32 and t.dim() == 4 and t.device == q.device and not t.is_nested for t in (q, k, v)):
         return False
     B, H, L, d = q.shape
-    S = k.shape[2]
-    if not (tuple(k.shape) == (B, H, S, d) and tuple(v.shape) == (B, H, S, d) and B >= 1 and H >= 1 and B * H < 2 ** 31):
+    Hkv, S = k.shape[1:3]
+    if not (tuple(k.shape) == (B, Hkv, S, d) and tuple(v.shape) == (B, Hkv, S, d) and B >= 1 and Hkv >= 1 and B * H < 2 ** 31):
+        return False
+    if not (H % Hkv == 0 and H // Hkv >= 2 and H // Hkv * L <= _ATTN_GQA_ROWS if gqa else H == Hkv):
         return False
     if not (1 <= L <= max_len and 1 <= S <= max_len and 1 <= d <= max_d):
         return False
@@ -1226,21 +1313,50 @@ def _wide_or_fused_scaled_dot_product_attention(query, key, value, attn_mask=Non
         query, key, value, attn_mask=attn_mask, dropout_p=dropout_p, is_causal=is_causal, scale=scale, **kw)
 
 
+def _gqa_or(rest, query, key, value, attn_mask=None, dropout_p=0.0, is_causal=False, scale=None, **kw):
+    """Grouped calls (``enable_gqa=True`` and fewer key/value heads than query heads) take the grouped-query family; every other call
+    IS ``rest`` (with equal heads ``enable_gqa`` means nothing and is not passed on)."""
+    heads = [t.shape[1] if torch.is_tensor(t) and t.dim() == 4 else None for t in (query, key)]
+    if kw.get("enable_gqa", False) is not True or None in heads or heads[0] == heads[1]:
+        if kw.get("enable_gqa", False) is True and None not in heads:
+            kw = {name: val for name, val in kw.items() if name != "enable_gqa"}
+        return rest(query, key, value, attn_mask=attn_mask, dropout_p=dropout_p, is_causal=is_causal, scale=scale, **kw)
+    mask = _declared_mask(query, key, value, attn_mask, dropout_p, is_causal, dict(kw), min(_ATTN_GQA_MAX, _ATTN_TILED_MAX), gqa=True)
+    if mask is False:
+        return _TORCH_SDPA(query, key, value, attn_mask=attn_mask, dropout_p=dropout_p, is_causal=is_causal, scale=scale, **kw)
+    s = 1.0 / math.sqrt(query.shape[-1]) if scale is None else float(scale)
+    return _AttnGqaForward.apply(query, key, value, mask, bool(is_causal), s)
+
+
+def gqa_scaled_dot_product_attention(query, key, value, attn_mask=None, dropout_p=0.0, is_causal=False, scale=None, **kw):
+    """``tiled_scaled_dot_product_attention`` above, whose declared family also takes grouped-query heads: with ``enable_gqa=True`` and
+    Hq = g Hkv query heads on Hkv < Hq key/value heads (query head h reads key/value head h // g), at most ``_ATTN_GQA_MAX`` queries and
+    keys, d <= 64, g L <= 4096 and every other condition as above, the double backward is one bhg_attention_gqa_backward_vjp call on the
+    un-repeated K and V, counted by ``declared_attention_gqa_calls()``.  Without ``enable_gqa`` or with Hq == Hkv it IS the function
+    above: the same nodes, the same counters.  Anything else IS the torch function with the caller's arguments, errors included."""
+    return _gqa_or(tiled_scaled_dot_product_attention, query, key, value, attn_mask=attn_mask, dropout_p=dropout_p, is_causal=is_causal,
+                   scale=scale, **kw)
+
+
 @contextlib.contextmanager
-def declared_attention(tiled: bool = False, wide: bool = False, fused: bool = False):
+def declared_attention(tiled: bool = False, wide: bool = False, fused: bool = False, gqa: bool = False):
     """Inside the context ``torch.nn.functional.scaled_dot_product_attention`` is the function above: ``nn.MultiheadAttention``,
     ``nn.TransformerEncoder`` and model code that calls the torch function reach the declaration without being rewritten, and
     ``sdpa_kernel(MATH)`` is not needed for shapes in the family.  ``tiled=True`` installs ``tiled_scaled_dot_product_attention``
     instead (sequences of up to ``_ATTN_TILED_MAX`` tokens), ``wide=True`` ``wide_scaled_dot_product_attention`` (that, and heads of up
     to ``_ATTN_WIDE_MAX_D`` elements), ``fused=True`` ``fused_scaled_dot_product_attention`` (the tiled family with a native forward and
     first backward that save no probability matrix; with ``wide=True`` as well, heads of more than 64 elements still take the wide
-    function).  Only the forward that records the graph has to run inside; the
+    function), ``gqa=True`` ``gqa_scaled_dot_product_attention`` (the tiled family and grouped-query heads; with ``fused=True`` and / or
+    ``wide=True`` as well, grouped calls take the grouped-query function and the rest go where those flags send them).  Only the forward that records the graph has to run inside; the
     solve's double backward runs wherever it runs.  Restored on exit, exceptions included; nesting is safe."""
     F = torch.nn.functional
     previous = F.scaled_dot_product_attention
-    F.scaled_dot_product_attention = (_wide_or_fused_scaled_dot_product_attention if wide and fused else
-                                      fused_scaled_dot_product_attention if fused else wide_scaled_dot_product_attention if wide else
-                                      tiled_scaled_dot_product_attention if tiled else scaled_dot_product_attention)
+    chosen = (_wide_or_fused_scaled_dot_product_attention if wide and fused else
+              fused_scaled_dot_product_attention if fused else wide_scaled_dot_product_attention if wide else
+              tiled_scaled_dot_product_attention if tiled else scaled_dot_product_attention)
+    if gqa:
+        chosen = functools.partial(_gqa_or, chosen) if wide or fused else gqa_scaled_dot_product_attention
+    F.scaled_dot_product_attention = chosen
     try:
         yield
     finally:

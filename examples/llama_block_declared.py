@@ -10,7 +10,8 @@ training_step stays OPAQUE — the Hessian-vector products are autograd's double
     (csrc/bhg_rmsnorm.hip, at most two launches) instead of ATen's decomposition;
   * the attention core by running the forward inside `betty_amd.nn.declared_attention()`, which F.scaled_dot_product_attention(...,
     is_causal=True) then reaches (`tiled=True` for sequences of more than 64 tokens; `wide=True` for heads of more than 64 elements,
-    `--width 256 --heads 2` for LLaMA's 128);
+    `--width 256 --heads 2` for LLaMA's 128; `gqa=True` with `--kv-heads N`, fewer key/value heads than query heads: K and V are
+    projected to N heads and handed over un-repeated with enable_gqa=True);
   * SwiGLU by calling `betty_amd.nn.gated_activation(gate, up, "silu")` where the block would have written F.silu(gate) * up.
 
     python examples/llama_block_declared.py --k 5 --iters 10 [--undeclared]
@@ -32,20 +33,24 @@ from betty_amd.problems import ImplicitProblem  # noqa: E402
 
 DECLARED = [True]
 FUSED = [False]   # --fused
+KV_HEADS = [0]    # --kv-heads: 0 = as many as query heads (multi-head attention)
 
 
 class Block(nn.Module):
     def __init__(self, width, heads, ffn):
         super().__init__()
-        self.heads = heads
-        self.norm1, self.qkv, self.proj = nn.RMSNorm(width), nn.Linear(width, 3 * width, bias=False), nn.Linear(width, width, bias=False)
+        self.heads, self.kv_heads = heads, KV_HEADS[0] or heads
+        self.norm1, self.proj = nn.RMSNorm(width), nn.Linear(width, width, bias=False)
+        self.qkv = nn.Linear(width, width + 2 * self.kv_heads * (width // heads), bias=False)
         self.norm2, self.gate, self.up = nn.RMSNorm(width), nn.Linear(width, ffn, bias=False), nn.Linear(width, ffn, bias=False)
         self.down = nn.Linear(ffn, width, bias=False)
 
     def forward(self, x):
         B, T, W = x.shape
-        q, k, v = (t.reshape(B, T, self.heads, W // self.heads).transpose(1, 2) for t in self.qkv(self.norm1(x)).chunk(3, dim=-1))
-        h = x + self.proj(F.scaled_dot_product_attention(q, k, v, is_causal=True).transpose(1, 2).reshape(B, T, W))
+        d, kv = W // self.heads, self.kv_heads * (W // self.heads)
+        q, k, v = (t.reshape(B, T, -1, d).transpose(1, 2) for t in self.qkv(self.norm1(x)).split((W, kv, kv), dim=-1))
+        gqa = {"enable_gqa": True} if self.kv_heads != self.heads else {}
+        h = x + self.proj(F.scaled_dot_product_attention(q, k, v, is_causal=True, **gqa).transpose(1, 2).reshape(B, T, W))
         n = self.norm2(h)
         gate, up = self.gate(n), self.up(n)
         return h + self.down(bnn.gated_activation(gate, up, "silu") if DECLARED[0] else F.silu(gate) * up)
@@ -63,7 +68,7 @@ class Decoder(nn.Module):
             with torch.nn.attention.sdpa_kernel(torch.nn.attention.SDPBackend.MATH):
                 return self.head(self.norm(self.blocks(self.embed(tokens)))[:, -1])
         wide = self.embed.embedding_dim // self.blocks[0].heads > 64
-        with bnn.declared_attention(tiled=tokens.shape[1] > 64, wide=wide, fused=FUSED[0]):   # only the forward that records the graph has to run inside
+        with bnn.declared_attention(tiled=tokens.shape[1] > 64, wide=wide, fused=FUSED[0], gqa=bool(KV_HEADS[0])):   # only the forward that records the graph has to run inside
             return self.head(self.norm(self.blocks(self.embed(tokens)))[:, -1])
 
 
@@ -105,8 +110,9 @@ def main():
     ap.add_argument("--heads", type=int, default=4)
     ap.add_argument("--undeclared", action="store_true", help="leave every layer undeclared (the A/B arm)")
     ap.add_argument("--fused", action="store_true", help="attention's forward and first backward native as well (declared_attention(fused=True))")
+    ap.add_argument("--kv-heads", type=int, default=0, help="grouped-query attention with this many key/value heads (declared_attention(gqa=True))")
     args = ap.parse_args()
-    DECLARED[0], FUSED[0] = not args.undeclared, args.fused
+    DECLARED[0], FUSED[0], KV_HEADS[0] = not args.undeclared, args.fused, args.kv_heads
     torch.manual_seed(0)
     g = torch.Generator().manual_seed(1)
     vocab, classes = 32, 8
@@ -127,6 +133,7 @@ def main():
                     dependencies={"u2l": {upper: [inner]}, "l2u": {inner: [upper]}})
     c0 = (bnn.fused_rmsnorm_calls(), bnn.declared_attention_calls(), bnn.declared_activation_calls())
     wide0, fused0 = bnn.declared_attention_wide_calls()["backward_vjp"], bnn.declared_attention_fused_calls()
+    gqa0 = bnn.declared_attention_gqa_calls()["backward_vjp"]
     t0 = time.perf_counter()
     engine.run()
     if torch.cuda.is_available():
@@ -140,6 +147,9 @@ def main():
           f"SwiGLU {act}; meta-weight-net finite {finite}")
     if args.fused:
         print(f"fused attention nodes: {({key: n - fused0[key] for key, n in bnn.declared_attention_fused_calls().items()})}")
+    if args.kv_heads:
+        print(f"{args.heads} query heads on {args.kv_heads} key/value heads: grouped-query attention double-backward calls "
+              f"{bnn.declared_attention_gqa_calls()['backward_vjp'] - gqa0}")
     if args.width // args.heads > 64:
         print(f"heads of {args.width // args.heads} elements: wide attention double-backward calls {bnn.declared_attention_wide_calls()['backward_vjp'] - wide0}")
 

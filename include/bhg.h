@@ -875,6 +875,35 @@ int bhg_attention_fused_backward(const float* q, const float* k, const float* v,
                                  int B, int H, int L, int S, int d, float* gq, float* gk, float* gv, void* ws, size_t ws_bytes,
                                  void* stream);
 
+/* ---- the attention core with grouped-query heads (csrc/bhg_attention_gqa.hip) -------------------------------------------------------------
+ * The same vector-Jacobian product, quantities, tiles, arithmetic and workspace as bhg_attention_tiled_backward_vjp, for Hq = g Hkv query
+ * heads on Hkv key/value heads, g >= 2: q, go, aq (and dq, dgo) are (B, Hq, L, d), k, v, ak, av (and dk, dv) are (B, Hkv, S, d), and query
+ * head h reads key/value head h / g (torch's enable_gqa, i.e. repeat_interleave(g, dim = 1)); dk and dv are summed over each group.
+ * 1 <= L, S <= 512, 1 <= d <= 64, g L <= 4096.  The g query heads of a (batch, kv head) are ONE attention with g L packed query rows,
+ * r = j L + i for row i of the group's j-th head.  TWO launches:
+ *   1  grid B Hkv ceil(g L / 64), 64 PACKED rows per workgroup (a tile may span several query heads): the online pass for m, l, D, E, R
+ *      and the second sweep for dq and dgo (skipped when both are NULL), as in the tiled sibling;
+ *   2  grid B Hkv ceil(S / 32), 32 keys per workgroup, K, V, aK, aV loaded once per group: sweeps all ceil(g L / 64) packed query tiles
+ *      with the statistics of launch 1 and accumulates dk and dv in registers over the whole group (not launched when both are NULL).
+ * A packed row is addressed as (head = g kvh + r / L, row = r % L) with the head and row strides of its input, so (Hq, L) need not be
+ * contiguous; the mask, viewed as (B, Hq, L, S) with stride-0 broadcast, is read at (b, head, row, .); the causal bound of a packed row
+ * is its `row` (top-left aligned, j <= row).  Fully masked rows have probability zero.  No atomics, no g-fold partial results, no
+ * reduction pass: deterministic.  Asynchronous on `stream`, no host synchronisation.
+ * `strides` holds four element strides for each of q, k, v, go, aq, ak, av (28 entries).  Workspace `ws`:
+ * bhg_attention_gqa_ws_bytes(B, Hq, L) = 40 B Hq L bytes, 8-byte aligned: (B, Hq, L) rows of [m, l, D, E, R] (0 for sizes <= 0).
+ * Refused with -1 and a message, before any device access: everything the tiled sibling refuses, with its words; Hq not a multiple of
+ * Hkv; g = 1 (the message names bhg_attention_tiled_backward_vjp); g L > 4096.
+ *
+ * bhg_attention_gqa_plan is host logic only, answered by the very function the launch calls, one line of `key=value` pairs: g, rows = g L,
+ * vec, bm = 64, bn = 32, dp, pd = dp + 4, ps = 36, grid_q = B Hkv ceil(rows / 64), grid_k = B Hkv ceil(S / 32), lds_q and lds_k (the
+ * tiled sibling's: 123904 and 114688 bytes at dp = 64, <= max_lds = 163840), ws (bytes).                                                 */
+size_t bhg_attention_gqa_ws_bytes(int B, int Hq, int L);
+int bhg_attention_gqa_plan(int B, int Hq, int Hkv, int L, int S, int d, int vec_ok, char* buf, size_t buf_bytes);
+int bhg_attention_gqa_backward_vjp(const float* q, const float* k, const float* v, const float* go, const float* aq, const float* ak,
+                                   const float* av, const long long* strides, const float* mask, const long long* mask_strides,
+                                   int causal, float scale, int B, int Hq, int Hkv, int L, int S, int d, float* dq, float* dk, float* dv,
+                                   float* dgo, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- smooth activations, plain and gated: their share of a Hessian-vector product (csrc/bhg_activation.hip) ----------------------------
  * Plain, y = f(x): the first backward is F : (x, gy) -> gx = gy f'(x).  bhg_act_backward_vjp is its vector-Jacobian product: for a
  * cotangent a of gx,      dgy = a f'(x)      dx = a gy f''(x).
